@@ -16,7 +16,7 @@ smoke: build
 	$(PY) -c "import __graft_entry__ as g; g.smoke()"
 
 bench: build      ## one JSON line: pairs/s, users/s, rooflines, CPU baseline
-	$(PY) bench.py
+	$(PY) bench.py --full
 
 example: build    ## the C ABI from plain C99
 	gcc -std=c99 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude examples/c_abi_demo.c -Lelliot_amd/csrc -lelliot_hip \

@@ -3,7 +3,13 @@
 
 One JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run measures the headline figure only: it builds the inputs, warms up with W training steps, times EXACTLY K training
+steps once (no events, no repeats) and prints the line (`value` = pairs/s, `ms_per_step` = milliseconds of one timed step).
+--full adds everything described below: the per-kernel breakdown pass, the median of --repeats timed repeats, the rooflines,
+the top-k block, the secondary legs and the CPU baseline.  --dump-outputs DIR writes what the last timed training step left
+behind (the model tables, a fixed seeded sample of rows of a large table, and the loss) as DIR/<name>.npy.
 
 N = 1  workload = the shape BASELINE.json's metric / north_star quote their target on: BPRMF d=128 on synthetic 10M users x 1M items
        (SURVEY.md 8d "S-10M"; it fits one MI355X: tables + Adam slots 17 GB, positives' CSR 3.3 GB), inputs resident in HBM before
@@ -72,7 +78,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=3, help="timed repeats of K steps per leg; the median repeat is the leg's time")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything, not just the headline: per-kernel breakdown, --repeats repeats, rooflines, top-k, the other "
+                         "legs (--legs) and the CPU baseline (off: a plain run times --steps training steps once and prints the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed training step computed (model tables, a fixed seeded "
+                         "sample of rows of a large table, and the loss) as DIR/<name>.npy, float32 / float64, at most 64 MB")
+    ap.add_argument("--repeats", type=int, default=3, help="--full: timed repeats of K steps per leg; the median repeat is the leg's time")
     ap.add_argument("--users", type=int, default=10_000_000, help="headline shape: north_star's target (10M users x 1M items x 128)")
     ap.add_argument("--items", type=int, default=1_000_000)
     ap.add_argument("--factors", type=int, default=128)
@@ -98,7 +110,8 @@ def parse():
                     help="N > 1: users are independent units (no collective) / north_star's item shards + all-gather of partial "
                          "top-k (default: user for --shard user, item for the item-shard leg)")
     ap.add_argument("--legs", default="auto",
-                    help="comma list of bpr,item_shard,c2,sweep,plugin,c5,vae,neumf,graph,metrics (auto: N=1 -> all but item_shard; N>1 -> bpr,item_shard)")
+                    help="--full: comma list of bpr,item_shard,c2,sweep,plugin,c5,vae,neumf,graph,metrics (auto: N=1 -> all but item_shard; "
+                         "N>1 -> bpr,item_shard)")
     ap.add_argument("--c2-shape", default="1000000,100000", help="users,items of the c2 leg (BASELINE configs[1]; sweep and plugin legs run on its data)")
     ap.add_argument("--c5-shape", default="6250000,5000000,256",
                     help="users,items,factors of the c5 leg (BASELINE configs[4] = 50M x 5M x 256 on 8 GPUs: the per-GPU shape under user sharding)")
@@ -125,7 +138,10 @@ def parse():
     ap.add_argument("--neumf-shape", default="1250000,1000000,128,262144", help="users,items,factors,batch of the neumf leg")
     ap.add_argument("--graph-shape", default="1000000,100000,64,2", help="users,items,factors,n_layers of the graph leg (LightGCN; MF2020 beside it)")
     ap.add_argument("--neumf-topk-users", type=int, default=128, help="users per full-catalogue scoring step of the neumf leg (0: skip)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full and args.legs != "auto":
+        ap.error("--legs selects what --full measures; a plain run times the headline training step only")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -203,6 +219,7 @@ def max_over_ranks(x, world, device):
 
 
 REPEATS = 3                     # timed repeats of K steps per leg; the median is reported
+FULL = True                     # False: a plain run (main(): no --full) -- one timed pass of K steps, no breakdown pass, no events
 
 
 class _Report(dict):
@@ -223,13 +240,25 @@ def timed(ctx, world, fn, warmup, steps, finish=None, events_in_timed_region=Tru
     on every launch, taken first: it also names the dominant kernel.  fn_breakdown: the step to run in that pass when `fn`
     overlaps kernels on several streams (per-kernel elapsed times of concurrent kernels mean nothing; the breakdown is then
     of the same kernels run back to back).  Legs of 40+ short launches per step (Mult-VAE, NeuMF:
-    events_in_timed_region=False) are timed without any event."""
+    events_in_timed_region=False) are timed without any event.
+    A plain run (FULL False): W untimed calls, then ONE timed pass of exactly K calls without any event; the report is empty."""
     repeats = REPEATS if repeats is None else repeats
     for _ in range(warmup):
         fn()
     if finish:
         finish()
     barrier(world)
+    if not FULL:
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        if finish:
+            finish()
+        barrier(world)
+        dt = max_over_ranks(time.perf_counter() - t0, world, ctx.device)
+        rep = _Report()
+        rep.live, rep.repeats_ms, rep.calls = {}, [dt / steps * 1e3], warmup + steps
+        return dt, rep
     ctx.timing(True)                                             # breakdown pass (untimed)
     for _ in range(steps):
         (fn_breakdown or fn)()
@@ -297,6 +326,35 @@ def dominant(rep):
     name = max(rep, key=lambda n: rep[n][1])
     cnt, ms = getattr(rep, "live", {}).get(name, rep[name])
     return name, ms / cnt * 1e-3
+
+
+OUTPUT_TABLE_BYTES = 16 << 20   # --dump-outputs: per table; a larger table is written as a fixed, seeded sample of its rows
+
+
+def train_outputs(st, loss_per_pair, seed=0):
+    """What a caller of the timed training step holds after its last step: the model tables Gu, Gi, Bi (for a table larger than
+    OUTPUT_TABLE_BYTES, the rows <name>_rows -- a fixed seeded sample, ascending -- of it) and the loss per pair of the timed
+    steps.  float32 / float64 host arrays."""
+    out = {"loss_per_pair": np.array([loss_per_pair], dtype=np.float64)}
+    for name, t in (("Gu", st.Gu), ("Gi", st.Gi), ("Bi", st.Bi)):
+        n = int(t.shape[0])
+        rows = max(1, OUTPUT_TABLE_BYTES // (4 * (t.numel() // max(n, 1))))
+        if n > rows:
+            idx = np.sort(np.random.RandomState(seed).choice(n, rows, replace=False))
+            out[name + "_rows"] = idx.astype(np.float64)
+            t = t[torch.from_numpy(idx).to(t.device)]
+        out[name] = t.detach().float().cpu().numpy()
+    return out
+
+
+def write_outputs(outputs, path, limit=64 << 20):
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in outputs.values())
+    if total > limit:
+        raise RuntimeError(f"bench.py: --dump-outputs would write {total} bytes (limit {limit})")
+    for name, a in outputs.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def source_hash():
@@ -515,7 +573,8 @@ def replay_other_leg(args, ctx, data, replay):
 # ---------------------------------------------------------------------------------------------------------------------
 # BPR-MF leg (train + top-k), any sharding
 # ---------------------------------------------------------------------------------------------------------------------
-def bpr_leg(args, ctx, world, rank, data, shard, topk_shard, with_metrics=False, keep_host=False):
+def bpr_leg(args, ctx, world, rank, data, shard, topk_shard, with_metrics=False, keep_host=False, outputs=None):
+    """outputs: a dict that receives train_outputs() of the state right after the timed training steps (--dump-outputs)."""
     from elliot_amd import ops, parallel
     dev = ctx.device
     U, I, F, B, k = args.users, args.items, args.factors, args.batch, args.k
@@ -658,8 +717,26 @@ def bpr_leg(args, ctx, world, rank, data, shard, topk_shard, with_metrics=False,
             collectives.append(("partial top-k lists [Ub,k] (ids + scores) per block", "all_gather", 2 * world * Ub * k * 4,
                                 lambda: (coll.all_gather(part), coll.all_gather(part))))
 
+    if not sharded:
+        par = "single"
+    elif exchange == "user":
+        par = (f"user-shard x{world}: train = {B} triplets/rank for the rank's own users (item table replicated) + "
+               + (f"all-reduce of the item gradients ({I * (F + 1) * 4 / 1e6:.0f} MB)" if item_ex == "dense" else
+                  f"all-gather of the ranks' touched item-gradient rows (~{n_touch} records of {F + 2} words per rank)"))
+    else:
+        par = (f"item-shard x{world}: train = {B} triplets/rank + "
+               + ("reduce-scatter of the dense user-gradient table, optimiser on U/G user rows, all-gather of the rows"
+                  if exchange == "dense" else "all-gather of user-gradient rows") + " (weak)")
     dt_train, rep_train = timed(ctx, world, train_step, W, K, finish_train, fn_breakdown=breakdown_step)
     loss = pop_loss()
+    loss_per_pair = loss / (B * world * max(rep_train.calls, 1))
+    if outputs is not None:
+        outputs.update(train_outputs(st, loss_per_pair))
+    if not FULL:
+        # a plain run: the headline training figure only (top-k, rooflines, collectives and metrics are --full's)
+        return {"value": world * B * K / dt_train, "unit": "pairs/s", "ms_per_step": dt_train / K * 1e3,
+                "repeats_ms_per_step": rep_train.repeats_ms, "scaling": "weak", "parallelism": par, "loss_per_pair_last": loss_per_pair,
+                "interactions": int(pos.nnz)}
     prepare_topk()
     Kt = int(getattr(args, "topk_steps", 0) or K)            # (a leg whose top-k block takes 0.3 s times fewer of them than training steps)
     dt_topk, rep_topk = timed(ctx, world, topk_step, min(W, Kt), Kt)
@@ -851,16 +928,6 @@ def bpr_leg(args, ctx, world, rank, data, shard, topk_shard, with_metrics=False,
                     if screened else {}),
                  "effective_TFLOPs": flops / (dt_topk / Kt) / 1e12,
                  "kernels_ms_per_step": {n: v[1] / Kt for n, v in rep_topk.items()}}
-    if not sharded:
-        par = "single"
-    elif exchange == "user":
-        par = (f"user-shard x{world}: train = {B} triplets/rank for the rank's own users (item table replicated) + "
-               + (f"all-reduce of the item gradients ({I * (F + 1) * 4 / 1e6:.0f} MB)" if item_ex == "dense" else
-                  f"all-gather of the ranks' touched item-gradient rows (~{n_touch} records of {F + 2} words per rank)"))
-    else:
-        par = (f"item-shard x{world}: train = {B} triplets/rank + "
-               + ("reduce-scatter of the dense user-gradient table, optimiser on U/G user rows, all-gather of the rows"
-                  if exchange == "dense" else "all-gather of user-gradient rows") + " (weak)")
     topk_sharding = ("single" if not sharded else
                      f"by user: each rank scores {Ub}-user blocks of the users it owns against its replica of the item table, no collective"
                      if user_sharded else
@@ -869,7 +936,7 @@ def bpr_leg(args, ctx, world, rank, data, shard, topk_shard, with_metrics=False,
     res = {
         "value": pairs_per_s, "unit": "pairs/s", "ms_per_step": dt_train / K * 1e3, "repeats_ms_per_step": rep_train.repeats_ms,
         "scaling": "weak",
-        "parallelism": par, "loss_per_pair_last": loss / (B * world * max(rep_train.calls, 1)), "roofline": roof_train,
+        "parallelism": par, "loss_per_pair_last": loss_per_pair, "roofline": roof_train,
         "topk": {"value": users_per_s, "unit": "users/s", "ms_per_step": dt_topk / Kt * 1e3, "repeats_ms_per_step": rep_topk.repeats_ms, "steps": Kt,
                  "scaling": "weak" if (topk_by_user or user_sharded or not sharded) else "strong",
                  "sharding": topk_sharding, "roofline": roof_topk},
@@ -1357,7 +1424,7 @@ def _bpr_summary(leg):
 def compact_line(full):
     """The stdout line: the contract's fields + one-number summaries of the secondary legs.  Everything else stays in `full`."""
     line = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
-                                 "vs_baseline", "dtype", "data", "topk_users_per_s", "topk_ms_per_block", "topk_frac") if k in full}
+                                 "vs_baseline", "dtype", "data", "full", "topk_users_per_s", "topk_ms_per_block", "topk_frac") if k in full}
     cfg = full.get("config", {})
     line["config"] = {k: cfg[k] for k in ("workload", "users", "items", "factors", "interactions", "batch", "batch_per_gpu", "optimizer", "replay",
                                           "topk_block", "k", "parallelism", "world_size_observed", "backend", "collectives_through")
@@ -1367,8 +1434,9 @@ def compact_line(full):
     if "parallelism" in line["config"]:
         line["config"]["parallelism"] = line["config"]["parallelism"][:200]
     line["loss_per_pair_last"] = full.get("loss_per_pair_last")
-    line["roofline"] = _roof(full.get("roofline"), ("step_GBs_moved", "frac_back_to_back"))
-    line["topk"] = _topk_summary(full.get("topk"))
+    if "roofline" in full or "topk" in full:                     # (a plain run measures neither)
+        line["roofline"] = _roof(full.get("roofline"), ("step_GBs_moved", "frac_back_to_back"))
+        line["topk"] = _topk_summary(full.get("topk"))
     if "collectives" in full:
         line["collectives"] = [{"op": c["op"], "MB": c["bytes"] / 1e6, "ms": c["ms"], "expected_ms": c.get("expected_ms")}
                                for c in full["collectives"]]
@@ -1417,7 +1485,8 @@ def compact_line(full):
                                 "host_cpu_count": cb.get("host_cpu_count"), "sample": (cb.get("sample") or "")[:160],
                                 "topk": {k: (cb.get("topk") or {}).get(k) for k in ("value", "unit", "cores", "kind")},
                                 **({"reference": cb["reference"]} if "reference" in cb else {})}
-    line["legs_file"] = full.get("legs_file")
+    if full.get("legs_file"):
+        line["legs_file"] = full["legs_file"]
     # every non-null `traffic` in the line comes from the same place: said once
     def _any_traffic(o):
         if isinstance(o, dict):
@@ -1431,14 +1500,18 @@ def compact_line(full):
 
 
 def emit(full, args):
-    """Full objects -> bench_legs.json (repo root; + gpurun_out/ when present) and stderr; compact line -> stdout (last line)."""
+    """Full objects -> bench_legs.json (repo root, and a copy in the output folder when there is one) and stderr; compact line ->
+    stdout (last line).  A plain run (no --full) writes the report only where --legs-file asks for it."""
     if getattr(args, "legs_file", None):
         paths = [args.legs_file]
+    elif not getattr(args, "full", True):
+        paths = []
     else:
         paths = [os.path.join(REPO, "bench_legs.json" if full.get("n_gpus", 1) == 1 else f"bench_legs_n{full['n_gpus']}.json")]
         if os.path.isdir(os.path.join(REPO, "gpurun_out")):
             paths.append(os.path.join(REPO, "gpurun_out", os.path.basename(paths[0])))
-    full["legs_file"] = os.path.basename(paths[0])
+    if paths:
+        full["legs_file"] = os.path.basename(paths[0])
     blob = json.dumps(_r(full, 9))
     for p in paths:
         try:
@@ -1468,9 +1541,10 @@ def emit(full, args):
 
 
 def main():
-    global REPEATS
+    global REPEATS, FULL
     args = parse()
-    REPEATS = max(1, args.repeats)
+    FULL = args.full
+    REPEATS = max(1, args.repeats) if FULL else 1
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         sys.exit(self_launch(args))
     world, rank, local, backend = dist_setup(args)
@@ -1486,8 +1560,11 @@ def main():
     torch.cuda.set_device(dev)
     U, I, F, B, k = args.users, args.items, args.factors, args.batch, args.k
     sharded = world > 1 or args.force_sharded
-    legs = args.legs.split(",") if args.legs != "auto" else (["bpr", "item_shard"] if world > 1 else
-                                                            ["bpr", "c2", "metrics", "sweep", "plugin", "c5", "vae", "neumf", "graph"])
+    if not FULL:
+        legs = ["bpr"]                                      # a plain run: the headline training step, nothing else
+    else:
+        legs = args.legs.split(",") if args.legs != "auto" else (["bpr", "item_shard"] if world > 1 else
+                                                                ["bpr", "c2", "metrics", "sweep", "plugin", "c5", "vae", "neumf", "graph"])
 
     # ---------------- synthetic inputs, resident in HBM -------------------------------------------
     # headline: north_star's target shape (every rank builds the same CSR and keeps its part)
@@ -1497,12 +1574,13 @@ def main():
         from elliot_amd import parallel
         data["coll"] = parallel.RcclAbiCollectives(ctx, rank, world)          # RCCL through el_comm_* (one communicator for all legs)
 
-    want_cpu = world == 1 and not args.no_cpu_baseline
+    want_cpu = FULL and world == 1 and not args.no_cpu_baseline
     topk_shard = args.topk_shard or ("user" if args.shard == "user" else "item")
+    outputs = {} if args.dump_outputs and rank == 0 else None
     main_leg = bpr_leg(args, ctx, world, rank, data, args.shard, topk_shard, with_metrics="metrics" in legs and "c2" not in legs,
-                       keep_host=want_cpu and rank == 0)
+                       keep_host=want_cpu and rank == 0, outputs=outputs)
     other = None
-    if world == 1 and not args.force_sharded and args.opt == "adam_tf_dense" and "bpr" in legs:
+    if FULL and world == 1 and not args.force_sharded and args.opt == "adam_tf_dense" and "bpr" in legs:
         torch.cuda.empty_cache()
         other = replay_other_leg(args, ctx, data, "exact" if args.replay == "series" else "series")
     second = None
@@ -1564,31 +1642,33 @@ def main():
     if rank != 0:
         return
 
+    if outputs is not None:
+        write_outputs(outputs, args.dump_outputs)
     host = main_leg.pop("_host", None)
-    tk = main_leg["topk"]
+    tk = main_leg.get("topk")
     line = {
         "metric": "BPR-MF positive-pairs/sec + full-catalog top-k users/sec",
         "value": main_leg["value"], "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": main_leg["ms_per_step"], "repeats_ms_per_step": main_leg["repeats_ms_per_step"], "repeats": REPEATS,
         "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        # the second half of the metric, at the top level (the full object is "topk")
-        "topk_users_per_s": tk["value"], "topk_ms_per_block": tk["ms_per_step"], "topk_frac": tk["roofline"]["frac"],
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": FULL,
+        # the second half of the metric, at the top level (the full object is "topk"; --full only)
+        **({"topk_users_per_s": tk["value"], "topk_ms_per_block": tk["ms_per_step"], "topk_frac": tk["roofline"]["frac"]} if tk else {}),
         "config": {"workload": ("BPRMF d=128, synthetic 10M users x 1M items (the shape BASELINE.json's metric / north_star quote the target on; "
                                 "fits one MI355X)" if (U, I, F) == (10_000_000, 1_000_000, 128)
                                 else "BPRMF d=128, synthetic 1M users x 100K items (BASELINE configs[1])" if (U, I, F) == (1_000_000, 100_000, 128)
                                 else f"BPRMF d={F}, synthetic {U} users x {I} items"),
                    "users": U, "items": I, "factors": F, "interactions": main_leg["interactions"], "batch": B,
                    "batch_per_gpu": B, "optimizer": args.opt, "replay": args.replay if (not sharded and args.opt == "adam_tf_dense") else None,
-                   "topk_block": main_leg["topk_block"], "k": k,
+                   "topk_block": main_leg.get("topk_block"), "k": k if FULL else None,
                    "parallelism": main_leg["parallelism"] + ("; top-k: see topk.sharding" if sharded else ""),
                    "scaling_note": ("one model of this shape partitioned over the ranks (user rows sharded, item table replicated), B triplets "
                                     "per rank and step: the batch grows with N, the tables do not") if sharded else None,
                    "world_size_observed": world, "backend": backend, "collectives_through": args.comm if sharded else None},
         "loss_per_pair_last": main_leg["loss_per_pair_last"],
-        "roofline": main_leg["roofline"],
-        "topk": main_leg["topk"],
     }
+    if FULL:
+        line["roofline"], line["topk"] = main_leg["roofline"], main_leg["topk"]
     for key in ("collectives", "metrics"):
         if key in main_leg:
             line[key] = main_leg[key]

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/${1:-pmc_train_issue}
 mkdir -p $OUT
 cd $R
-CMD="python bench.py --legs bpr --no-cpu-baseline --trained-epochs 0 --steps 6 --warmup 1 --repeats 1 --legs-file /tmp/legs_pmc.json"
+CMD="python bench.py --full --legs bpr --no-cpu-baseline --trained-epochs 0 --steps 6 --warmup 1 --repeats 1 --legs-file $OUT/legs.json"
 i=0
 for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM" "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU" \
            "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_INSTS_LDS" "GRBM_GUI_ACTIVE SQ_WAVES SQ_INST_CYCLES_SALU SQ_ACTIVE_INST_SCA"; do

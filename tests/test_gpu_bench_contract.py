@@ -1,9 +1,11 @@
-"""bench.py prints ONE JSON line with the fields the driver reads (run here on a reduced workload so that it takes seconds)."""
+"""bench.py prints ONE JSON line with the fields the driver reads (run here on a reduced workload so that it takes seconds): a plain run
+(the headline training step only, --dump-outputs) and --full runs (every leg, roofline and baseline)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -22,14 +24,14 @@ def _strict(text):
 
 
 def run_bench(*extra, env=None, both=False):
-    """Runs bench.py; returns the FULL per-leg report (the side file) after checking the stdout line (one line, compact, strict JSON,
-    consistent with the report).  both=True: (line, full)."""
+    """Runs bench.py --full; returns the FULL per-leg report (the side file) after checking the stdout line (one line, compact, strict
+    JSON, consistent with the report).  both=True: (line, full)."""
     import tempfile
     legs = tempfile.NamedTemporaryFile(prefix="bench_legs_", suffix=".json", delete=False)
     legs.close()
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--users", "60000", "--items", "8000", "--factors", "64", "--batch", "65536",
            "--topk-block", "16384", "--steps", "3", "--warmup", "1", "--cpu-topk-users", "32", "--cpu-seconds", "0.5",
-           "--legs-file", legs.name, *extra]
+           "--legs-file", legs.name, "--full", *extra]
     e = dict(os.environ)
     e.update(env or {})
     try:
@@ -104,6 +106,50 @@ def test_default_line_has_every_field():
     assert d["metrics"]["value"] > 0
     fr = d["topk"]["fragile_users"]
     assert fr["users"] == d["config"]["topk_block"] and 0 <= fr["fragile"] <= fr["users"]
+
+
+def run_plain(*extra):
+    """bench.py without --full on the reduced workload; returns the stdout line (one line, the last one, strict JSON)."""
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--users", "60000", "--items", "8000", "--factors", "64", "--batch", "65536",
+           "--steps", "3", "--warmup", "1", *extra]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=REPO)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and out.stdout.rstrip().splitlines()[-1] == lines[0], out.stdout[-2000:]
+    return _strict(lines[0])
+
+
+def test_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain run: the contract's fields, ONE timed pass of exactly --steps steps (no repeats, no rooflines, no top-k, no other legs,
+    no CPU baseline, no side file), and --dump-outputs writes the tables after the last timed step -- the same files and, up to the
+    summation order of the gradient sums, the same values run after run (the inputs are identical)."""
+    legs_default = os.path.join(REPO, "bench_legs.json")
+    before = os.path.getmtime(legs_default) if os.path.exists(legs_default) else None
+    dumps = [str(tmp_path / "a"), str(tmp_path / "b")]
+    lines = [run_plain("--dump-outputs", d) for d in dumps]
+    for d in lines:
+        assert d["metric"] == "BPR-MF positive-pairs/sec + full-catalog top-k users/sec" and d["unit"] == "pairs/s" and d["dtype"] == "f32"
+        assert d["higher_is_better"] is True and d["full"] is False and d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+        assert d["value"] > 0 and d["ms_per_step"] > 0
+        assert abs(d["value"] - d["config"]["batch"] / (d["ms_per_step"] * 1e-3)) <= 1e-5 * d["value"]
+        for key in ("roofline", "topk", "topk_users_per_s", "cpu_baseline", "legs", "collectives", "legs_file"):
+            assert key not in d, key
+    after = os.path.getmtime(legs_default) if os.path.exists(legs_default) else None
+    assert after == before                                        # no side file from a plain run
+    files = sorted(os.listdir(dumps[0]))
+    assert files == sorted(os.listdir(dumps[1])) and {"Gu.npy", "Gi.npy", "Bi.npy", "loss_per_pair.npy"} <= set(files)
+    total = 0
+    for f in files:
+        a, b = np.load(os.path.join(dumps[0], f)), np.load(os.path.join(dumps[1], f))
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and np.isfinite(a).all(), f
+        assert np.allclose(a, b, rtol=1e-4, atol=1e-5), f
+        total += os.path.getsize(os.path.join(dumps[0], f))
+    assert total <= 64 << 20
+    # tables below bench.OUTPUT_TABLE_BYTES are written whole (the sampled form: tests/test_bench_line.py)
+    assert "Gu_rows.npy" not in files and np.load(os.path.join(dumps[0], "Gu.npy")).shape == (60000, 64)
+    assert np.load(os.path.join(dumps[0], "Gi.npy")).shape == (8000, 64) and np.load(os.path.join(dumps[0], "Bi.npy")).shape == (8000,)
+    loss = float(np.load(os.path.join(dumps[0], "loss_per_pair.npy"))[0])
+    assert loss > 0 and abs(loss - lines[0]["loss_per_pair_last"]) <= 1e-5 * loss
 
 
 def test_pipelined_and_plain_training_step_lines():
