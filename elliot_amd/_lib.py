@@ -20,6 +20,8 @@ EL_TOPK_SCREEN = 3
 EL_BPR_AUTO = 0
 EL_BPR_ATOMIC = 1
 EL_BPR_SORTED = 2
+EL_KNN_COSINE = 0
+EL_KNN_DOT = 1
 
 _f32p = C.c_void_p
 _i32p = C.c_void_p
@@ -255,6 +257,11 @@ PROTOTYPES = {
                                       C.c_int64]),
     "el_dense_topk": (C.c_int, [C.c_void_p, C.c_void_p, _f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                 _i64p, _i32p, _i64p, _i32p, C.c_int32, _i32p, _f32p]),
+    "el_knn_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "el_knn_build": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _i32p, _i64p, _i32p, _i32p, C.c_int64, C.c_int64, C.c_int32,
+                               C.c_int, C.c_int32, C.c_int64, C.c_int32, _i64p, _i32p, _f32p, C.c_void_p, C.c_size_t]),
+    "el_knn_score_topk": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _f32p, _i64p, _i32p, _f32p, C.c_int64, C.c_int64,
+                                    C.c_int64, _i64p, _i32p, _i64p, _i32p, C.c_int32, _i32p, _f32p]),
 }
 
 _lib = None

@@ -239,6 +239,85 @@ def topk_merge(ctx, parts_idx, parts_val):
 
 
 # ------------------------------------------------------------------------------------------
+# neighbourhood models (ItemKNN / UserKNN, implementation: standard)
+# ------------------------------------------------------------------------------------------
+KNN_SIMILARITIES = {"cosine": _lib.EL_KNN_COSINE, "dot": _lib.EL_KNN_DOT}
+
+
+def device_values(values, device):
+    """The values of a CSR as a float32 device tensor beside its DeviceCSR (never a zero-length buffer)."""
+    v = np.ascontiguousarray(values, dtype=np.float32)
+    return torch.from_numpy(v if v.shape[0] else np.zeros(1, np.float32)).to(device)
+
+
+def knn_integer_ratings(values):
+    """(scale, int32 values): ratings times 1 (integers) or 2 (half steps), exactly.  Anything else is refused."""
+    v = np.asarray(values, dtype=np.float64)
+    for scale in (1, 2):
+        s = v * scale
+        if np.all(np.isfinite(s)) and np.all(s == np.round(s)) and (s.size == 0 or np.abs(s).max() < 2 ** 31):
+            return scale, s.astype(np.int32)
+    raise ValueError("ItemKNN / UserKNN need integer or half-step ratings (the similarity counts are exact integers); "
+                     "this train matrix holds other values")
+
+
+def knn_build(ctx, R, side, n_neighbors, sim):
+    """Similarity.initialize (item_knn_similarity.py / user_knn_similarity.py:46-80): W of ItemKNN (side="item": the columns
+    of R) or UserKNN (side="user": its rows), top-`n_neighbors` non-zeros per column.  R: scipy sparse [U, I] with values.
+    Returns (DeviceCSR W, float32 values tensor); W is [n, n], columns ascending in every row."""
+    import scipy.sparse as sp
+    if sim not in KNN_SIMILARITIES:
+        raise ValueError(f"similarity {sim!r} is not supported; supported: {sorted(KNN_SIMILARITIES)}")
+    if side not in ("item", "user"):
+        raise ValueError("side must be 'item' or 'user'")
+    R = sp.csr_matrix(R)
+    R.sum_duplicates()
+    R.sort_indices()
+    Rt = R.T.tocsr()
+    Rt.sort_indices()
+    P, Q = (Rt, R) if side == "item" else (R, Rt)
+    n, n_other = P.shape
+    scale, pv = knn_integer_ratings(P.data)
+    _, qv = knn_integer_ratings(Q.data)
+    dev = ctx.device
+    Pc, Qc = DeviceCSR(P.indptr, P.indices, n_other, dev), DeviceCSR(Q.indptr, Q.indices, n, dev)
+    pvt = torch.from_numpy(pv if pv.size else np.zeros(1, np.int32)).to(dev)
+    qvt = torch.from_numpy(qv if qv.size else np.zeros(1, np.int32)).to(dev)
+    max_deg = int(np.diff(P.indptr).max()) if n else 0
+    max_abs = int(np.abs(pv).max()) if pv.size else 0
+    N = min(int(n_neighbors), n)
+    need = int(ctx.lib.el_knn_ws_bytes(int(n), int(n_neighbors)))
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    w_indptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    w_indices = torch.empty(max(n * N, 1), dtype=torch.int32, device=dev)
+    w_vals = torch.empty(max(n * N, 1), dtype=torch.float32, device=dev)
+    check(ctx.lib.el_knn_build(ctx.handle, ctx.stream(), _ptr(Pc.indptr), _ptr(Pc.indices), _ptr(pvt), _ptr(Qc.indptr),
+                               _ptr(Qc.indices), _ptr(qvt), int(n), int(n_other), int(n_neighbors), KNN_SIMILARITIES[sim],
+                               int(scale), max_deg, max_abs, _ptr(w_indptr), _ptr(w_indices), _ptr(w_vals),
+                               C.c_void_p(ws.data_ptr()), need), "el_knn_build")
+    nnz = int(w_indptr[-1].item())
+    W = DeviceCSR.from_tensors(w_indptr, w_indices[:nnz], n)
+    return W, (w_vals[:nnz] if nnz else w_vals[:1])
+
+
+def knn_score_topk(ctx, A, A_vals, B, B_vals, u_start, u_stop, k, excl=None, cand=None, out_idx=None, out_val=None):
+    """R.dot(W) (ItemKNN: A = R, B = W) or W.dot(R) (UserKNN: A = W, B = R) for users [u_start, u_stop), masked top-k
+    (get_user_recs, item_knn_similarity.py:159-175) without the [U, I] block: (idx int32 [n, k], val float32 [n, k])."""
+    n = int(u_stop) - int(u_start)
+    if out_idx is None:
+        out_idx = torch.empty((n, k), dtype=torch.int32, device=ctx.device)
+    if out_val is None:
+        out_val = torch.empty((n, k), dtype=torch.float32, device=ctx.device)
+    ep, ei = _csr_ptrs(excl)
+    cp, ci = _csr_ptrs(cand)
+    check(ctx.lib.el_knn_score_topk(ctx.handle, ctx.stream(), _ptr(A.indptr, torch.int64), _ptr(A.indices, torch.int32),
+                                    _ptr(A_vals, torch.float32), _ptr(B.indptr, torch.int64), _ptr(B.indices, torch.int32),
+                                    _ptr(B_vals, torch.float32), int(u_start), int(u_stop), int(B.n_cols), ep, ei, cp, ci,
+                                    int(k), _ptr(out_idx, torch.int32), _ptr(out_val, torch.float32)), "el_knn_score_topk")
+    return out_idx, out_val
+
+
+# ------------------------------------------------------------------------------------------
 # accuracy metrics on the device (SURVEY 8f, N1)
 # ------------------------------------------------------------------------------------------
 METRIC_NAMES = ("nDCG", "Precision", "Recall", "HR", "MAP", "MRR", "F1")

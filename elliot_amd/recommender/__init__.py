@@ -16,6 +16,9 @@ from .autoencoders.vae.multi_vae import MultiVAE
 from .autoencoders.dae.multi_dae import MultiDAE
 from .neural.NeuMF.neural_matrix_factorization import NeuMF
 from .neural.GeneralizedMF.generalized_matrix_factorization import GMF
+from .knn.item_knn.item_knn import ItemKNN
+from .knn.user_knn.user_knn import UserKNN
 
 __all__ = ["BaseRecommenderModel", "init_charger", "RecMixin", "BPRMF_batch", "BPRMF", "MultiVAE", "MultiDAE", "NeuMF", "GMF",
-           "MF", "PMF", "FunkSVD", "LogisticMatrixFactorization", "LMF", "CML", "MF2020", "LightGCN", "NGCF", "ProxyRecommender"]
+           "MF", "PMF", "FunkSVD", "LogisticMatrixFactorization", "LMF", "CML", "MF2020", "LightGCN", "NGCF", "ProxyRecommender",
+           "ItemKNN", "UserKNN"]

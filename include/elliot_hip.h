@@ -448,6 +448,50 @@ int el_dense_topk(el_ctx* ctx, void* stream, const float* preds, int64_t ld,
                   const int64_t* cand_indptr, const int32_t* cand_indices,
                   int32_t k, int32_t* out_idx, float* out_val);
 
+/* ---- neighbourhood models: ItemKNN / UserKNN, implementation: standard --------------------------------------------- */
+
+#define EL_KNN_COSINE 0
+#define EL_KNN_DOT 1
+
+/* Replaces Similarity.initialize (item_knn_similarity.py:46-80, user_knn_similarity.py:46-78): the similarity of the
+ * columns (ItemKNN: sklearn cosine_similarity(R.T) or R.T @ R, :96-101) or rows (UserKNN: cosine_similarity(R) or R @ R.T)
+ * of R, cut to the N largest non-zeros of every column (:62-73, self-similarity included) and laid out as W.tocsr() (:76-77).
+ *   P (targets -> the other side t) and Q (t -> x) are the two orientations of R with INTEGER values: ratings times scale
+ *   (1: integer ratings, 2: half steps); ItemKNN passes P = R^T, Q = R; UserKNN P = R, Q = R^T.  Q rows ascending.
+ *   cnt[c,x] = sum_t P[c,t] Q[t,x] and n_c = sum_t P[c,t]^2 are exact integers (order-independent LDS atomics; int32 when
+ *   max_deg * max_abs^2 fits, int64 otherwise, an error beyond that); max_deg = longest row of P, max_abs = max |value|.
+ *   EL_KNN_DOT    value = (float)(cnt / scale^2)
+ *   EL_KNN_COSINE value = (float)(cnt_d / sqrt(n_c_d * n_x_d)), every operand a double divided by scale^2, fp64
+ *                 correctly rounded and rounded once to float (sklearn normalises in float32 first: within ~1e-5 relative)
+ *   column c of W keeps min(N, non-zeros) entries by (value desc, index asc) (the reference's argsort cut breaks ties
+ *   arbitrarily); W[x, c] = value.
+ * Output: W as CSR over x, n rows, columns ascending: w_indptr int64[n+1], w_indices int32 / w_vals float with room for
+ * n * min(N, n) entries (the nnz is w_indptr[n]).  N <= 2048.  Nothing n x n is materialised:
+ * ws = el_knn_ws_bytes(n, n_neighbors) bytes.                                                                          */
+size_t el_knn_ws_bytes(int64_t n, int32_t n_neighbors);
+int el_knn_build(el_ctx* ctx, void* stream,
+                 const int64_t* p_indptr, const int32_t* p_indices, const int32_t* p_vals,
+                 const int64_t* q_indptr, const int32_t* q_indices, const int32_t* q_vals,
+                 int64_t n, int64_t n_other, int32_t n_neighbors, int sim, int32_t scale,
+                 int64_t max_deg, int32_t max_abs,
+                 int64_t* w_indptr, int32_t* w_indices, float* w_vals, void* ws, size_t ws_bytes);
+
+/* Replaces self._preds = R.dot(W) (ItemKNN, item_knn_similarity.py:78) / W.dot(R) (UserKNN, user_knn_similarity.py:77)
+ * followed by get_user_recs (:159-175) for users [u_start, u_stop):
+ *   score[u, i] = sum over the entries a of A row u IN STORED ORDER of A[u,a] * B[a,i], from +0 for every item, as
+ *   separate round-to-nearest multiply and add (scipy csr_matmat): ItemKNN A = R, B = W; UserKNN A = W, B = R.
+ *   B rows ascending; A rows indexed by absolute user id.
+ *   mask and candidate CSRs as el_dense_topk; top-k by (score desc, index asc) over every unmasked item, zero scores
+ *   included; rows with fewer than k candidates are padded with (-1, -inf).  k <= 4032.
+ *   out_idx int32[(u_stop-u_start), k], out_val float[(u_stop-u_start), k].  The [U, I] block is never materialised.  */
+int el_knn_score_topk(el_ctx* ctx, void* stream,
+                      const int64_t* a_indptr, const int32_t* a_indices, const float* a_vals,
+                      const int64_t* b_indptr, const int32_t* b_indices, const float* b_vals,
+                      int64_t u_start, int64_t u_stop, int64_t I,
+                      const int64_t* excl_indptr, const int32_t* excl_indices,
+                      const int64_t* cand_indptr, const int32_t* cand_indices,
+                      int32_t k, int32_t* out_idx, float* out_val);
+
 /* ---- dense layers: fp32 MFMA GEMM with fused bias + activation (K9, K12) ----------------- */
 
 /* Replaces: keras.layers.Dense forward/backward products of the neural latent-factor models
