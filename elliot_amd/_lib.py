@@ -22,6 +22,8 @@ EL_BPR_ATOMIC = 1
 EL_BPR_SORTED = 2
 EL_KNN_COSINE = 0
 EL_KNN_DOT = 1
+EL_ALS_SKIP_EMPTY = 1
+EL_ALS_MAX_F = 128
 
 _f32p = C.c_void_p
 _i32p = C.c_void_p
@@ -262,6 +264,12 @@ PROTOTYPES = {
                                C.c_int, C.c_int32, C.c_int64, C.c_int32, _i64p, _i32p, _f32p, C.c_void_p, C.c_size_t]),
     "el_knn_score_topk": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _f32p, _i64p, _i32p, _f32p, C.c_int64, C.c_int64,
                                     C.c_int64, _i64p, _i32p, _i64p, _i32p, C.c_int32, _i32p, _f32p]),
+    "el_als_gram_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "el_als_gram": (C.c_int, [C.c_void_p, C.c_void_p, _f64p, C.c_int64, C.c_int32, _f64p, C.c_void_p, C.c_size_t]),
+    "el_als_solve_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "el_als_solve": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, C.c_int64, _f64p, C.c_int64, C.c_int32, _f64p, C.c_double,
+                               C.c_double, C.c_double, C.c_int, _i32p, _i64p, C.c_int64, C.c_int64, C.c_int64, _f64p, _i32p,
+                               C.c_void_p, C.c_size_t]),
 }
 
 _lib = None

@@ -318,6 +318,137 @@ def knn_score_topk(ctx, A, A_vals, B, B_vals, u_start, u_stop, k, excl=None, can
 
 
 # ------------------------------------------------------------------------------------------
+# alternating least squares (iALS / WRMF)
+# ------------------------------------------------------------------------------------------
+ALS_PIECE_LEN = 8192          # rows longer than this are summed in pieces (el_als_solve's long-row plan)
+
+
+def als_plan(indptr, piece_len=ALS_PIECE_LEN):
+    """Host: the long-row plan of a CSR for el_als_solve -- (long_rows int32, long_first int64, n_pieces)."""
+    lens = np.diff(np.asarray(indptr, dtype=np.int64))
+    rows = np.flatnonzero(lens > piece_len).astype(np.int32)
+    first = np.zeros(rows.shape[0] + 1, np.int64)
+    np.cumsum((lens[rows] + piece_len - 1) // piece_len, out=first[1:])
+    return rows, first, int(first[-1])
+
+
+class AlsCSR:
+    """One orientation of the train pattern for el_als_solve: the DeviceCSR plus its long-row plan."""
+
+    def __init__(self, indptr, indices, n_cols, device, piece_len=ALS_PIECE_LEN):
+        self.csr = DeviceCSR(indptr, indices, n_cols, device)
+        rows, first, self.n_pieces = als_plan(indptr, piece_len)
+        self.piece_len = int(piece_len)
+        self.n_long = int(rows.shape[0])
+        self.long_rows = torch.from_numpy(rows if rows.size else np.zeros(1, np.int32)).to(device)
+        self.long_first = torch.from_numpy(first).to(device)
+        self.empty = np.diff(np.asarray(indptr, dtype=np.int64)) == 0
+
+
+def _als_ws(ctx, holder, attr, need):
+    ws = getattr(holder, attr, None)
+    if need and (ws is None or ws.numel() < need):
+        ws = torch.empty(need, dtype=torch.uint8, device=ctx.device)
+        setattr(holder, attr, ws)
+    return (C.c_void_p(ws.data_ptr()) if need else None), need
+
+
+def als_gram(ctx, Y, out=None, holder=None):
+    """G = Y^T Y (fp64 [F, F], el_als_gram): fixed slots, symmetric bit for bit."""
+    n, F = Y.shape
+    if out is None:
+        out = torch.empty((F, F), dtype=torch.float64, device=ctx.device)
+    ws, need = _als_ws(ctx, holder if holder is not None else ctx, "_als_gram_ws", int(ctx.lib.el_als_gram_ws_bytes(int(n), int(F))))
+    check(ctx.lib.el_als_gram(ctx.handle, ctx.stream(), _ptr(Y, torch.float64, "Y"), int(n), int(F), _ptr(out, torch.float64, "G"),
+                              ws, need), "el_als_gram")
+    return out
+
+
+def als_solve(ctx, pattern, Y, G, w_A, w_b, lam, X, skip_empty=False, holder=None):
+    """One ALS half-step (el_als_solve): X[r] = (G + w_A sum y y^T + lam I)^-1 (w_b sum y) for every row of `pattern` (AlsCSR over
+    the rows of Y).  Raises numpy.linalg.LinAlgError naming the first row met with a non-positive pivot."""
+    n_rows, F = X.shape
+    if Y.shape[1] != F or tuple(G.shape) != (F, F):
+        raise ValueError("X / Y / G factor mismatch")
+    if pattern.csr.n_rows != n_rows or pattern.csr.n_cols != Y.shape[0]:
+        raise ValueError("pattern shape does not match X / Y")
+    holder = holder if holder is not None else ctx
+    ws, need = _als_ws(ctx, holder, "_als_solve_ws", int(ctx.lib.el_als_solve_ws_bytes(int(pattern.n_pieces), int(F))))
+    status = getattr(holder, "_als_status", None)
+    if status is None:
+        status = holder._als_status = torch.empty(2, dtype=torch.int32, device=ctx.device)
+    check(ctx.lib.el_als_solve(ctx.handle, ctx.stream(), _ptr(pattern.csr.indptr, torch.int64), _ptr(pattern.csr.indices, torch.int32),
+                               int(n_rows), _ptr(Y, torch.float64, "Y"), int(Y.shape[0]), int(F), _ptr(G, torch.float64, "G"),
+                               float(w_A), float(w_b), float(lam), _lib.EL_ALS_SKIP_EMPTY if skip_empty else 0,
+                               _ptr(pattern.long_rows, torch.int32), _ptr(pattern.long_first, torch.int64), pattern.n_long,
+                               pattern.n_pieces, pattern.piece_len, _ptr(X, torch.float64, "X"), _ptr(status, torch.int32), ws, need),
+          "el_als_solve")
+    bad, plan = (int(v) for v in status.cpu().tolist())
+    if plan != 0x7fffffff:
+        raise _lib.ElliotHipError(f"el_als_solve: the long-row plan does not describe row {plan}")
+    if bad != 0x7fffffff:
+        raise np.linalg.LinAlgError(f"ALS: the normal equations of row {bad} are not positive definite (non-positive pivot)")
+    return X
+
+
+class AlsDeviceState:
+    """X [U, F], Y [I, F] (fp64), both orientations of the train pattern and the two weights of iALS / WRMF in HBM.
+
+    step() is one reference train_step: the user half with G = Y^T Y, then the item half --
+      gram="fresh" (iALS, iALS_model.py:61): G = X^T X of the NEW X, empty items keep their row (warm items only, :37-38)
+      gram="stale" (WRMF, wrmf_model.py:41-42): G = X^T X taken at the top of the step from the OLD X, every item solved."""
+
+    def __init__(self, ctx, X, Y, indptr, indices, w_A, w_b, reg, gram="fresh", piece_len=ALS_PIECE_LEN):
+        if gram not in ("fresh", "stale"):
+            raise ValueError("gram must be 'fresh' (iALS) or 'stale' (WRMF)")
+        self.ctx = ctx
+        dev = ctx.device
+        own = lambda x: torch.from_numpy(np.array(x, dtype=np.float64, order="C")).to(dev)
+        self.X, self.Y = own(X), own(Y)
+        self.U, self.F = int(self.X.shape[0]), int(self.X.shape[1])
+        self.I = int(self.Y.shape[0])
+        if self.F > _lib.EL_ALS_MAX_F:
+            raise ValueError(f"factors={self.F} unsupported (at most {_lib.EL_ALS_MAX_F})")
+        import scipy.sparse as sp
+        R = sp.csr_matrix((np.ones(len(indices), np.float32), np.asarray(indices), np.asarray(indptr)), shape=(self.U, self.I))
+        R.sort_indices()
+        Rt = R.T.tocsr()
+        Rt.sort_indices()
+        self.users = AlsCSR(R.indptr, R.indices, self.I, dev, piece_len)
+        self.items = AlsCSR(Rt.indptr, Rt.indices, self.U, dev, piece_len)
+        self.w_A, self.w_b, self.reg, self.gram = float(w_A), float(w_b), float(reg), gram
+        self.Gy = torch.empty((self.F, self.F), dtype=torch.float64, device=dev)
+        self.Gx = torch.empty((self.F, self.F), dtype=torch.float64, device=dev)
+        self._zero_bias = None
+
+    def user_half(self):
+        als_gram(self.ctx, self.Y, out=self.Gy, holder=self)
+        als_solve(self.ctx, self.users, self.Y, self.Gy, self.w_A, self.w_b, self.reg, self.X, holder=self)
+
+    def item_half(self):
+        als_gram(self.ctx, self.X, out=self.Gx, holder=self)
+        als_solve(self.ctx, self.items, self.X, self.Gx, self.w_A, self.w_b, self.reg, self.Y, skip_empty=True, holder=self)
+
+    def step(self):
+        if self.gram == "fresh":
+            self.user_half()
+            self.item_half()
+            return
+        als_gram(self.ctx, self.Y, out=self.Gy, holder=self)
+        als_gram(self.ctx, self.X, out=self.Gx, holder=self)
+        als_solve(self.ctx, self.users, self.Y, self.Gy, self.w_A, self.w_b, self.reg, self.X, holder=self)
+        als_solve(self.ctx, self.items, self.X, self.Gx, self.w_A, self.w_b, self.reg, self.Y, holder=self)
+
+    def recommend(self, mask, k, start, stop):
+        """X Y^T (fp64) for users [start, stop) and the masked top-k (el_score_topk_f64 with b = 0): (idx, val) on the device."""
+        kind, csr = mask if mask is not None else (None, None)
+        if self._zero_bias is None:
+            self._zero_bias = torch.zeros(self.I, dtype=torch.float64, device=self.ctx.device)
+        return score_topk_f64(self.ctx, self.X, self.Y, self._zero_bias, start, stop, k, excl=csr if kind == "excl" else None,
+                              cand=csr if kind == "cand" else None)
+
+
+# ------------------------------------------------------------------------------------------
 # accuracy metrics on the device (SURVEY 8f, N1)
 # ------------------------------------------------------------------------------------------
 METRIC_NAMES = ("nDCG", "Precision", "Recall", "HR", "MAP", "MRR", "F1")

@@ -18,7 +18,9 @@ from .neural.NeuMF.neural_matrix_factorization import NeuMF
 from .neural.GeneralizedMF.generalized_matrix_factorization import GMF
 from .knn.item_knn.item_knn import ItemKNN
 from .knn.user_knn.user_knn import UserKNN
+from .latent_factor_models.iALS.iALS import iALS
+from .latent_factor_models.WRMF.wrmf import WRMF
 
 __all__ = ["BaseRecommenderModel", "init_charger", "RecMixin", "BPRMF_batch", "BPRMF", "MultiVAE", "MultiDAE", "NeuMF", "GMF",
            "MF", "PMF", "FunkSVD", "LogisticMatrixFactorization", "LMF", "CML", "MF2020", "LightGCN", "NGCF", "ProxyRecommender",
-           "ItemKNN", "UserKNN"]
+           "ItemKNN", "UserKNN", "iALS", "WRMF"]

@@ -492,6 +492,36 @@ int el_knn_score_topk(el_ctx* ctx, void* stream,
                       const int64_t* cand_indptr, const int32_t* cand_indices,
                       int32_t k, int32_t* out_idx, float* out_val);
 
+/* ---- alternating least squares: iALS / WRMF ------------------------------------------------------------------------ */
+
+#define EL_ALS_SKIP_EMPTY 1     /* el_als_solve: rows without entries keep their X row (iALS item half, warm items only) */
+#define EL_ALS_MAX_F 128
+
+/* Replaces yTy = Y.T.dot(Y) / xTx = X.T.dot(X) (iALS_model.py:41,61, wrmf_model.py:41-42): G[F, F] = Y^T Y of an fp64
+ * row-major Y[n, F], F <= 128.  Rows are summed in fixed slots of consecutive rows (the slot count depends on n only), the
+ * slots are added in slot order, the upper triangle is the mirror of the lower: the same bits on every run, symmetric
+ * bit for bit.  ws = el_als_gram_ws_bytes(n, F) bytes (0: none needed).                                                   */
+size_t el_als_gram_ws_bytes(int64_t n, int32_t F);
+int el_als_gram(el_ctx* ctx, void* stream, const double* Y, int64_t n, int32_t F, double* G, void* ws, size_t ws_bytes);
+
+/* Replaces one half of iALSModel.train_step (iALS_model.py:43-52 users, :54-72 items) / WRMFModel.train_step
+ * (wrmf_model.py:43-58): for every row r of the CSR (indptr int64[n_rows+1], indices int32 into the rows of Y[n_other, F]):
+ *   A_r = G + w_A * S_r + lambda I,  S_r = sum_{j in r} y_j y_j^T, terms added in ascending CSR position
+ *   b_r = w_b * sum_{j in r} y_j
+ *   X[r] = A_r^-1 b_r by Cholesky (fp64, no pivoting); an empty row gets X[r] = 0 by the same arithmetic, or keeps its
+ *   X row under EL_ALS_SKIP_EMPTY.
+ * Rows with more than piece_len entries must be listed: long_rows int32[n_long] ascending, long_first int64[n_long + 1]
+ * with long_first[0] = 0 and long_first[j + 1] - long_first[j] = ceil(len / piece_len); n_pieces = long_first[n_long].
+ * Each piece of piece_len positions is summed into its own slot of ws = el_als_solve_ws_bytes(n_pieces, F) bytes and
+ * the slots are added in piece order: the same bits on every run.
+ * status int32[2] on the device, written by the call: [0] the smallest row met with a non-positive pivot, [1] the
+ * smallest long row the plan does not describe; 0x7fffffff = none.  Those rows' X are left untouched.  F <= 128.        */
+size_t el_als_solve_ws_bytes(int64_t n_pieces, int32_t F);
+int el_als_solve(el_ctx* ctx, void* stream, const int64_t* indptr, const int32_t* indices, int64_t n_rows,
+                 const double* Y, int64_t n_other, int32_t F, const double* G, double w_A, double w_b, double lambda,
+                 int flags, const int32_t* long_rows, const int64_t* long_first, int64_t n_long, int64_t n_pieces,
+                 int64_t piece_len, double* X, int32_t* status, void* ws, size_t ws_bytes);
+
 /* ---- dense layers: fp32 MFMA GEMM with fused bias + activation (K9, K12) ----------------- */
 
 /* Replaces: keras.layers.Dense forward/backward products of the neural latent-factor models
