@@ -169,19 +169,6 @@ extern "C" int el_bpr_sample_meta(el_ctx* ctx, void* stream, const int64_t* pos_
 // ---------------------------------------------------------------------------------------
 // K2-K4: BPRMF_batch train step
 // ---------------------------------------------------------------------------------------
-template <int VW>
-__device__ __forceinline__ void ld_vec(const float* p, float* dst) {
-    if (VW == 4) {
-        float4 t = *reinterpret_cast<const float4*>(p);
-        dst[0] = t.x;
-        dst[1] = t.y;
-        dst[2] = t.z;
-        dst[3] = t.w;
-    } else {
-        dst[0] = p[0];
-    }
-}
-
 __device__ __forceinline__ float el_softplus(float x) {
     // tf.nn.softplus: x for large x, exp(x) for very negative x, log1p(exp(x)) otherwise
     if (x > 15.0f) return x;
@@ -219,9 +206,9 @@ __device__ __forceinline__ void bprmf_fwd_bwd_body(const el_bprmf_state& st, con
 #pragma unroll
         for (int x = 0; x < VW; ++x) gu[q][x] = gi[q][x] = gj[q][x] = 0.f;
         if (ok) {
-            ld_vec<VW>(pu + e, gu[q]);
-            ld_vec<VW>(pi + e, gi[q]);
-            ld_vec<VW>(pj + e, gj[q]);
+            ldv<VW>(pu + e, gu[q]);
+            ldv<VW>(pi + e, gi[q]);
+            ldv<VW>(pj + e, gj[q]);
         }
 #pragma unroll
         for (int x = 0; x < VW; ++x) {
@@ -545,11 +532,11 @@ __global__ __launch_bounds__(256) void k_rows_apply(el_bprmf_state st, const int
         const int e = (sub + q * lpt) * VW;
         if (e < F) {
             float a[VW], gg[VW], mm[VW], vv[VW];
-            ld_vec<VW>(th + e, a);
-            ld_vec<VW>(g + e, gg);
+            ldv<VW>(th + e, a);
+            ldv<VW>(g + e, gg);
             if (ADAM) {
-                ld_vec<VW>(m + e, mm);
-                ld_vec<VW>(v + e, vv);
+                ldv<VW>(m + e, mm);
+                ldv<VW>(v + e, vv);
             }
 #pragma unroll
             for (int x = 0; x < VW; ++x) {

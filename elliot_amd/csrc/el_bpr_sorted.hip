@@ -12,40 +12,15 @@
 //   5. optimiser           k_adam_dense (TF semantics) / k_rows_apply (el_bpr.hip)
 // Segments longer than a chunk (popular items under Zipf: tens of thousands of occurrences) are
 // split over several lane groups; segments that live inside one chunk are written with plain stores, a
-// segment cut by chunk boundaries leaves one partial row per chunk and k_bpr_item_combine adds them IN
-// CHUNK ORDER (round 6: no floating-point atomics anywhere in the sorted step -- two runs on the same
-// batches give the same bits, and the fused / deferred forms equal the two-pass form bit for bit at any size).
+// segment cut by chunk boundaries leaves one partial row per chunk and k_seg_combine / k_seg_combine_long
+// (el_segcombine.h) add them IN CHUNK ORDER (round 6: no floating-point atomics anywhere in the sorted step -- two
+// runs on the same batches give the same bits, and the fused / deferred forms equal the two-pass form bit for bit
+// at any size).
 #include "el_common.h"
+#include "el_segcombine.h"
 #include <cstdlib>
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
-
-template <int VW>
-__device__ __forceinline__ void ldv(const float* p, float* dst) {
-    if (VW == 4) {
-        float4 t = *reinterpret_cast<const float4*>(p);
-        dst[0] = t.x;
-        dst[1] = t.y;
-        dst[2] = t.z;
-        dst[3] = t.w;
-    } else if (VW == 2) {
-        float2 t = *reinterpret_cast<const float2*>(p);
-        dst[0] = t.x;
-        dst[VW - 1] = t.y;
-    } else {
-        dst[0] = p[0];
-    }
-}
-template <int VW>
-__device__ __forceinline__ void stv(float* p, const float* src) {
-    if (VW == 4) {
-        *reinterpret_cast<float4*>(p) = make_float4(src[0], src[1], src[2], src[3]);
-    } else if (VW == 2) {
-        *reinterpret_cast<float2*>(p) = make_float2(src[0], src[VW - 1]);
-    } else {
-        p[0] = src[0];
-    }
-}
 
 __device__ __forceinline__ float el_softplus_s(float x) {
     if (x > 15.0f) return x;
@@ -733,15 +708,14 @@ __global__ __launch_bounds__(256) void k_bpr_flush_items(el_bprmf_state st, int3
 // keeps as many loads in flight as the two-pass walk did.
 // Both forms: a segment cut by a chunk boundary (the popular items of a Zipf catalogue) leaves its partial rows in the step's partial
 // buffer -- slot 2 g for the segment that reaches INTO lane group g's chunk from the left, slot 2 g + 1 for the one that starts
-// inside it and runs on -- and the group that holds the segment's first position puts (item, g) on the step's split list;
-// k_bpr_item_combine -- the next launch -- adds a listed item's partials in chunk order and takes the step (fused form) or stores the
-// gradient row (two-pass form).  (No in-kernel "last partial" hand-over: an agent-scope fence on this part writes back the
-// XCD's L2 -- measured: 0.25 -> 0.92 ms for the item segments at configs[1] with one fence pair per chunk.)
+// inside it and runs on; k_seg_combine -- the next launch -- finds the cut segments from the keys, adds each one's partials in chunk
+// order and hands the row to ItemFinish: the step (fused form) or the stored gradient row (two-pass form).  (No in-kernel "last
+// partial" hand-over: an agent-scope fence on this part writes back the XCD's L2 -- measured: 0.25 -> 0.92 ms for the item segments
+// at configs[1] with one fence pair per chunk.)
 // (The user-side kernel of the step ran before: nothing else reads an item row here.)
 struct ItemFuse {
     int32_t* last;       // [I]
-    int32_t* split;      // [0] = number of listed rows (zeroed before the launch), [1 + 2 e], [2 + 2 e] = row and head group of entry e
-    int32_t* split_long; // the same layout: listed rows with a whole lane group's width of continuations or more (k_bpr_item_combine fills it)
+    int32_t* split_long; // the cut segments k_seg_combine hands on to k_seg_combine_long (read by those two: SegParts)
     float* part;         // [2 groups, F] partial rows of cut segments; part_b [2 groups] their bias parts
     float* part_b;
     float* hist;         // lr ring: this kernel records lr_t of step t for the replays that follow
@@ -827,7 +801,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
                 p.st.tGi[cur] = p.step;
                 p.st.tBi[cur] = p.step;
             }
-            // (the head of a cut segment is not listed: k_bpr_item_combine finds it from the keys -- tens of thousands of appends to
+            // (the head of a cut segment is not listed: k_seg_combine finds it from the keys -- tens of thousands of appends to
             //  one counter cost more than three key reads per lane group)
         }
     };
@@ -932,205 +906,51 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     flush(p1 == p.n || (int64_t)(p.keys[p1] - p.key_off) != cur);
 }
 
-// ---- the rows on the split list (segments cut by chunk boundaries) ---------------------------------------------------------------------
-// A listed item's partial rows are the head's (slot 2 g0 + 1) and one per following lane group whose chunk still begins inside the segment
-// (slot 2 g, g = g0 + 1 ...: the sorted key at that chunk's first position is still this item).  They are added in a FIXED order -- no
-// atomics, the same bits on every run and in both forms -- and then: fused form -- Keras' Adam step on the row in place, Gi_last stamped;
-// two-pass form -- the gradient row stored into gGi / gBi for the dense pass.
-//   k_bpr_item_combine       one LANE GROUP per listed row (most rows are cut once: two partials); lane k looks at lane group g0 + 1 + k:
-//                            up to lpt - 1 continuations are summed here in ascending order, longer segments go on the long list
-//   k_bpr_item_combine_long  one WORKGROUP per row of the long list (the popular items of a Zipf catalogue: ~1 100 partials for the
-//                            hottest at B = 2^20): each lane group adds a contiguous share in ascending order, eight loads in flight, the
-//                            shares meet in LDS in lane-group order
-template <int VW, int CPL, bool IFUSE>
-__device__ __forceinline__ void item_row_finish(const el_bprmf_state& st, const ItemFuse& f, int64_t row, int sub, int lpt, const float (&gg)[CPL][VW],
-                                                float gb) {
-    const int F = st.F;
-    const float omb1 = 1.0f - f.b1, omb2 = 1.0f - f.b2;
-#pragma unroll
-    for (int q = 0; q < CPL; ++q) {
-        const int e = (sub + q * lpt) * VW;
-        if (e >= F) continue;
-        if (IFUSE) {
-            float th[VW], mm[VW], vv[VW];
-            ldv<VW>(st.Gi + row * F + e, th);
-            ldv<VW>(st.mGi + row * F + e, mm);
-            ldv<VW>(st.vGi + row * F + e, vv);
-#pragma unroll
-            for (int x = 0; x < VW; ++x) el_adam_elem(th[x], mm[x], vv[x], gg[q][x], f.lr_t, f.b1, f.b2, omb1, omb2, f.eps);
-            stv<VW>(st.Gi + row * F + e, th);
-            stv<VW>(st.mGi + row * F + e, mm);
-            stv<VW>(st.vGi + row * F + e, vv);
-        } else {
-            stv<VW>(st.gGi + row * F + e, gg[q]);
-        }
-    }
-    if (sub == 0) {
-        if (IFUSE) {
-            float beta = st.Bi[row], mb = st.mBi[row], vb2 = st.vBi[row];
-            el_adam_elem(beta, mb, vb2, gb, f.lr_t, f.b1, f.b2, omb1, omb2, f.eps);
-            st.Bi[row] = beta, st.mBi[row] = mb, st.vBi[row] = vb2;
-            f.last[row] = f.t;
-        } else {
-            st.gBi[row] = gb;
-        }
-    }
-}
-
-template <int VW, int CPL, bool IFUSE>
-__global__ __launch_bounds__(256) void k_bpr_item_combine(el_bprmf_state st, ItemFuse f, const u32* __restrict__ keys, u32 key_off, int64_t n,
-                                                          int chunk, int lpt) {
-    const int F = st.F;
-    const int64_t ent = ((int64_t)blockIdx.x * 256 + threadIdx.x) / lpt;
-    const int sub = (int)(threadIdx.x & (lpt - 1));
-    // lane group g0 looks at ITS chunk: the chunk's last segment is the head of a cut row when it goes on into chunk g0 + 1 and started
-    // inside chunk g0
-    const int64_t g0 = ent;
-    const int64_t p0 = g0 * (int64_t)chunk, p1 = p0 + chunk;
-    if (p1 >= n) return;                                        // (the last chunk's last segment ends with the data)
-    const u32 kl = keys[p1 - 1];
-    if (keys[p1] != kl) return;                                 // ends inside
-    if (keys[p0] == kl && p0 > 0 && keys[p0 - 1] == kl) return; // a middle piece: spans the whole chunk, started before it
-    const int64_t row = (int64_t)(kl - key_off);
-    const int64_t pos = (g0 + 1 + sub) * (int64_t)chunk;
-    const bool cont = pos < n && (int64_t)(keys[pos] - key_off) == row;
-    const unsigned long long bal = __ballot(cont);
-    const int lane0 = (int)(threadIdx.x & 63) & ~(lpt - 1);
-    const unsigned long long mine = lpt >= 64 ? bal : ((bal >> lane0) & ((1ull << lpt) - 1ull));
-    const unsigned long long full = lpt >= 64 ? ~0ull : ((1ull << lpt) - 1ull);
-    if (mine == full) {                                         // lpt or more continuations: the workgroup kernel's
-        if (sub == 0) {
-            const int e2 = atomicAdd(f.split_long, 1);
-            f.split_long[1 + 2 * e2] = (int32_t)row;
-            f.split_long[2 + 2 * e2] = (int32_t)g0;
-        }
-        return;
-    }
-    const int ncont = __builtin_ctzll(~mine);                   // consecutive continuations
-    float acc[CPL][VW];
-    float accb = f.part_b[2 * g0 + 1];
-#pragma unroll
-    for (int q = 0; q < CPL; ++q) {
-        const int e = (sub + q * lpt) * VW;
-#pragma unroll
-        for (int x = 0; x < VW; ++x) acc[q][x] = 0.f;
-        if (e < F) ldv<VW>(f.part + (2 * g0 + 1) * F + e, acc[q]);
-    }
-    for (int k = 1; k <= ncont; k += 4) {
-        float v[4][CPL][VW], vb[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int64_t sl = 2 * (g0 + (k + t <= ncont ? k + t : k));
-            vb[t] = f.part_b[sl];
-#pragma unroll
-            for (int q = 0; q < CPL; ++q) {
-                const int e = (sub + q * lpt) * VW;
-#pragma unroll
-                for (int x = 0; x < VW; ++x) v[t][q][x] = 0.f;
-                if (e < F) ldv<VW>(f.part + sl * F + e, v[t][q]);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            if (k + t > ncont) continue;
-            accb += vb[t];
-#pragma unroll
-            for (int q = 0; q < CPL; ++q)
-#pragma unroll
-                for (int x = 0; x < VW; ++x) acc[q][x] += v[t][q][x];
-        }
-    }
-    item_row_finish<VW, CPL, IFUSE>(st, f, row, sub, lpt, acc, accb);
-}
-
-template <int VW, int CPL, bool IFUSE>
-__global__ __launch_bounds__(256) void k_bpr_item_combine_long(el_bprmf_state st, ItemFuse f, const u32* __restrict__ keys, u32 key_off, int64_t n,
-                                                               int chunk, int lpt) {
-    const int F = st.F;
-    const int nlist = f.split_long[0];
-    __shared__ int s_np;
-    __shared__ float s_red[4096];                             // (256 / lpt) lane groups x F floats: lpt * VW * CPL >= F, CPL <= 4 -> <= 4096
-    __shared__ float s_rb[32];
-    const int ngl = 256 / lpt, gl = threadIdx.x / lpt, sub = threadIdx.x & (lpt - 1);
-    for (int ent = blockIdx.x; ent < nlist; ent += gridDim.x) {
-        const int64_t row = (int64_t)f.split_long[1 + 2 * ent];
-        const int64_t g0 = (int64_t)f.split_long[2 + 2 * ent];
-        // how many lane groups after g0 continue the segment (consecutive): the first chunk whose first key is another item ends it
-        if (threadIdx.x == 0) s_np = 0x7fffffff;
-        __syncthreads();
-        for (int base = 0; s_np == 0x7fffffff; base += 256) {
-            const int64_t gq = g0 + 1 + base + threadIdx.x, pos = gq * (int64_t)chunk;
-            const bool cont = pos < n && (int64_t)(keys[pos] - key_off) == row;
-            if (!cont) atomicMin(&s_np, base + (int)threadIdx.x);
-            __syncthreads();
-        }
-        const int ncont = s_np;                                // continuation partials: slots 2 (g0 + k), k = 1 .. ncont
-        const int np = 1 + ncont;                              // + the head's
-        const int per = (np + ngl - 1) / ngl;
-        const int k0 = gl * per, k1 = (k0 + per < np) ? k0 + per : np;
-        float acc[CPL][VW];
-#pragma unroll
-        for (int q = 0; q < CPL; ++q)
-#pragma unroll
-            for (int x = 0; x < VW; ++x) acc[q][x] = 0.f;
-        float accb = 0.f;
-        auto slot_of = [&](int k) { return k == 0 ? 2 * g0 + 1 : 2 * (g0 + k); };
-        for (int k = k0; k < k1; k += 8) {
-            float v[8][CPL][VW];
-            float vb[8];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const int kk = k + t < k1 ? k + t : k;
-                const int64_t sl = slot_of(kk);
-                vb[t] = f.part_b[sl];
-#pragma unroll
-                for (int q = 0; q < CPL; ++q) {
-                    const int e = (sub + q * lpt) * VW;
-#pragma unroll
-                    for (int x = 0; x < VW; ++x) v[t][q][x] = 0.f;
-                    if (e < F) ldv<VW>(f.part + sl * F + e, v[t][q]);
-                }
-            }
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                if (k + t >= k1) continue;
-                accb += vb[t];
-#pragma unroll
-                for (int q = 0; q < CPL; ++q)
-#pragma unroll
-                    for (int x = 0; x < VW; ++x) acc[q][x] += v[t][q][x];
-            }
-        }
-        // lane-group sums -> LDS -> added in lane-group order by group 0
+// ---- segments cut by chunk boundaries: the finish of a combined row (k_seg_combine, el_segcombine.h) -----------------------------------
+// fused form: Keras' Adam step on the row in place, Gi_last stamped; two-pass form: the gradient row stored into gGi / gBi
+template <bool IFUSE>
+struct ItemFinish {
+    float *Gi, *mGi, *vGi, *Bi, *mBi, *vBi, *gGi, *gBi;
+    int32_t* last;
+    float lr_t, b1, b2, eps;
+    int32_t t;
+    int F;
+    template <int CPL, int VW>
+    __device__ __forceinline__ void operator()(int64_t row, int sub, int lpt, const float (&gg)[CPL][VW], float gb) const {
+        const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
 #pragma unroll
         for (int q = 0; q < CPL; ++q) {
             const int e = (sub + q * lpt) * VW;
-            if (e < F) stv<VW>(s_red + gl * F + e, acc[q]);
-        }
-        if (sub == 0) s_rb[gl] = accb;
-        __syncthreads();
-        if (gl == 0) {
-            const int used = (np + per - 1) / per;              // lane groups that held partials
-            float gb = 0.f;
-            for (int h = 0; h < used; ++h) gb += s_rb[h];
-            float gg[CPL][VW];
+            if (e >= F) continue;
+            if (IFUSE) {
+                float th[VW], mm[VW], vv[VW];
+                ldv<VW>(Gi + row * F + e, th);
+                ldv<VW>(mGi + row * F + e, mm);
+                ldv<VW>(vGi + row * F + e, vv);
 #pragma unroll
-            for (int q = 0; q < CPL; ++q) {
-                const int e = (sub + q * lpt) * VW;
-#pragma unroll
-                for (int x = 0; x < VW; ++x) gg[q][x] = 0.f;
-                if (e >= F) continue;
-                for (int h = 0; h < used; ++h) {
-                    float t4[VW];
-                    ldv<VW>(s_red + h * F + e, t4);
-#pragma unroll
-                    for (int x = 0; x < VW; ++x) gg[q][x] += t4[x];
-                }
+                for (int x = 0; x < VW; ++x) el_adam_elem(th[x], mm[x], vv[x], gg[q][x], lr_t, b1, b2, omb1, omb2, eps);
+                stv<VW>(Gi + row * F + e, th);
+                stv<VW>(mGi + row * F + e, mm);
+                stv<VW>(vGi + row * F + e, vv);
+            } else {
+                stv<VW>(gGi + row * F + e, gg[q]);
             }
-            item_row_finish<VW, CPL, IFUSE>(st, f, row, sub, lpt, gg, gb);
         }
-        __syncthreads();
+        if (sub == 0) {
+            if (IFUSE) {
+                float beta = Bi[row], mb = mBi[row], vb2 = vBi[row];
+                el_adam_elem(beta, mb, vb2, gb, lr_t, b1, b2, omb1, omb2, eps);
+                Bi[row] = beta, mBi[row] = mb, vBi[row] = vb2;
+                last[row] = t;
+            } else {
+                gBi[row] = gb;
+            }
+        }
     }
+};
+template <bool IFUSE>
+static ItemFinish<IFUSE> item_finish(const el_bprmf_state& st, const ItemFuse& f) {
+    return {st.Gi, st.mGi, st.vGi, st.Bi, st.mBi, st.vBi, st.gGi, st.gBi, f.last, f.lr_t, f.b1, f.b2, f.eps, f.t, st.F};
 }
 
 // ---- host ---------------------------------------------------------------------------------
@@ -1139,7 +959,7 @@ __global__ __launch_bounds__(256) void k_bpr_item_combine_long(el_bprmf_state st
 // the item side (16 -> 128 positions: 0.84 -> 0.35 ms at B = 1M) as long as enough groups remain to fill the chip.
 static int item_chunk_for(int64_t B, int64_t I) {
     if (g_el_cur_ctx && g_el_cur_ctx->opt.ichunk > 0)           // el_ctx_set_option("ichunk"): tests pin the summation order with it
-        return g_el_cur_ctx->opt.ichunk < 16 ? 16 : (int)g_el_cur_ctx->opt.ichunk;     // (>= 16: the split list is sized for it)
+        return g_el_cur_ctx->opt.ichunk < 16 ? 16 : (int)g_el_cur_ctx->opt.ichunk;     // (>= 16: the partial slots are sized for it)
     int64_t c = (2 * B) / 8192;                          // (round 3, with the fused user side: 256 at B = 2^20 -- 1.275 -> 1.25 ms per step;
     c = c < 16 ? 16 : (c > 256 ? 256 : c);               //  128: 0.259, 256: 0.247, 384: 0.256, 512: 0.277 ms for the item segments at 100 K items)
     // Round 5: that optimum belongs to LONG segments (100 K items under 2^21 positions: 20 per item).  With a catalogue the batch
@@ -1158,14 +978,6 @@ static int user_chunk_for(int64_t B) {
     return (int)(c < 4 ? 4 : (c > 16 ? 16 : c));
 }
 
-static int bits_for(int64_t n) {
-    int b = 1;
-    while ((1LL << b) < n && b < 32) ++b;
-    return b;
-}
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct SortedWs {
     u32 *keyU_in, *valU_in, *keyU, *valU, *keyI_in, *valI_in, *keyI, *valI;
     float* s;
@@ -1173,9 +985,8 @@ struct SortedWs {
     size_t tmp_bytes;
     int32_t* rowptr;       // [U + 1] first sorted position of every user row (fused user-side kernel)
     int32_t* hpos;         // [B] per triplet: sorted head position of its user's segment (deferred decay)
-    int32_t* split;        // (unused since the combine pass finds the cut rows from the keys; kept so that the workspace layout stays put)
-    int32_t* split_long;   // the same, for the rows k_bpr_item_combine hands on to k_bpr_item_combine_long
-    float* part;           // [2 (B / 8 + 1), F] + [2 (B / 8 + 1)]: their partial rows and bias parts (NULL when carved without F)
+    int32_t* split_long;   // the cut item segments k_seg_combine hands on to k_seg_combine_long (SegParts)
+    float* part;           // [2 (B / 8 + 1), F] + [2 (B / 8 + 1)]: partial rows and bias parts of the cut item segments (NULL when carved without F)
     float* part_b;
     size_t total;
 };
@@ -1186,7 +997,7 @@ static int carve_ws(int64_t B, int64_t U, int64_t I, char* base, SortedWs* w, in
     size_t off = 0;
     auto take = [&](size_t bytes) {
         char* p = base ? base + off : nullptr;
-        off += align256(bytes);
+        off += el_align256(bytes);
         return p;
     };
     // users [0, B) and items [B, 3B) share one array each, so that one radix sort of 3B keys (users as u, items as
@@ -1200,13 +1011,12 @@ static int carve_ws(int64_t B, int64_t U, int64_t I, char* base, SortedWs* w, in
     w->s = (float*)take((size_t)B * 4);
     size_t t1 = 0, t2 = 0;
     u32* np = nullptr;
-    if (rocprim::radix_sort_pairs(nullptr, t1, np, np, np, np, (unsigned)(3 * B), 0, bits_for(U + I), (hipStream_t)0) != hipSuccess) return 1;
-    if (rocprim::radix_sort_pairs(nullptr, t2, np, np, np, np, (unsigned)(2 * B), 0, bits_for(I), (hipStream_t)0) != hipSuccess) return 1;
+    if (rocprim::radix_sort_pairs(nullptr, t1, np, np, np, np, (unsigned)(3 * B), 0, el_bits_for(U + I), (hipStream_t)0) != hipSuccess) return 1;
+    if (rocprim::radix_sort_pairs(nullptr, t2, np, np, np, np, (unsigned)(2 * B), 0, el_bits_for(I), (hipStream_t)0) != hipSuccess) return 1;
     w->tmp_bytes = t1 > t2 ? t1 : t2;
     w->tmp = take(w->tmp_bytes);
     w->rowptr = (int32_t*)take((size_t)(U + 1) * 4);
     w->hpos = (int32_t*)take((size_t)B * 4);
-    w->split = (int32_t*)take((size_t)(2 * (B / 8 + 4) + 4) * 4);
     w->split_long = (int32_t*)take((size_t)(2 * (B / 8 + 4) + 4) * 4);
     w->part = w->part_b = nullptr;
     if (F > 0) {                                         // (lane groups: at most 2 B / 16 -- item_chunk_for never goes below 16 positions)
@@ -1228,7 +1038,7 @@ static int sort_batch(hipStream_t s, const SortedWs& w, const int32_t* u, const 
               w.keyI_in, w.valI_in, (u32)U);
     ElKernelTimer t("rocprim_radix_sort_pairs", s);
     size_t tb = w.tmp_bytes;
-    EL_CHECK_HIP(rocprim::radix_sort_pairs(w.tmp, tb, w.keyU_in, w.keyU, w.valU_in, w.valU, (unsigned)(3 * B), 0, bits_for(U + I), s));
+    EL_CHECK_HIP(rocprim::radix_sort_pairs(w.tmp, tb, w.keyU_in, w.keyU, w.valU_in, w.valU, (unsigned)(3 * B), 0, el_bits_for(U + I), s));
     if (with_rowptr) EL_LAUNCH("k_bpr_rowptr", k_bpr_rowptr, dim3((unsigned)((B + 1 + 255) / 256)), dim3(256), 0, s, w.keyU, B, U, w.rowptr);
     return 0;
 }
@@ -1477,12 +1287,13 @@ static int launch_segs(const SegParams& base, hipStream_t s, int64_t B, const So
     const bool ser = base.st.replay_series != 0;
     ItemFuse fi;
     memset(&fi, 0, sizeof(fi));
-    fi.split = w.split, fi.split_long = w.split_long, fi.part = w.part, fi.part_b = w.part_b;
+    fi.split_long = w.split_long, fi.part = w.part, fi.part_b = w.part_b;
     if (ifuse) {
         fi.last = base.st.Gi_last, fi.hist = base.st.lr_hist, fi.hist_mask = base.st.lr_hist_cap - 1;
         fi.lr_t = lr_t, fi.b1 = 0.9f, fi.b2 = 0.999f, fi.eps = 1e-7f, fi.t = base.step;
     }
-    const unsigned gridC = gridI;                                 // a lane group per listed row: at most one row per item lane group
+    const SegParts sp = {pi.keys, pi.key_off, pi.n, pi.chunk, lpt, pi.st.F, fi.split_long, fi.part, fi.part_b};
+    const unsigned gridC = gridI;                                 // a combine lane group per item lane group: it looks at that one's chunk
     const unsigned gridL = (unsigned)(gi < 1024 ? (gi < 1 ? 1 : gi) : 1024);      // long rows: one workgroup each, grid-stride
     // deferred user side: two positions in flight per lane group with the heads' m / v / stamp prefetched (rows of <= 512 B per lane
     // pass: VW == 4, CPL <= 2; measured against 3, 4, 8 in flight and against a row per whole wave in round 5: profiles/r05_*)
@@ -1502,13 +1313,14 @@ static int launch_segs(const SegParams& base, hipStream_t s, int64_t B, const So
         }                                                                                                 \
         EL_CHECK_HIP(hipMemsetAsync(w.split_long, 0, 4, s));                                              \
         if (ifuse && VW == 4 && CPL_ <= 2) {                                                              \
-            EL_LAUNCH("k_bpr_item_seg", (k_bpr_item_seg<VW, CPL_, (VW == 4 && CPL_ <= 2)>), dim3(gridI), dim3(256), ldsI, s, pi, fi);   \
-            EL_LAUNCH("k_bpr_item_combine", (k_bpr_item_combine<VW, CPL_, (VW == 4 && CPL_ <= 2)>), dim3(gridC), dim3(256), 0, s, pi.st, fi, pi.keys, pi.key_off, pi.n, pi.chunk, lpt);  \
-            EL_LAUNCH("k_bpr_item_combine_long", (k_bpr_item_combine_long<VW, CPL_, (VW == 4 && CPL_ <= 2)>), dim3(gridL), dim3(256), 0, s, pi.st, fi, pi.keys, pi.key_off, pi.n, pi.chunk, lpt);  \
+            constexpr bool IF_ = VW == 4 && CPL_ <= 2;                                                    \
+            EL_LAUNCH("k_bpr_item_seg", (k_bpr_item_seg<VW, CPL_, IF_>), dim3(gridI), dim3(256), ldsI, s, pi, fi);   \
+            EL_LAUNCH("k_bpr_item_combine", (k_seg_combine<VW, CPL_, ItemFinish<IF_>>), dim3(gridC), dim3(256), 0, s, sp, item_finish<IF_>(pi.st, fi));  \
+            EL_LAUNCH("k_bpr_item_combine_long", (k_seg_combine_long<VW, CPL_, ItemFinish<IF_>>), dim3(gridL), dim3(256), 0, s, sp, item_finish<IF_>(pi.st, fi));  \
         } else {                                                                                          \
             EL_LAUNCH("k_bpr_item_seg", (k_bpr_item_seg<VW, CPL_, false>), dim3(gridI), dim3(256), ldsI, s, pi, fi);    \
-            EL_LAUNCH("k_bpr_item_combine", (k_bpr_item_combine<VW, CPL_, false>), dim3(gridC), dim3(256), 0, s, pi.st, fi, pi.keys, pi.key_off, pi.n, pi.chunk, lpt);  \
-            EL_LAUNCH("k_bpr_item_combine_long", (k_bpr_item_combine_long<VW, CPL_, false>), dim3(gridL), dim3(256), 0, s, pi.st, fi, pi.keys, pi.key_off, pi.n, pi.chunk, lpt);  \
+            EL_LAUNCH("k_bpr_item_combine", (k_seg_combine<VW, CPL_, ItemFinish<false>>), dim3(gridC), dim3(256), 0, s, sp, item_finish<false>(pi.st, fi));  \
+            EL_LAUNCH("k_bpr_item_combine_long", (k_seg_combine_long<VW, CPL_, ItemFinish<false>>), dim3(gridL), dim3(256), 0, s, sp, item_finish<false>(pi.st, fi));  \
         }                                                                                                 \
     } while (0)
     if (cpl == 1) EL_SEG(1);
@@ -1839,7 +1651,7 @@ extern "C" int el_bprmf_shard_grads(el_ctx* ctx, void* stream, const el_bprmf_st
         ElKernelTimer t("rocprim_radix_sort_pairs", s);
         size_t tb = w.tmp_bytes;
         EL_CHECK_HIP(rocprim::radix_sort_pairs(w.tmp, tb, w.keyI_in, w.keyI, w.valI_in, w.valI, (unsigned)(2 * B), 0,
-                                               bits_for(st.I), s));
+                                               el_bits_for(st.I), s));
     }
     SegParams pi;
     memset(&pi, 0, sizeof(pi));
@@ -1863,16 +1675,16 @@ extern "C" int el_bprmf_shard_grads(el_ctx* ctx, void* stream, const el_bprmf_st
     const size_t ldsI = (size_t)(256 / lpt) * BPR_ISTG * 4 * 4;
     ItemFuse fi;
     memset(&fi, 0, sizeof(fi));
-    fi.split = w.split, fi.split_long = w.split_long, fi.part = w.part, fi.part_b = w.part_b;
+    fi.split_long = w.split_long, fi.part = w.part, fi.part_b = w.part_b;
     EL_CHECK_HIP(hipMemsetAsync(w.split_long, 0, 4, s));
+    const SegParts sp = {pi.keys, pi.key_off, pi.n, pi.chunk, lpt, pi.st.F, fi.split_long, fi.part, fi.part_b};
+    const ItemFinish<false> fin = item_finish<false>(pi.st, fi);
     const unsigned gridC = gridI, gridL = (unsigned)(gi < 1024 ? (gi < 1 ? 1 : gi) : 1024);
 #define EL_IS(VW_, CPL_)                                                                                                                     \
     do {                                                                                                                                     \
         EL_LAUNCH("k_bpr_item_seg", (k_bpr_item_seg<VW_, CPL_, false>), dim3(gridI), dim3(256), ldsI, s, pi, fi);                            \
-        EL_LAUNCH("k_bpr_item_combine", (k_bpr_item_combine<VW_, CPL_, false>), dim3(gridC), dim3(256), 0, s, pi.st, fi, pi.keys, pi.key_off, \
-                  pi.n, pi.chunk, lpt);                                                                                                      \
-        EL_LAUNCH("k_bpr_item_combine_long", (k_bpr_item_combine_long<VW_, CPL_, false>), dim3(gridL), dim3(256), 0, s, pi.st, fi, pi.keys,       \
-                  pi.key_off, pi.n, pi.chunk, lpt);                                                                                          \
+        EL_LAUNCH("k_bpr_item_combine", (k_seg_combine<VW_, CPL_, ItemFinish<false>>), dim3(gridC), dim3(256), 0, s, sp, fin);                 \
+        EL_LAUNCH("k_bpr_item_combine_long", (k_seg_combine_long<VW_, CPL_, ItemFinish<false>>), dim3(gridL), dim3(256), 0, s, sp, fin);       \
     } while (0)
     if (vec) {
         if (cpl == 1) EL_IS(4, 1); else if (cpl == 2) EL_IS(4, 2); else EL_IS(4, 4);
@@ -1889,7 +1701,7 @@ static int carve_rows_ws(int64_t n, int64_t n_ids, char* base, u32** kin, u32** 
     size_t off = 0;
     auto take = [&](size_t bytes) {
         char* p = base ? base + off : nullptr;
-        off += align256(bytes);
+        off += el_align256(bytes);
         return p;
     };
     *kin = (u32*)take((size_t)n * 4);
@@ -1898,7 +1710,7 @@ static int carve_rows_ws(int64_t n, int64_t n_ids, char* base, u32** kin, u32** 
     *vout = (u32*)take((size_t)n * 4);
     size_t t1 = 0;
     u32* np = nullptr;
-    if (rocprim::radix_sort_pairs(nullptr, t1, np, np, np, np, (unsigned)n, 0, bits_for(n_ids), (hipStream_t)0) != hipSuccess) return 1;
+    if (rocprim::radix_sort_pairs(nullptr, t1, np, np, np, np, (unsigned)n, 0, el_bits_for(n_ids), (hipStream_t)0) != hipSuccess) return 1;
     *tmp_bytes = t1;
     *tmp = take(t1);
     *total = off;
@@ -1930,7 +1742,7 @@ extern "C" int el_rows_segment_sum(el_ctx* ctx, void* stream, const int32_t* ids
     EL_LAUNCH("k_iota_keys", k_iota_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ids, n, kin, vin);
     {
         ElKernelTimer t("rocprim_radix_sort_pairs", s);
-        EL_CHECK_HIP(rocprim::radix_sort_pairs(tmp, tb, kin, kout, vin, vout, (unsigned)n, 0, bits_for(n_ids), s));
+        EL_CHECK_HIP(rocprim::radix_sort_pairs(tmp, tb, kin, kout, vin, vout, (unsigned)n, 0, el_bits_for(n_ids), s));
     }
     const bool vec = (F % 4 == 0) && (((uintptr_t)rows) % 16 == 0) && (((uintptr_t)out) % 16 == 0);
     int cpl = 1;

@@ -30,16 +30,6 @@ int el_bprmf_apply_optimizer(el_ctx* ctx, hipStream_t s, const el_bprmf_state& s
 
 namespace {
 
-template <int VW>
-__device__ __forceinline__ void cml_ld(const float* p, float* dst) {
-    if (VW == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        dst[0] = t.x, dst[1] = t.y, dst[2] = t.z, dst[3] = t.w;
-    } else {
-        dst[0] = p[0];
-    }
-}
-
 struct CmlArgs {
     el_bprmf_state st;
     const int32_t* bu;
@@ -92,9 +82,9 @@ __global__ __launch_bounds__(256) void k_cml_rows(CmlArgs p) {
 #pragma unroll
             for (int x = 0; x < VW; ++x) gu[q][x] = gi[q][x] = gj[q][x] = 0.f;
             if (e < F) {
-                cml_ld<VW>(pu + e, gu[q]);
-                cml_ld<VW>(pi + e, gi[q]);
-                cml_ld<VW>(pj + e, gj[q]);
+                ldv<VW>(pu + e, gu[q]);
+                ldv<VW>(pi + e, gi[q]);
+                ldv<VW>(pj + e, gj[q]);
             }
             if (PHASE == 0) {
 #pragma unroll

@@ -170,6 +170,43 @@ typedef unsigned int u32;
 
 #define EL_WAVE 64
 
+// ---- workspace carving (host) -------------------------------------------------------
+static inline size_t el_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// key bits of a radix sort over keys in [0, n)
+static inline int el_bits_for(int64_t n) {
+    int b = 1;
+    while ((1LL << b) < n && b < 32) ++b;
+    return b;
+}
+
+// ---- a lane's VW consecutive floats of a row (VW = 1, 2, 4; p aligned to 4 VW bytes) ---
+template <int VW>
+__device__ __forceinline__ void ldv(const float* p, float* dst) {
+    if (VW == 4) {
+        float4 t = *reinterpret_cast<const float4*>(p);
+        dst[0] = t.x;
+        dst[1] = t.y;
+        dst[2] = t.z;
+        dst[3] = t.w;
+    } else if (VW == 2) {
+        float2 t = *reinterpret_cast<const float2*>(p);
+        dst[0] = t.x;
+        dst[VW - 1] = t.y;
+    } else {
+        dst[0] = p[0];
+    }
+}
+template <int VW>
+__device__ __forceinline__ void stv(float* p, const float* src) {
+    if (VW == 4) {
+        *reinterpret_cast<float4*>(p) = make_float4(src[0], src[1], src[2], src[3]);
+    } else if (VW == 2) {
+        *reinterpret_cast<float2*>(p) = make_float2(src[0], src[VW - 1]);
+    } else {
+        p[0] = src[0];
+    }
+}
+
 // ---- order-preserving float <-> uint maps (top-k keys) ---------------------------
 // key = ord(score) << 32 | ~item  : larger key == better (score desc, then index asc).
 // -0.0f is canonicalised to +0.0f so that the key order equals IEEE compare order.

@@ -179,14 +179,12 @@ __global__ void k_mt_chase(const int4* __restrict__ cand, int64_t W, int64_t n, 
     result[1] = t;
 }
 
-static size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static int64_t mt_words_for(int64_t n) { return 16 * n + 8 * MT_N; }
 
 extern "C" size_t el_bpr_sample_mt19937_ws_bytes(int64_t n) {
     if (n <= 0) return 0;
     const int64_t W = mt_words_for(n);
-    return a256((size_t)W * 4) + a256((size_t)W * 16) + a256((MT_N + 1) * 4) + a256(16);
+    return el_align256((size_t)W * 4) + el_align256((size_t)W * 16) + el_align256((MT_N + 1) * 4) + el_align256(16);
 }
 
 extern "C" int el_bpr_sample_mt19937(el_ctx* ctx, void* stream, uint32_t* mt_state, const int64_t* lists_indptr,
@@ -203,9 +201,9 @@ extern "C" int el_bpr_sample_mt19937(el_ctx* ctx, void* stream, uint32_t* mt_sta
     EL_REQUIRE(ws != nullptr && ws_bytes >= el_bpr_sample_mt19937_ws_bytes(n), "el_bpr_sample_mt19937: workspace too small");
     char* base = (char*)ws;
     u32* words = (u32*)base;
-    int4* cand = (int4*)(base + a256((size_t)W * 4));
-    u32* backup = (u32*)(base + a256((size_t)W * 4) + a256((size_t)W * 16));
-    int64_t* result = (int64_t*)((char*)backup + a256((MT_N + 1) * 4));
+    int4* cand = (int4*)(base + el_align256((size_t)W * 4));
+    u32* backup = (u32*)(base + el_align256((size_t)W * 4) + el_align256((size_t)W * 16));
+    int64_t* result = (int64_t*)((char*)backup + el_align256((MT_N + 1) * 4));
     hipStream_t s = (hipStream_t)stream;
     EL_CHECK_HIP(hipMemcpyAsync(backup, mt_state, (MT_N + 1) * 4, hipMemcpyDeviceToDevice, s));
     EL_LAUNCH("k_mt_generate", k_mt_generate, dim3(1), dim3(256), 0, s, mt_state, words, W, (int64_t)0, (const u32*)backup);

@@ -1183,11 +1183,6 @@ static unsigned head_grid(int64_t n, el_ctx* ctx) {
 }
 
 // ---- the step workspace (el_nmf_state.step_ws): sort buffers, the long-segment list, the MF factor copies, partial sums ------------------
-static int nmf_bits_for(int64_t n) {
-    int b = 1;
-    while (b < 32 && (1LL << b) < n) ++b;
-    return b;
-}
 struct NmfStepWs {
     // two complete sort sets: el_nmf_presort orders the NEXT batch into the set the current step does not use
     u32 *kin[2], *kout[2];
@@ -1217,7 +1212,7 @@ static int nmf_carve(el_ctx* ctx, const el_nmf_state* st, void* base, NmfStepWs*
     size_t tb = 0;
     u32* np = nullptr;
     int32_t* nv = nullptr;
-    if (rocprim::radix_sort_pairs(nullptr, tb, np, np, nv, nv, (unsigned)(2 * B), 0, nmf_bits_for(st->U + st->I), (hipStream_t)0) != hipSuccess) {
+    if (rocprim::radix_sort_pairs(nullptr, tb, np, np, nv, nv, (unsigned)(2 * B), 0, el_bits_for(st->U + st->I), (hipStream_t)0) != hipSuccess) {
         el_set_error("el_nmf: rocprim::radix_sort_pairs size query failed");
         return 1;
     }
@@ -1318,7 +1313,7 @@ static int nmf_sort_into(el_ctx* ctx, hipStream_t s, const el_nmf_state* st, con
     ElKernelTimer tm("rocprim_radix_sort_pairs", s);
     size_t tb = w->tmp_bytes;
     EL_CHECK_HIP(rocprim::radix_sort_pairs(w->tmp[set], tb, w->kin[set], w->kout[set], w->vin[set], w->vout[set], (unsigned)(2 * n), 0,
-                                           nmf_bits_for(st->U + st->I), s));
+                                           el_bits_for(st->U + st->I), s));
     (void)ctx;
     return 0;
 }

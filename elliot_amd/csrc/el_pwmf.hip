@@ -27,23 +27,6 @@ __global__ void k_adam_dense(float* th, float* g, float* m, float* v, int64_t n,
 
 namespace {
 
-template <int VW>
-__device__ __forceinline__ void pw_ld(const float* p, float* dst) {
-    if (VW == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        dst[0] = t.x, dst[1] = t.y, dst[2] = t.z, dst[3] = t.w;
-    } else {
-        dst[0] = p[0];
-    }
-}
-template <int VW>
-__device__ __forceinline__ void pw_st(float* p, const float* src) {
-    if (VW == 4)
-        *reinterpret_cast<float4*>(p) = make_float4(src[0], src[1], src[2], src[3]);
-    else
-        p[0] = src[0];
-}
-
 __device__ __forceinline__ float pw_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float pw_softplus(float x) {           // log(1 + exp(x)) without overflow
     if (x > 15.0f) return x + expf(-x);
@@ -84,8 +67,8 @@ __global__ __launch_bounds__(256) void k_pw_fwd(PwFwd p) {
             const int e = (sub + q * lpt) * VW;
             if (e < F) {
                 float a[VW], c[VW];
-                pw_ld<VW>(pu + e, a);
-                pw_ld<VW>(pi + e, c);
+                ldv<VW>(pu + e, a);
+                ldv<VW>(pi + e, c);
 #pragma unroll
                 for (int x = 0; x < VW; ++x) dot = fmaf(a[x], c[x], dot);
             }
@@ -97,8 +80,8 @@ __global__ __launch_bounds__(256) void k_pw_fwd(PwFwd p) {
                 const int e = (sub + q * lpt) * VW;
                 if (e < F) {
                     float a[VW], c[VW];
-                    pw_ld<VW>(pu + e, a);
-                    pw_ld<VW>(pi + e, c);
+                    ldv<VW>(pu + e, a);
+                    ldv<VW>(pi + e, c);
 #pragma unroll
                     for (int x = 0; x < VW; ++x) sq += a[x] * a[x] + c[x] * c[x];
                 }
@@ -164,7 +147,6 @@ struct PwSeg {
     // pieces of segments cut by chunk boundaries (el_segcombine.h)
     float* part;
     float* part_b;
-    int32_t* split;
 };
 
 // finish of a combined row: the gradient row and its bias part, stored
@@ -177,7 +159,7 @@ struct PwFinish {
 #pragma unroll
         for (int q = 0; q < CPL; ++q) {
             const int e = (sub + q * lpt) * VW;
-            if (e < F) sc_st<VW>(g + row * F + e, gg[q]);
+            if (e < F) stv<VW>(g + row * F + e, gg[q]);
         }
         if (sub == 0 && gb) gb[row] = b;
     }
@@ -199,7 +181,7 @@ __global__ __launch_bounds__(256) void k_pw_seg(PwSeg p) {
     int cnt = 0;
     auto flush = [&](bool ends_inside) {
         const bool plain = started_inside && ends_inside;
-        // a cut piece: slot 2 grp + 1 when the segment starts in this chunk (the head piece: it lists the row), 2 grp otherwise
+        // a cut piece: slot 2 grp + 1 when the segment starts in this chunk (the head piece), 2 grp otherwise
         const int64_t slot = 2 * grp + (started_inside ? 1 : 0);
         float* g = plain ? p.g + cur * F : p.part + slot * F;
         const float w = (float)cnt * p.l_w;
@@ -212,11 +194,11 @@ __global__ __launch_bounds__(256) void k_pw_seg(PwSeg p) {
                 for (int x = 0; x < VW; ++x) v[x] = acc[q][x];
                 if (w != 0.f) {
                     float r[VW];
-                    pw_ld<VW>(p.own + cur * F + e, r);
+                    ldv<VW>(p.own + cur * F + e, r);
 #pragma unroll
                     for (int x = 0; x < VW; ++x) v[x] += w * r[x];
                 }
-                pw_st<VW>(g + e, v);
+                stv<VW>(g + e, v);
             }
         }
         if (sub == 0) {
@@ -262,7 +244,7 @@ __global__ __launch_bounds__(256) void k_pw_seg(PwSeg p) {
                     const int e = (sub + q * lpt) * VW;
 #pragma unroll
                     for (int x = 0; x < VW; ++x) rr[t][q][x] = 0.f;
-                    if (okv[t] && e < F) pw_ld<VW>(po + e, rr[t][q]);
+                    if (okv[t] && e < F) ldv<VW>(po + e, rr[t][q]);
                 }
             }
 #pragma unroll
@@ -359,20 +341,13 @@ __global__ __launch_bounds__(64) void k_rerank_rows_long(int32_t* __restrict__ i
     }
 }
 
-int bits_for(int64_t n) {
-    int b = 1;
-    while ((1LL << b) < n && b < 32) ++b;
-    return b;
-}
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct PwWs {
     u32 *keyU_in, *valU_in, *keyU, *valU, *keyI_in, *valI_in, *keyI, *valI;
     float* coef;
     void* tmp;
     size_t tmp_bytes, total;
     float *part, *part_b;          // partial rows of cut segments: 2 per lane group of the finer side
-    int32_t *split, *split_long;
+    int32_t* split_long;           // the cut segments k_seg_combine hands on to k_seg_combine_long (SegParts)
 };
 
 int item_chunk(int64_t n);
@@ -382,7 +357,7 @@ int carve(int64_t n, int64_t U, int64_t I, int F, char* base, PwWs* w) {
     size_t off = 0;
     auto take = [&](size_t bytes) {
         char* p = base ? base + off : nullptr;
-        off += align256(bytes);
+        off += el_align256(bytes);
         return p;
     };
     u32** slots[4] = {&w->keyU_in, &w->valU_in, &w->keyU, &w->valU};      // users [0, n), items [n, 2n) of one array each
@@ -394,9 +369,9 @@ int carve(int64_t n, int64_t U, int64_t I, int F, char* base, PwWs* w) {
     w->coef = (float*)take((size_t)n * 4);
     size_t t1 = 0, t2 = 0, t3 = 0;
     u32* np = nullptr;
-    if (rocprim::radix_sort_pairs(nullptr, t1, np, np, np, np, (unsigned)(2 * n), 0, bits_for(U + I), (hipStream_t)0) != hipSuccess) return 1;
-    if (rocprim::radix_sort_pairs(nullptr, t2, np, np, np, np, (unsigned)n, 0, bits_for(U), (hipStream_t)0) != hipSuccess) return 1;
-    if (rocprim::radix_sort_pairs(nullptr, t3, np, np, np, np, (unsigned)n, 0, bits_for(U + I), (hipStream_t)0) != hipSuccess) return 1;
+    if (rocprim::radix_sort_pairs(nullptr, t1, np, np, np, np, (unsigned)(2 * n), 0, el_bits_for(U + I), (hipStream_t)0) != hipSuccess) return 1;
+    if (rocprim::radix_sort_pairs(nullptr, t2, np, np, np, np, (unsigned)n, 0, el_bits_for(U), (hipStream_t)0) != hipSuccess) return 1;
+    if (rocprim::radix_sort_pairs(nullptr, t3, np, np, np, np, (unsigned)n, 0, el_bits_for(U + I), (hipStream_t)0) != hipSuccess) return 1;
     if (t2 > t1) t1 = t2;
     if (t3 > t1) t1 = t3;
     w->tmp_bytes = t1;
@@ -405,7 +380,6 @@ int carve(int64_t n, int64_t U, int64_t I, int F, char* base, PwWs* w) {
     const int64_t groups = (n + (cu < ci ? cu : ci) - 1) / (cu < ci ? cu : ci) + 1;
     w->part = (float*)take((size_t)2 * groups * (size_t)(F > 0 ? F : 1) * 4);
     w->part_b = (float*)take((size_t)2 * groups * 4);
-    w->split = (int32_t*)take((size_t)(2 * groups + 4) * 4);
     w->split_long = (int32_t*)take((size_t)(2 * groups + 4) * 4);
     w->total = off;
     return 0;
@@ -468,11 +442,11 @@ template <int VW>
 int launch_seg(PwSeg p, const PwWs& w, const char* nm, hipStream_t s) {
     int cpl = 1;
     p.lpt = el_pick_lpt(p.F, VW, &cpl);
-    p.part = w.part, p.part_b = w.part_b, p.split = w.split;
+    p.part = w.part, p.part_b = w.part_b;
     const int64_t groups = (p.n + p.chunk - 1) / p.chunk;
     const unsigned grid = (unsigned)((groups * p.lpt + 255) / 256);
     EL_CHECK_HIP(hipMemsetAsync(w.split_long, 0, 4, s));
-    SegParts sp = {p.keys, p.key_off, p.n, p.chunk, p.lpt, p.F, nullptr, w.split_long, w.part, w.part_b};
+    SegParts sp = {p.keys, p.key_off, p.n, p.chunk, p.lpt, p.F, w.split_long, w.part, w.part_b};
     PwFinish fin = {p.g, p.gb, p.F};
     const unsigned gl = (unsigned)(groups < 1024 ? (groups < 1 ? 1 : groups) : 1024);
 #define EL_PW_SEG(CPL_)                                                                                                \
@@ -546,11 +520,11 @@ static int pw_grads(el_ctx* ctx, hipStream_t s, const el_pwmf_state* stp, const 
         ElKernelTimer t("rocprim_radix_sort_pairs", s);
         size_t tb = w.tmp_bytes;
         if (do_users && do_items)                                  // one sort orders both sides (every user key < every item key)
-            EL_CHECK_HIP(rocprim::radix_sort_pairs(w.tmp, tb, w.keyU_in, w.keyU, w.valU_in, w.valU, (unsigned)(2 * n), 0, bits_for(st.U + st.I), s));
+            EL_CHECK_HIP(rocprim::radix_sort_pairs(w.tmp, tb, w.keyU_in, w.keyU, w.valU_in, w.valU, (unsigned)(2 * n), 0, el_bits_for(st.U + st.I), s));
         else if (do_users)
-            EL_CHECK_HIP(rocprim::radix_sort_pairs(w.tmp, tb, w.keyU_in, w.keyU, w.valU_in, w.valU, (unsigned)n, 0, bits_for(st.U), s));
+            EL_CHECK_HIP(rocprim::radix_sort_pairs(w.tmp, tb, w.keyU_in, w.keyU, w.valU_in, w.valU, (unsigned)n, 0, el_bits_for(st.U), s));
         else
-            EL_CHECK_HIP(rocprim::radix_sort_pairs(w.tmp, tb, w.keyI_in, w.keyI, w.valI_in, w.valI, (unsigned)n, 0, bits_for(st.U + st.I), s));
+            EL_CHECK_HIP(rocprim::radix_sort_pairs(w.tmp, tb, w.keyI_in, w.keyI, w.valI_in, w.valI, (unsigned)n, 0, el_bits_for(st.U + st.I), s));
     }
     const float l_w = st.kind == EL_PW_LOGISTIC ? st.l_w : 0.f;
     if (do_users) {
@@ -659,7 +633,7 @@ static int64_t pw_loop_cap(int64_t events, int64_t B) {
 
 extern "C" size_t el_pwmf_train_loop_ws_bytes(int64_t events, int64_t B) {
     if (events <= 0 || B <= 0) return 0;
-    return align256((size_t)pw_loop_cap(events, B) * 12);
+    return el_align256((size_t)pw_loop_cap(events, B) * 12);
 }
 
 extern "C" int el_pwmf_train_loop(el_ctx* ctx, void* stream, const el_pwmf_state* stp, const int64_t* pos_indptr,

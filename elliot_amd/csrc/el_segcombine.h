@@ -1,13 +1,15 @@
-// Rows of a sorted-segment gradient pass that were cut by chunk boundaries, finished WITHOUT floating-point atomics (round 6; the
-// scheme of el_bpr_sorted.hip's k_bpr_item_combine, generic over what "finish" means: el_pwmf.hip stores the row to its gradient table).
+// Rows of a sorted-segment gradient pass that were cut by chunk boundaries, finished WITHOUT floating-point atomics (round 6; used by
+// el_bpr_sorted.hip, whose finish is Keras' Adam step on the item row or a store to gGi / gBi, and el_pwmf.hip, which stores the row to
+// its gradient table).
 //
 // The segment pass gives every lane group a fixed chunk of sorted positions.  A segment that lies inside one chunk is finished there.
 // A piece of a segment that is cut goes to a partial slot instead: slot 2 g + 1 for the piece that STARTS inside group g's chunk (the
-// head piece: it also appends (row, g) to the split list), slot 2 g for a piece that started before the chunk (at most one of each per
-// group).  The pieces of a listed row are then the head's and one per following lane group whose chunk still begins inside the segment
-// (the sorted key at that chunk's first position is still this row), and they are added here in a FIXED order:
-//   k_seg_combine       one lane group per listed row: lane k looks at group g0 + 1 + k; up to lpt - 1 continuations are summed in
-//                       ascending order, longer segments go on the long list
+// head piece), slot 2 g for a piece that started before the chunk (at most one of each per group).  The pieces of a cut row are then
+// the head's and one per following lane group whose chunk still begins inside the segment (the sorted key at that chunk's first
+// position is still this row), and they are added here in a FIXED order:
+//   k_seg_combine       one lane group per lane group of the segment pass, which finds the head piece at the end of ITS chunk from the
+//                       keys: lane k looks at group g0 + 1 + k; up to lpt - 1 continuations are summed in ascending order, longer
+//                       segments go on the long list
 //   k_seg_combine_long  one workgroup per row of the long list: each lane group adds a contiguous share in ascending order, eight loads
 //                       in flight, the shares are added in lane-group order
 // The same bits on every run.  FIN: a trivially copyable functor, fin(row, sub, lpt, g[CPL][VW], gb) called by the lanes of ONE lane
@@ -20,52 +22,24 @@ struct SegParts {
     u32 key_off;            // key - key_off = row
     int64_t n;              // sorted positions
     int chunk, lpt, F;
-    int32_t* split;         // [1 + 2 (groups + 1)]: count, then (row, head lane group) pairs; NULL: k_seg_combine finds the heads itself
-    int32_t* split_long;    // the same, filled by k_seg_combine
+    int32_t* split_long;    // [1 + 2 (groups + 1)]: count (zeroed before k_seg_combine), then (row, head lane group) pairs
     float* part;            // [2 groups, F]
     float* part_b;          // [2 groups]
 };
 
-template <int VW>
-__device__ __forceinline__ void sc_ld(const float* __restrict__ p, float (&v)[VW]) {
-    if (VW == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        v[0] = t.x, v[1 % VW] = t.y, v[2 % VW] = t.z, v[3 % VW] = t.w;
-    } else {
-#pragma unroll
-        for (int x = 0; x < VW; ++x) v[x] = p[x];
-    }
-}
-template <int VW>
-__device__ __forceinline__ void sc_st(float* __restrict__ p, const float (&v)[VW]) {
-    if (VW == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1 % VW], v[2 % VW], v[3 % VW]);
-    else {
-#pragma unroll
-        for (int x = 0; x < VW; ++x) p[x] = v[x];
-    }
-}
-
 template <int VW, int CPL, typename FIN>
 __global__ __launch_bounds__(256) void k_seg_combine(SegParts sp, FIN fin) {
     const int F = sp.F, lpt = sp.lpt;
-    const int64_t ent = ((int64_t)blockIdx.x * 256 + threadIdx.x) / lpt;
+    // no list of cut rows (a contended counter costs more than it saves where chunks are a few positions long): lane group g looks at
+    // ITS chunk -- the last segment of chunk g is a cut head when it goes on into chunk g + 1 and started inside chunk g
+    const int64_t g0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) / lpt;
     const int sub = (int)(threadIdx.x & (lpt - 1));
-    int64_t row, g0;
-    if (sp.split) {                                             // listed heads
-        if (ent >= (int64_t)sp.split[0]) return;
-        row = (int64_t)sp.split[1 + 2 * ent];
-        g0 = (int64_t)sp.split[2 + 2 * ent];
-    } else {
-        // no list (a contended counter costs more than it saves where chunks are a few positions long): lane group g looks at ITS chunk --
-        // the last segment of chunk g is a cut head when it goes on into chunk g + 1 and started inside chunk g
-        g0 = ent;
-        const int64_t p0 = g0 * (int64_t)sp.chunk, p1 = p0 + sp.chunk;
-        if (p1 >= sp.n) return;                                 // (the last chunk's last segment ends with the data)
-        const u32 kl = sp.keys[p1 - 1];
-        if (sp.keys[p1] != kl) return;                          // ends inside
-        if (sp.keys[p0] == kl && p0 > 0 && sp.keys[p0 - 1] == kl) return;      // a middle piece: spans the whole chunk, started before it
-        row = (int64_t)(kl - sp.key_off);
-    }
+    const int64_t p0 = g0 * (int64_t)sp.chunk, p1 = p0 + sp.chunk;
+    if (p1 >= sp.n) return;                                     // (the last chunk's last segment ends with the data)
+    const u32 kl = sp.keys[p1 - 1];
+    if (sp.keys[p1] != kl) return;                              // ends inside
+    if (sp.keys[p0] == kl && p0 > 0 && sp.keys[p0 - 1] == kl) return;          // a middle piece: spans the whole chunk, started before it
+    const int64_t row = (int64_t)(kl - sp.key_off);
     const int64_t pos = (g0 + 1 + sub) * (int64_t)sp.chunk;
     const bool cont = pos < sp.n && (int64_t)(sp.keys[pos] - sp.key_off) == row;
     const unsigned long long bal = __ballot(cont);
@@ -88,7 +62,7 @@ __global__ __launch_bounds__(256) void k_seg_combine(SegParts sp, FIN fin) {
         const int e = (sub + q * lpt) * VW;
 #pragma unroll
         for (int x = 0; x < VW; ++x) acc[q][x] = 0.f;
-        if (e < F) sc_ld<VW>(sp.part + (2 * g0 + 1) * F + e, acc[q]);
+        if (e < F) ldv<VW>(sp.part + (2 * g0 + 1) * F + e, acc[q]);
     }
     for (int k = 1; k <= ncont; k += 4) {
         float v[4][CPL][VW], vb[4];
@@ -101,7 +75,7 @@ __global__ __launch_bounds__(256) void k_seg_combine(SegParts sp, FIN fin) {
                 const int e = (sub + q * lpt) * VW;
 #pragma unroll
                 for (int x = 0; x < VW; ++x) v[t][q][x] = 0.f;
-                if (e < F) sc_ld<VW>(sp.part + sl * F + e, v[t][q]);
+                if (e < F) ldv<VW>(sp.part + sl * F + e, v[t][q]);
             }
         }
 #pragma unroll
@@ -128,15 +102,21 @@ __global__ __launch_bounds__(256) void k_seg_combine_long(SegParts sp, FIN fin) 
     for (int ent = blockIdx.x; ent < nlist; ent += gridDim.x) {
         const int64_t row = (int64_t)sp.split_long[1 + 2 * ent];
         const int64_t g0 = (int64_t)sp.split_long[2 + 2 * ent];
+        // how many lane groups after g0 continue the segment (consecutive): the first chunk whose first key is another row ends it.
+        // 256 chunks per pass; every wave must leave after the SAME pass: each wave reads s_np only once every atomicMin of the pass is
+        // done (first barrier), and no wave lowers it in the next pass before every wave has read it (second barrier)
         if (threadIdx.x == 0) s_np = 0x7fffffff;
         __syncthreads();
-        for (int base = 0; s_np == 0x7fffffff; base += 256) {
+        int ncont;                                             // continuation partials: slots 2 (g0 + k), k = 1 .. ncont
+        for (int base = 0;; base += 256) {
             const int64_t gq = g0 + 1 + base + threadIdx.x, pos = gq * (int64_t)sp.chunk;
             const bool cont = pos < sp.n && (int64_t)(sp.keys[pos] - sp.key_off) == row;
             if (!cont) atomicMin(&s_np, base + (int)threadIdx.x);
             __syncthreads();
+            ncont = s_np;
+            __syncthreads();
+            if (ncont != 0x7fffffff) break;
         }
-        const int ncont = s_np;                                // continuation partials: slots 2 (g0 + k), k = 1 .. ncont
         const int np = 1 + ncont;                              // + the head's
         const int per = (np + ngl - 1) / ngl;
         const int k0 = gl * per, k1 = (k0 + per < np) ? k0 + per : np;
@@ -160,7 +140,7 @@ __global__ __launch_bounds__(256) void k_seg_combine_long(SegParts sp, FIN fin) 
                     const int e = (sub + q * lpt) * VW;
 #pragma unroll
                     for (int x = 0; x < VW; ++x) v[t][q][x] = 0.f;
-                    if (e < F) sc_ld<VW>(sp.part + sl * F + e, v[t][q]);
+                    if (e < F) ldv<VW>(sp.part + sl * F + e, v[t][q]);
                 }
             }
 #pragma unroll
@@ -176,7 +156,7 @@ __global__ __launch_bounds__(256) void k_seg_combine_long(SegParts sp, FIN fin) 
 #pragma unroll
         for (int q = 0; q < CPL; ++q) {
             const int e = (sub + q * lpt) * VW;
-            if (e < F) sc_st<VW>(s_red + gl * F + e, acc[q]);
+            if (e < F) stv<VW>(s_red + gl * F + e, acc[q]);
         }
         if (sub == 0) s_rb[gl] = accb;
         __syncthreads();
@@ -193,7 +173,7 @@ __global__ __launch_bounds__(256) void k_seg_combine_long(SegParts sp, FIN fin) 
                 if (e >= F) continue;
                 for (int h = 0; h < used; ++h) {
                     float t4[VW];
-                    sc_ld<VW>(s_red + h * F + e, t4);
+                    ldv<VW>(s_red + h * F + e, t4);
 #pragma unroll
                     for (int x = 0; x < VW; ++x) gg[q][x] += t4[x];
                 }

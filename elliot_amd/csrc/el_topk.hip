@@ -685,10 +685,8 @@ static int64_t list_cap_for(int64_t n_users) {
     return c < LIST_DENSE ? LIST_DENSE : c;       // (the dense tier borrows the split scratch for its partial lists)
 }
 
-static size_t a256_(size_t x) { return (x + 255) & ~(size_t)255; }
-
 size_t el_topk_list_scratch_bytes(int64_t n_users, int64_t I_local, int k) {
-    return 2 * a256_((size_t)LIST_SPLIT * (size_t)list_cap_for(n_users) * (size_t)k * 4) + a256_((size_t)LIST_DENSE * (size_t)I_local * 4);
+    return 2 * el_align256((size_t)LIST_SPLIT * (size_t)list_cap_for(n_users) * (size_t)k * 4) + el_align256((size_t)LIST_DENSE * (size_t)I_local * 4);
 }
 
 int el_topk_run_list(const TopkParams& p0, void* scratch, size_t scratch_bytes, hipStream_t st) {
@@ -696,8 +694,8 @@ int el_topk_run_list(const TopkParams& p0, void* scratch, size_t scratch_bytes, 
     const int64_t cap = list_cap_for(n_users);
     EL_REQUIRE(scratch && scratch_bytes >= el_topk_list_scratch_bytes(n_users, p0.I_local, p0.k), "el_topk_run_list: scratch too small");
     int32_t* part_idx = (int32_t*)scratch;
-    float* part_val = (float*)((char*)scratch + a256_((size_t)LIST_SPLIT * (size_t)cap * (size_t)p0.k * 4));
-    float* preds = (float*)((char*)scratch + 2 * a256_((size_t)LIST_SPLIT * (size_t)cap * (size_t)p0.k * 4));
+    float* part_val = (float*)((char*)scratch + el_align256((size_t)LIST_SPLIT * (size_t)cap * (size_t)p0.k * 4));
+    float* preds = (float*)((char*)scratch + 2 * el_align256((size_t)LIST_SPLIT * (size_t)cap * (size_t)p0.k * 4));
     if (p0.I_local > 0) {                            // tier 1: entries [0, LIST_DENSE)
         TopkParams d = p0;
         d.ulist_skip = 0;

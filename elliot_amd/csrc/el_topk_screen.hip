@@ -885,8 +885,6 @@ __global__ __launch_bounds__(256) void k_screen_flags(ScreenParams sp, int64_t n
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-static size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static int screen_fp(int F) { return F <= 32 ? 32 : (F <= 64 ? 64 : (F <= 128 ? 128 : 256)); }
 
 bool el_topk_screen_eligible(int F, int k, const void* cand) { return cand == nullptr && F >= 1 && F <= 256 && k >= 1 && k <= 128; }
@@ -944,8 +942,8 @@ static ScreenPolicy screen_policy(int k, int64_t I_local) {
 size_t el_topk_screen_ws_bytes(int64_t n_users, int64_t I_local, int F, int k, int64_t excl_nnz) {
     const int FP = screen_fp(F);
     if (excl_nnz < 0) excl_nnz = 0;
-    return a256((size_t)I_local * FP * 2) + a256(16) + a256((size_t)n_users * SCR_TI * 4) + 8 * a256((size_t)n_users * 4) + a256((size_t)I_local * 8) +
-           a256(el_topk_list_scratch_bytes(n_users, I_local, k)) + a256(((size_t)n_users * screen_policy(k, I_local).surv + (size_t)excl_nnz) * 12);
+    return el_align256((size_t)I_local * FP * 2) + el_align256(16) + el_align256((size_t)n_users * SCR_TI * 4) + 8 * el_align256((size_t)n_users * 4) + el_align256((size_t)I_local * 8) +
+           el_align256(el_topk_list_scratch_bytes(n_users, I_local, k)) + el_align256(((size_t)n_users * screen_policy(k, I_local).surv + (size_t)excl_nnz) * 12);
 }
 
 template <int FP, int MODE, int NW, bool PROF>
@@ -1028,29 +1026,29 @@ int el_topk_screen_run(const TopkParams& p, void* ws, size_t ws_bytes, hipStream
     ScreenParams sp;
     sp.t = p;
     unsigned short* gib = (unsigned short*)base;                  // item side first: its place does not depend on n_users, so the
-    base += a256((size_t)p.I_local * FP * 2);                     // image survives from block to block (EL_TOPK_ITEMS_UNCHANGED)
+    base += el_align256((size_t)p.I_local * FP * 2);              // image survives from block to block (EL_TOPK_ITEMS_UNCHANGED)
     sp.inorm = (float2*)base;
-    base += a256((size_t)p.I_local * 8);
+    base += el_align256((size_t)p.I_local * 8);
     float* stats = (float*)base;
-    base += a256(16);
+    base += el_align256(16);
     sp.smax = (float*)base;
-    base += a256((size_t)n_users * SCR_TI * 4);
+    base += el_align256((size_t)n_users * SCR_TI * 4);
     sp.thr = (float*)base;
-    base += a256((size_t)n_users * 4);
+    base += el_align256((size_t)n_users * 4);
     sp.cnt = (int32_t*)base;
-    base += a256((size_t)n_users * 4);
+    base += el_align256((size_t)n_users * 4);
     sp.ovf = (int32_t*)base;
-    base += a256((size_t)n_users * 4);
+    base += el_align256((size_t)n_users * 4);
     sp.ulist = (int32_t*)base;
-    base += a256((size_t)n_users * 4);
+    base += el_align256((size_t)n_users * 4);
     sp.Tg = (float*)base;
-    base += a256((size_t)n_users * 4);
+    base += el_align256((size_t)n_users * 4);
     sp.Eu = (float*)base;
-    base += a256((size_t)n_users * 4);
+    base += el_align256((size_t)n_users * 4);
     sp.nuv = (float*)base;
-    base += a256((size_t)n_users * 4);
+    base += el_align256((size_t)n_users * 4);
     sp.duv = (float*)base;
-    base += a256((size_t)n_users * 4);
+    base += el_align256((size_t)n_users * 4);
     const ScreenPolicy pol = screen_policy(p.k, p.I_local);
     sp.surv = pol.surv;
     sp.stride = pol.stride;
@@ -1061,7 +1059,7 @@ int el_topk_screen_run(const TopkParams& p, void* ws, size_t ws_bytes, hipStream
     sp.ulist_n = (int32_t*)(stats + 2);
     void* fb_scratch = base;
     const size_t fb_bytes = el_topk_list_scratch_bytes(n_users, p.I_local, p.k);
-    base += a256(fb_bytes);
+    base += el_align256(fb_bytes);
     sp.list_cap = (int64_t)(((char*)ws + ws_bytes - base) / 12) & ~(int64_t)31;   // whatever the caller provisioned for surv*U + nnz
     sp.lists = (u64*)base;
     sp.lsc = (float*)(base + (size_t)sp.list_cap * 8);

@@ -196,25 +196,30 @@ def test_bprsgd_conflict_free_batch_equals_oracle(ctx):
 
 
 def test_sorted_path_is_deterministic(ctx):
-    """Stable sort -> fixed summation order: rows whose segment touches at most two chunks get identical bits
-    on every run (float add is commutative); only longer segments are combined with order-dependent atomics."""
+    """Stable sort -> fixed summation order, and the partial rows of a segment cut by chunk boundaries are added in chunk
+    order (k_seg_combine / k_seg_combine_long, el_segcombine.h): two runs give the same bits in every table.  The hottest item's
+    segment spans more than 256 chunks, so the workgroup kernel's scan for the segment's end takes more than one pass."""
     rs = np.random.RandomState(77)
     U, I, F, B = 400000, 500, 64, 20000
     Gu, Gi, Bi = _setup(rs, U, I, F)
     d = ctx.device
-    u = torch.from_numpy(rs.randint(0, U, B).astype(np.int32)).to(d)
-    i = torch.from_numpy((rs.zipf(1.3, B) % I).astype(np.int32)).to(d)     # very hot items -> multi-chunk segments
-    j = torch.from_numpy(rs.randint(0, I, B).astype(np.int32)).to(d)
+    u_h = rs.randint(0, U, B).astype(np.int32)
+    i_h = (rs.zipf(1.3, B) % I).astype(np.int32)     # very hot items -> multi-chunk segments
+    j_h = rs.randint(0, I, B).astype(np.int32)
+    # the item side sorts the 2 B positions by item; at this batch size a lane group's chunk is 16 positions (the smallest)
+    cnt = np.bincount(np.concatenate([i_h, j_h]), minlength=I)
+    hot = int(cnt.argmax())
+    p0 = int(cnt[:hot].sum())
+    assert (p0 + int(cnt[hot]) - 1) // 16 - p0 // 16 + 1 > 256
+    u, i, j = (torch.from_numpy(x).to(d) for x in (u_h, i_h, j_h))
     outs = []
     for _ in range(2):
         st = ops.BprmfDeviceState(ctx, Gu, Gi, Bi, optimizer="adam_tf_dense")
-        for _s in range(1):   # one step: later steps inherit the item rows' order-dependent round-off
-            st.train_step(u, i, j, 0.01, 0.1, 0.001, algo="sorted")
+        st.train_step(u, i, j, 0.01, 0.1, 0.001, algo="sorted")
         outs.append((cpu(st.Gu).copy(), cpu(st.Gi).copy(), cpu(st.Bi).copy(), st.pop_loss()))
-    # multi-chunk segments are combined with a few atomics, so only single-chunk rows are bit-stable:
-    # users (short segments) must be identical; items/bias agree to round-off
-    assert np.array_equal(outs[0][0], outs[1][0])
-    assert np.abs(outs[0][1] - outs[1][1]).max() < 1e-4 and abs(outs[0][3] - outs[1][3]) < 1e-3
+    for k in range(3):
+        assert np.array_equal(outs[0][k].view(np.int32), outs[1][k].view(np.int32)), ("Gu", "Gi", "Bi")[k]
+    assert abs(outs[0][3] - outs[1][3]) < 1e-3       # (the loss is summed with double-precision atomics)
 
 
 # ---------------------------------------------------------------------------------- item-sharded path
@@ -713,10 +718,9 @@ def test_fused_item_side_equals_the_two_pass_form_bit_for_bit(ctx, F, I, defer, 
 @pytest.mark.parametrize("chunk", [16, 64])
 @pytest.mark.parametrize("defer", [False, True])
 def test_fused_item_side_with_segments_cut_by_chunk_boundaries(ctx, chunk, defer, lib_option):
-    """Zipf catalogue, small chunks: the popular items' segments span many lane groups, whose partial rows meet in gGi / gBi through
-    atomics; the rows go on the step's split list and a second launch takes the Adam step from the accumulated gradient and clears it.  The order of those atomic
-    additions is the hardware's in both forms, so the comparison with the two-pass form is to fp32 re-association accuracy -- and
-    exact on every row whose segment lies inside one chunk; the accumulators come back zero, every row is stamped."""
+    """Zipf catalogue, small chunks: the popular items' segments span many lane groups, each of which leaves a partial row;
+    k_seg_combine / k_seg_combine_long add them in chunk order and take the Adam step on the row (fused form) or store the gradient
+    row (two-pass form), so the two forms agree bit for bit in every table; every row is stamped."""
     lib_option("ichunk", chunk)
     F, U, I, B = 128, 3000, 1200, 8192
     rs = np.random.RandomState(chunk)
@@ -736,7 +740,7 @@ def test_fused_item_side_with_segments_cut_by_chunk_boundaries(ctx, chunk, defer
     assert ops.deterministic_item_sums(ctx)
     for name in ("Gi", "mGi", "vGi", "Bi", "mBi", "vBi", "Gu", "mGu", "vGu"):
         x, y = getattr(a, name), getattr(b, name)
-        # the partial rows of a cut segment are added in chunk order by k_bpr_item_combine in BOTH forms: no atomics, the same bits
+        # the partial rows of a cut segment are added in chunk order by k_seg_combine in BOTH forms: no atomics, the same bits
         assert torch.equal(x.view(torch.int32), y.view(torch.int32)), (name, int((x != y).sum()), float((x - y).abs().max()))
     la, lb = a.pop_loss(), b.pop_loss()
     assert abs(la - lb) <= 1e-5 * abs(la)
@@ -746,7 +750,7 @@ def test_fused_item_side_with_segments_cut_by_chunk_boundaries(ctx, chunk, defer
 def test_sorted_step_is_deterministic_and_equals_the_oracle_on_a_zipf_catalogue(ctx, F, I):
     """Default chunking, a Zipf catalogue whose hottest items own thousands of the 2 B sorted positions (segments cut into dozens of
     partials, lists of hundreds of cut rows): two runs from the same tables on the same batches give the same bits in every table --
-    k_bpr_item_combine adds a cut segment's partials in chunk order -- in the fused + deferred form and in the two-pass form, the two
+    k_seg_combine adds a cut segment's partials in chunk order -- in the fused + deferred form and in the two-pass form, the two
     forms agree bit for bit with each other, and the result is the oracle's to fp32 re-association accuracy (F = 20: rows of 80 bytes on
     eight-lane groups; F = 256: 64-lane groups, four per combine workgroup)."""
     rs = np.random.RandomState(F)
