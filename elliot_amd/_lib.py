@@ -270,6 +270,16 @@ PROTOTYPES = {
     "el_als_solve": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, C.c_int64, _f64p, C.c_int64, C.c_int32, _f64p, C.c_double,
                                C.c_double, C.c_double, C.c_int, _i32p, _i64p, C.c_int64, C.c_int64, C.c_int64, _f64p, _i32p,
                                C.c_void_p, C.c_size_t]),
+    "el_ease_gram": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _i32p, _i64p, _i32p, _i32p, C.c_int64, C.c_int64, C.c_int32,
+                               C.c_int64, C.c_int32, C.c_double, _f64p, C.c_int64]),
+    "el_inv_f64_ws_bytes": (C.c_size_t, [C.c_int64]),
+    "el_inv_f64": (C.c_int, [C.c_void_p, C.c_void_p, _f64p, C.c_int64, C.c_int64, _i32p, _i32p, C.c_void_p, C.c_size_t]),
+    "el_lu_f64": (C.c_int, [C.c_void_p, C.c_void_p, _f64p, C.c_int64, C.c_int64, _i32p, _i32p]),
+    "el_topk_pad": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, _f32p, C.c_int64]),
+    "el_ease_weights_ws_bytes": (C.c_size_t, [C.c_int64]),
+    "el_ease_weights": (C.c_int, [C.c_void_p, C.c_void_p, _f64p, C.c_int64, C.c_int64, _f32p, C.c_int64, C.c_void_p, C.c_size_t]),
+    "el_csr_dense_scores": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _f32p, C.c_int64, C.c_int64, _f32p, C.c_int64,
+                                      C.c_int64, _f32p, C.c_int64]),
 }
 
 _lib = None

@@ -449,6 +449,179 @@ class AlsDeviceState:
 
 
 # ------------------------------------------------------------------------------------------
+# EASE^R (Gram, fp64 inverse, weights, CSR x dense scores)
+# ------------------------------------------------------------------------------------------
+EASE_SCORE_BLOCK_BYTES = 1 << 28     # bound of one [Ub, I] float32 score block
+
+
+def ease_integer_ratings(values):
+    """(scale, int32 values) as knn_integer_ratings; EASER refuses anything else with its own message."""
+    try:
+        return knn_integer_ratings(values)
+    except ValueError:
+        raise ValueError("EASER needs integer or half-step ratings (the Gram counts are exact integers); "
+                         "this train matrix holds other values") from None
+
+
+def ease_gram(ctx, R, l2_norm, out=None):
+    """ease_r.py:76-82: G = R^T R of a scipy [U, I] train matrix with the diagonal replaced by (float)(n_i + l2_norm), as an fp64
+    [I, I] device tensor (el_ease_gram: exact integer counts)."""
+    import scipy.sparse as sp
+    R = sp.csr_matrix(R)
+    R.sum_duplicates()
+    R.sort_indices()
+    Rt = R.T.tocsr()
+    Rt.sort_indices()
+    U, I = R.shape
+    scale, rv = ease_integer_ratings(R.data)
+    _, tv = ease_integer_ratings(Rt.data)
+    dev = ctx.device
+    Rc, Tc = DeviceCSR(R.indptr, R.indices, I, dev), DeviceCSR(Rt.indptr, Rt.indices, U, dev)
+    rvt = torch.from_numpy(rv if rv.size else np.zeros(1, np.int32)).to(dev)
+    tvt = torch.from_numpy(tv if tv.size else np.zeros(1, np.int32)).to(dev)
+    max_deg = int(np.diff(Rt.indptr).max()) if I else 0
+    max_abs = int(np.abs(rv).max()) if rv.size else 0
+    if out is None:
+        out = torch.empty((I, I), dtype=torch.float64, device=dev)
+    check(ctx.lib.el_ease_gram(ctx.handle, ctx.stream(), _ptr(Tc.indptr), _ptr(Tc.indices), _ptr(tvt), _ptr(Rc.indptr),
+                               _ptr(Rc.indices), _ptr(rvt), int(I), int(U), int(scale), max_deg, max_abs, float(l2_norm),
+                               _ptr(out, torch.float64, "G"), int(out.stride(0))), "el_ease_gram")
+    return out
+
+
+def inv_f64(ctx, A, ipiv=None, ws=None):
+    """A <- A^-1 in place (el_inv_f64: LU with partial pivoting, fp64 MFMA updates).  Returns ipiv (int32 [n], 0-based, getrf
+    order).  Raises numpy.linalg.LinAlgError naming the first column whose pivot is zero or NaN."""
+    n = int(A.shape[0])
+    if A.dim() != 2 or A.shape[1] != n:
+        raise ValueError("inv_f64: A must be square")
+    if ipiv is None:
+        ipiv = torch.empty(n, dtype=torch.int32, device=ctx.device)
+    status = torch.empty(1, dtype=torch.int32, device=ctx.device)
+    need = int(ctx.lib.el_inv_f64_ws_bytes(n))
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=ctx.device)
+    check(ctx.lib.el_inv_f64(ctx.handle, ctx.stream(), _ptr(A, torch.float64, "A"), int(A.stride(0)), n, _ptr(ipiv, torch.int32), _ptr(status, torch.int32),
+                             C.c_void_p(ws.data_ptr()), need), "el_inv_f64")
+    bad = int(status.item())
+    if bad != 0x7fffffff:
+        raise np.linalg.LinAlgError(f"Singular matrix: the pivot of column {bad} is zero or NaN")
+    return ipiv
+
+
+def lu_f64(ctx, A, ipiv=None):
+    """P A = L U in place (el_lu_f64, getrf): returns ipiv; raises LinAlgError as inv_f64."""
+    n = int(A.shape[0])
+    if A.dim() != 2 or A.shape[1] != n:
+        raise ValueError("lu_f64: A must be square")
+    if ipiv is None:
+        ipiv = torch.empty(n, dtype=torch.int32, device=ctx.device)
+    status = torch.empty(1, dtype=torch.int32, device=ctx.device)
+    check(ctx.lib.el_lu_f64(ctx.handle, ctx.stream(), _ptr(A, torch.float64, "A"), int(A.stride(0)), n, _ptr(ipiv, torch.int32),
+                            _ptr(status, torch.int32)), "el_lu_f64")
+    bad = int(status.item())
+    if bad != 0x7fffffff:
+        raise np.linalg.LinAlgError(f"Singular matrix: the pivot of column {bad} is zero or NaN")
+    return ipiv
+
+
+def ease_weights(ctx, P, out=None):
+    """ease_r.py:86-88: B = P / (-diag(P)) by columns with a zero diagonal, as float32 [I, I] (el_ease_weights)."""
+    I = int(P.shape[0])
+    if out is None:
+        out = torch.empty((I, I), dtype=torch.float32, device=ctx.device)
+    need = int(ctx.lib.el_ease_weights_ws_bytes(I))
+    ws = torch.empty(need, dtype=torch.uint8, device=ctx.device)
+    check(ctx.lib.el_ease_weights(ctx.handle, ctx.stream(), _ptr(P, torch.float64, "P"), int(P.stride(0)), I,
+                                  _ptr(out, torch.float32, "B"), int(out.stride(0)), C.c_void_p(ws.data_ptr()), need), "el_ease_weights")
+    return out
+
+
+def csr_dense_scores(ctx, R, R_vals, B, u_start, u_stop, out=None):
+    """self._train.dot(B) (ease_r.py:93) for users [u_start, u_stop) in scipy's order: float32 [n, I] (el_csr_dense_scores)."""
+    n, I = int(u_stop) - int(u_start), int(B.shape[1])
+    if out is None:
+        out = torch.empty((n, I), dtype=torch.float32, device=ctx.device)
+    if out.shape[0] < n or out.shape[1] != I:
+        raise ValueError("csr_dense_scores: the output block is smaller than [n, I]")
+    check(ctx.lib.el_csr_dense_scores(ctx.handle, ctx.stream(), _ptr(R.indptr, torch.int64), _ptr(R.indices, torch.int32),
+                                      _ptr(R_vals, torch.float32), int(u_start), int(u_stop),
+                                      _ptr(B, torch.float32, "B"), int(B.stride(0)), I, _ptr(out, torch.float32, "S"),
+                                      int(out.stride(0))), "el_csr_dense_scores")
+    return out
+
+
+def ease_memory_need(I, U):
+    """Device bytes EaseDeviceState needs at its peak: G / P and the inverse's right-hand sides (8 I^2 each), B (4 I^2), one
+    score block and the CSRs."""
+    I, U = int(I), int(U)
+    block = min(max(EASE_SCORE_BLOCK_BYTES // (4 * max(I, 1)), 1), max(U, 1)) * 4 * I
+    return 8 * I * I + 8 * I * I + 4 * I * I + block
+
+
+class EaseDeviceState:
+    """R (float32 CSR, stored order) and B (float32 [I, I]) of EASE^R in HBM.
+
+    build() forms G (el_ease_gram), P = G^-1 (el_inv_f64), B (el_ease_weights) and frees G / P; recommend() scores blocks of at
+    most EASE_SCORE_BLOCK_BYTES with el_csr_dense_scores and selects with el_dense_topk; lists short of k are padded with
+    (-1, -inf) (el_topk_pad).  The device memory is checked before anything is allocated."""
+
+    def __init__(self, ctx, R, l2_norm):
+        import scipy.sparse as sp
+        self.ctx = ctx
+        R = sp.csr_matrix(R, dtype=np.float32)
+        self.U, self.I = int(R.shape[0]), int(R.shape[1])
+        self.l2_norm = float(l2_norm)
+        self.need = ease_memory_need(self.I, self.U)
+        free, _total = torch.cuda.mem_get_info(ctx.device)
+        if self.need > free:
+            raise ValueError(f"EASER: {self.I} items need {self.need} bytes of device memory (G / P and the inverse's right-hand "
+                             f"sides 2 x {8 * self.I * self.I}, B {4 * self.I * self.I}, one score block); {free} bytes are free")
+        ease_integer_ratings(R.data)
+        self._host = R
+        self.R = DeviceCSR(R.indptr, R.indices, self.I, ctx.device)
+        self.R_vals = device_values(R.data, ctx.device)
+        self.B = None
+        self.block_rows = min(max(EASE_SCORE_BLOCK_BYTES // (4 * max(self.I, 1)), 1), max(self.U, 1))
+        self._S = None
+
+    def build(self):
+        G = ease_gram(self.ctx, self._host, self.l2_norm)
+        inv_f64(self.ctx, G)
+        self.B = ease_weights(self.ctx, G)
+        del G
+        torch.cuda.empty_cache()
+        return self.B
+
+    def set_weights(self, B):
+        B = np.ascontiguousarray(B, dtype=np.float32)
+        if B.shape != (self.I, self.I):
+            raise ValueError(f"EASER weights have shape {B.shape}, the model expects {(self.I, self.I)}")
+        self.B = torch.from_numpy(B).to(self.ctx.device)
+
+    def recommend(self, mask, k, start, stop):
+        """Top-k of users [start, stop) under the tagged mask ("excl" | "cand", DeviceCSR): (idx, val) [n, k] on the device."""
+        kind, csr = mask if mask is not None else (None, None)
+        ep, ei = _csr_ptrs(csr if kind == "excl" else None)
+        cp, ci = _csr_ptrs(csr if kind == "cand" else None)
+        n = int(stop) - int(start)
+        out_idx = torch.empty((n, k), dtype=torch.int32, device=self.ctx.device)
+        out_val = torch.empty((n, k), dtype=torch.float32, device=self.ctx.device)
+        if self._S is None:
+            self._S = torch.empty((self.block_rows, self.I), dtype=torch.float32, device=self.ctx.device)
+        for s in range(int(start), int(stop), self.block_rows):
+            e = min(s + self.block_rows, int(stop))
+            csr_dense_scores(self.ctx, self.R, self.R_vals, self.B, s, e, out=self._S)
+            r = s - int(start)
+            check(self.ctx.lib.el_dense_topk(self.ctx.handle, self.ctx.stream(), C.c_void_p(self._S.data_ptr()), int(self.I), s, e,
+                                             int(self.I), ep, ei, cp, ci, int(k), C.c_void_p(out_idx[r].data_ptr()),
+                                             C.c_void_p(out_val[r].data_ptr())), "el_dense_topk")
+        check(self.ctx.lib.el_topk_pad(self.ctx.handle, self.ctx.stream(), _ptr(out_idx, torch.int32), _ptr(out_val, torch.float32),
+                                       int(n * k)), "el_topk_pad")
+        return out_idx, out_val
+
+
+# ------------------------------------------------------------------------------------------
 # accuracy metrics on the device (SURVEY 8f, N1)
 # ------------------------------------------------------------------------------------------
 METRIC_NAMES = ("nDCG", "Precision", "Recall", "HR", "MAP", "MRR", "F1")

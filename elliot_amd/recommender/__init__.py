@@ -20,7 +20,8 @@ from .knn.item_knn.item_knn import ItemKNN
 from .knn.user_knn.user_knn import UserKNN
 from .latent_factor_models.iALS.iALS import iALS
 from .latent_factor_models.WRMF.wrmf import WRMF
+from .autoencoders.EASE_R.ease_r import EASER
 
 __all__ = ["BaseRecommenderModel", "init_charger", "RecMixin", "BPRMF_batch", "BPRMF", "MultiVAE", "MultiDAE", "NeuMF", "GMF",
            "MF", "PMF", "FunkSVD", "LogisticMatrixFactorization", "LMF", "CML", "MF2020", "LightGCN", "NGCF", "ProxyRecommender",
-           "ItemKNN", "UserKNN", "iALS", "WRMF"]
+           "ItemKNN", "UserKNN", "iALS", "WRMF", "EASER"]

@@ -522,6 +522,54 @@ int el_als_solve(el_ctx* ctx, void* stream, const int64_t* indptr, const int32_t
                  int flags, const int32_t* long_rows, const int64_t* long_first, int64_t n_long, int64_t n_pieces,
                  int64_t piece_len, double* X, int32_t* status, void* ws, size_t ws_bytes);
 
+/* ---- EASE^R: Gram, dense fp64 inverse, weights, CSR x dense scores ------------------------------------------------ */
+
+/* Replaces safe_sparse_dot(R.T, R, dense_output=True) and the diagonal assignment of EASER.train (ease_r.py:76-82):
+ *   G[c, x] = sum_u R[u,c] R[u,x] (c != x) from INTEGER values (ratings times scale, 1: integers, 2: half steps), counted
+ *   exactly in LDS (int32 when max_deg * max_abs^2 fits, int64 otherwise) and divided by scale^2;
+ *   G[c, c] = (double)(float)(n_c + l2_norm), n_c = the stored entries of column c.
+ *   T = R^T (item -> users) and R (user -> items, rows ascending); max_deg = longest row of T, max_abs = max |value|.
+ *   G fp64 [I, I], leading dimension ldg.  Exact integers give a symmetric G bit for bit; it equals the reference's float32
+ *   G bit for bit while every sum stays below 2^24.                                                                        */
+int el_ease_gram(el_ctx* ctx, void* stream,
+                 const int64_t* t_indptr, const int32_t* t_indices, const int32_t* t_vals,
+                 const int64_t* r_indptr, const int32_t* r_indices, const int32_t* r_vals,
+                 int64_t I, int64_t U, int32_t scale, int64_t max_deg, int32_t max_abs, double l2_norm,
+                 double* G, int64_t ldg);
+
+/* Replaces np.linalg.inv (ease_r.py:84; LAPACK getrf + getri there) for any n x n fp64 matrix: A <- A^-1 in place (lda >= n)
+ * by LU with partial pivoting -- the largest |a| of the column, ties to the smallest row as idamax, NaN ranks first -- followed
+ * by the triangular solves L U X = P I.  The LU runs on [A | I]; ws = el_inv_f64_ws_bytes(n) bytes hold the right-hand sides.
+ * The O(n^3) updates run on v_mfma_f64_16x16x4_f64; each column's pivot search is its own launch (about 2 n + 6 n / 64
+ * launches).  The same input gives the same bits on every run.
+ * ipiv int32[n] (0-based, LAPACK's getrf order); status int32[1] on the device: the smallest column whose pivot is zero or
+ * NaN, 0x7fffffff = none; A and ipiv are undefined when it is set.                                                         */
+size_t el_inv_f64_ws_bytes(int64_t n);
+int el_inv_f64(el_ctx* ctx, void* stream, double* A, int64_t lda, int64_t n, int32_t* ipiv, int32_t* status,
+               void* ws, size_t ws_bytes);
+/* The factorisation alone (getrf): P A = L U in place (unit L below the diagonal, U on and above it), ipiv and status as
+ * el_inv_f64; the same kernels and the same bits as el_inv_f64's LU.                                                        */
+int el_lu_f64(el_ctx* ctx, void* stream, double* A, int64_t lda, int64_t n, int32_t* ipiv, int32_t* status);
+
+/* Replaces P / (-np.diag(P)) and the zeroed diagonal (ease_r.py:86-88): B[j, i] = (float)(-P[j, i] / P[i, i]), a correctly
+ * rounded fp64 division rounded once to float; B[i, i] = 0.  P fp64 [I, I] (ldp), B float [I, I] (ldb);
+ * ws = el_ease_weights_ws_bytes(I) bytes.                                                                                   */
+size_t el_ease_weights_ws_bytes(int64_t I);
+int el_ease_weights(el_ctx* ctx, void* stream, const double* P, int64_t ldp, int64_t I, float* B, int64_t ldb,
+                    void* ws, size_t ws_bytes);
+
+/* Replaces self._train.dot(B) (ease_r.py:93) for users [u_start, u_stop):
+ *   S[u - u_start, :] = sum over the entries a of row u IN STORED ORDER of R[u,a] * B[a, :], from +0, separate
+ *   round-to-nearest multiply and add (scipy csr_matvecs): given the same B, the reference's _preds bit for bit.
+ *   R rows indexed by absolute user id; B float [n_B, I] (ldb); S float [(u_stop-u_start), I] (lds).  Select with
+ *   el_dense_topk.                                                                                                          */
+int el_csr_dense_scores(el_ctx* ctx, void* stream, const int64_t* indptr, const int32_t* indices, const float* vals,
+                        int64_t u_start, int64_t u_stop, const float* B, int64_t ldb, int64_t I, float* S, int64_t lds);
+
+/* el_dense_topk fills a list short of k with masked items at -inf (the reference's get_top_k); this turns every entry whose
+ * value is -inf into (-1, -inf), the padding of the KNN and ALS lists.  idx int32[n], val float[n].                        */
+int el_topk_pad(el_ctx* ctx, void* stream, int32_t* idx, const float* val, int64_t n);
+
 /* ---- dense layers: fp32 MFMA GEMM with fused bias + activation (K9, K12) ----------------- */
 
 /* Replaces: keras.layers.Dense forward/backward products of the neural latent-factor models
