@@ -264,6 +264,12 @@ PROTOTYPES = {
                                C.c_int, C.c_int32, C.c_int64, C.c_int32, _i64p, _i32p, _f32p, C.c_void_p, C.c_size_t]),
     "el_knn_score_topk": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _f32p, _i64p, _i32p, _f32p, C.c_int64, C.c_int64,
                                     C.c_int64, _i64p, _i32p, _i64p, _i32p, C.c_int32, _i32p, _f32p]),
+    "el_csr_row_l1": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _f32p, C.c_int64, _f32p]),
+    "el_rp3_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int64]),
+    "el_rp3_rows": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _f32p, _i64p, _i32p, _f32p, _f64p, C.c_int64, C.c_int64,
+                              C.c_int32, C.c_int64, C.c_int64, _i32p, _f32p, _i32p, C.c_void_p, C.c_size_t]),
+    "el_rp3_cut": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, _f32p, _i32p, C.c_int64, C.c_int32, C.c_int, _i64p, _i32p, _f32p,
+                             C.c_void_p, C.c_size_t]),
     "el_als_gram_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "el_als_gram": (C.c_int, [C.c_void_p, C.c_void_p, _f64p, C.c_int64, C.c_int32, _f64p, C.c_void_p, C.c_size_t]),
     "el_als_solve_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),

@@ -318,6 +318,115 @@ def knn_score_topk(ctx, A, A_vals, B, B_vals, u_start, u_stop, k, excl=None, can
 
 
 # ------------------------------------------------------------------------------------------
+# RP3beta (graph_based/RP3beta; beta = 0 is P3alpha)
+# ------------------------------------------------------------------------------------------
+RP3_ROWS_WS_BYTES = 1 << 28          # bound of el_rp3_rows' workspace: longer row ranges are built in pieces
+
+
+def csr_row_l1(ctx, indptr, vals, n_rows=None):
+    """sklearn's normalize(., 'l1') on the values of a device CSR (el_csr_row_l1): fp64 sequential row sums in stored order,
+    out of place.  indptr int64 / vals float32 device tensors; returns the float32 values."""
+    n = int(indptr.shape[0] - 1 if n_rows is None else n_rows)
+    out = torch.empty_like(vals)
+    if vals.shape[0] and n:
+        check(ctx.lib.el_csr_row_l1(ctx.handle, ctx.stream(), _ptr(indptr, torch.int64, "indptr"), _ptr(vals, torch.float32, "vals"),
+                                    n, _ptr(out, torch.float32, "out")), "el_csr_row_l1")
+    return out
+
+
+def _rp3_power(ctx, vals, alpha):
+    """np.power on float32, on the host, exactly as the reference writes it (a device powf differs in the last bit)."""
+    return torch.from_numpy(np.power(vals.cpu().numpy(), alpha)).to(ctx.device)
+
+
+def rp3_operands(ctx, R, alpha, beta):
+    """rp3beta.py:77-96: (Piu DeviceCSR [I, U], its values, Pui DeviceCSR [U, I], its values, degree fp64 [I]) on the device from a
+    scipy [U, I] ratings matrix with any float values.  The row sums run over R's stored order; both CSRs come out with ascending
+    columns.  The two powers (degree, alpha) are NumPy's, on float32 arrays on the host."""
+    import scipy.sparse as sp
+    alpha, beta = float(alpha), float(beta)                          # Python floats: a NumPy float64 scalar would promote the powers
+    R = sp.csr_matrix(R, dtype=np.float32)
+    U, I = R.shape
+    dev = ctx.device
+    pui_vals = csr_row_l1(ctx, torch.from_numpy(R.indptr.astype(np.int64)).to(dev), device_values(R.data, dev), U)
+    indices = R.indices
+    if not R.has_sorted_indices:                                     # the sums are taken; the order inside a row is free now
+        rows = np.repeat(np.arange(U), np.diff(R.indptr))
+        perm = np.lexsort((R.indices, rows))
+        indices = R.indices[perm]
+        pui_vals = pui_vals[torch.from_numpy(perm).to(dev)].contiguous()
+    Pui = DeviceCSR(R.indptr, indices, I, dev)
+    X = sp.csr_matrix((np.ones(R.nnz, np.float32), indices, R.indptr), shape=(U, I)).T.tocsr()
+    X.sort_indices()
+    Piu = DeviceCSR(X.indptr, X.indices, U, dev)
+    piu_vals = csr_row_l1(ctx, Piu.indptr, device_values(X.data, dev), I)
+    cnt = np.diff(X.indptr).astype(np.float32)                       # X_bool.sum(axis=1) of a float32 matrix
+    degree = np.zeros(I)
+    nz = cnt != 0.0
+    degree[nz] = np.power(cnt[nz], -beta)
+    if alpha != 1.:
+        pui_vals, piu_vals = _rp3_power(ctx, pui_vals, alpha), _rp3_power(ctx, piu_vals, alpha)
+    return Piu, piu_vals, Pui, pui_vals, torch.from_numpy(degree).to(dev)
+
+
+def _rp3_n(n_neighbors, I):
+    return int(I) if int(n_neighbors) == -1 else int(n_neighbors)
+
+
+def rp3_rows(ctx, Piu, piu_vals, Pui, pui_vals, degree, n_neighbors, i_start=0, i_stop=None):
+    """rp3beta.py:111-141 for the rows [i_start, i_stop) (el_rp3_rows): (idx int32 [n, N], val float32 [n, N], cnt int32 [n]) on the
+    device, N = min(n_neighbors, I), every row's kept (column, value) pairs in rank order."""
+    I, U = Piu.n_rows, Pui.n_rows
+    n_neighbors = _rp3_n(n_neighbors, I)
+    if n_neighbors < 1:
+        raise ValueError("neighborhood must be >= 1 (or -1: every item)")
+    i_stop = I if i_stop is None else int(i_stop)
+    n, N = i_stop - int(i_start), min(n_neighbors, I)
+    idx = torch.empty((max(n, 1), N), dtype=torch.int32, device=ctx.device)
+    val = torch.empty((max(n, 1), N), dtype=torch.float32, device=ctx.device)
+    cnt = torch.empty(max(n, 1), dtype=torch.int32, device=ctx.device)
+    per_row = max(int(ctx.lib.el_rp3_ws_bytes(I, n_neighbors, 1)), 1)
+    block = max(min(RP3_ROWS_WS_BYTES // per_row, n), 1)
+    need = int(ctx.lib.el_rp3_ws_bytes(I, n_neighbors, block))
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=ctx.device)
+    for r0 in range(0, n, block):
+        r1 = min(r0 + block, n)
+        check(ctx.lib.el_rp3_rows(ctx.handle, ctx.stream(), _ptr(Piu.indptr, torch.int64), _ptr(Piu.indices, torch.int32),
+                                  _ptr(piu_vals, torch.float32), _ptr(Pui.indptr, torch.int64), _ptr(Pui.indices, torch.int32),
+                                  _ptr(pui_vals, torch.float32), _ptr(degree, torch.float64, "degree"), I, U, n_neighbors,
+                                  int(i_start) + r0, int(i_start) + r1, _ptr(idx[r0:], torch.int32), _ptr(val[r0:], torch.float32),
+                                  _ptr(cnt[r0:], torch.int32), C.c_void_p(ws.data_ptr()), need), "el_rp3_rows")
+    return idx[:n], val[:n], cnt[:n]
+
+
+def rp3_cut(ctx, idx, val, cnt, n_neighbors, normalize):
+    """rp3beta.py:143-174 on the row lists of all I rows (el_rp3_cut): (DeviceCSR W [I, I] columns ascending, float32 values), the
+    shape knn_build returns."""
+    I = int(cnt.shape[0])
+    n_neighbors = _rp3_n(n_neighbors, I)
+    N = min(n_neighbors, I)
+    if idx.shape != (I, N) or val.shape != (I, N):
+        raise ValueError(f"row lists must be [{I}, {N}], got {tuple(idx.shape)}")
+    need = int(ctx.lib.el_rp3_ws_bytes(I, n_neighbors, 0))
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=ctx.device)
+    w_indptr = torch.empty(I + 1, dtype=torch.int64, device=ctx.device)
+    w_indices = torch.empty(max(I * N, 1), dtype=torch.int32, device=ctx.device)
+    w_vals = torch.empty(max(I * N, 1), dtype=torch.float32, device=ctx.device)
+    check(ctx.lib.el_rp3_cut(ctx.handle, ctx.stream(), _ptr(idx, torch.int32), _ptr(val, torch.float32), _ptr(cnt, torch.int32), I,
+                             n_neighbors, 1 if normalize else 0, _ptr(w_indptr), _ptr(w_indices), _ptr(w_vals),
+                             C.c_void_p(ws.data_ptr()), need), "el_rp3_cut")
+    nnz = int(w_indptr[-1].item())
+    W = DeviceCSR.from_tensors(w_indptr, w_indices[:nnz], I)
+    return W, (w_vals[:nnz] if nnz else w_vals[:1])
+
+
+def rp3_build(ctx, Piu, piu_vals, Pui, pui_vals, degree, n_neighbors, normalize):
+    """W of RP3beta from finished operands (rp3_operands): rp3_rows + rp3_cut.  knn_score_topk(A = R, B = W) takes it directly."""
+    idx, val, cnt = rp3_rows(ctx, Piu, piu_vals, Pui, pui_vals, degree, n_neighbors)
+    return rp3_cut(ctx, idx, val, cnt, n_neighbors, normalize)
+
+
+# ------------------------------------------------------------------------------------------
 # alternating least squares (iALS / WRMF)
 # ------------------------------------------------------------------------------------------
 ALS_PIECE_LEN = 8192          # rows longer than this are summed in pieces (el_als_solve's long-row plan)

@@ -11,6 +11,7 @@ from .latent_factor_models.CML.CML import CML
 from .latent_factor_models.MF2020.MF import MF2020
 from .graph_based.lightgcn.LightGCN import LightGCN
 from .graph_based.ngcf.NGCF import NGCF
+from .graph_based.RP3beta.rp3beta import RP3beta
 from .generic.Proxy.Proxy import ProxyRecommender
 from .autoencoders.vae.multi_vae import MultiVAE
 from .autoencoders.dae.multi_dae import MultiDAE
@@ -24,4 +25,4 @@ from .autoencoders.EASE_R.ease_r import EASER
 
 __all__ = ["BaseRecommenderModel", "init_charger", "RecMixin", "BPRMF_batch", "BPRMF", "MultiVAE", "MultiDAE", "NeuMF", "GMF",
            "MF", "PMF", "FunkSVD", "LogisticMatrixFactorization", "LMF", "CML", "MF2020", "LightGCN", "NGCF", "ProxyRecommender",
-           "ItemKNN", "UserKNN", "iALS", "WRMF", "EASER"]
+           "ItemKNN", "UserKNN", "iALS", "WRMF", "EASER", "RP3beta"]

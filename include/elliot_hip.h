@@ -492,6 +492,44 @@ int el_knn_score_topk(el_ctx* ctx, void* stream,
                       const int64_t* cand_indptr, const int32_t* cand_indices,
                       int32_t k, int32_t* out_idx, float* out_val);
 
+/* ---- RP3beta (graph_based/RP3beta; beta = 0 is P3alpha) ------------------------------------------------------------- */
+
+/* Replaces sklearn's normalize(X, norm='l1', axis=1) on a CSR (rp3beta.py:78 Pui, :91 Piu, :147 normalize_similarity):
+ *   per row s = sum |x| accumulated sequentially in fp64 in stored order (sklearn keeps the sum in a C double), rows with
+ *   s == 0 are copied, every other entry becomes (float)((double)x / s).  Out of place: out float[nnz], out != vals.
+ *   Any float values: nothing here relies on integer ratings.                                                          */
+int el_csr_row_l1(el_ctx* ctx, void* stream, const int64_t* indptr, const float* vals, int64_t n_rows, float* out);
+
+/* Bytes of workspace: n_rows > 0 for el_rp3_rows over n_rows rows in one call, n_rows == 0 for el_rp3_cut.              */
+size_t el_rp3_ws_bytes(int64_t I, int32_t n_neighbors, int64_t n_rows);
+
+/* Replaces the block loop of RP3beta.train (rp3beta.py:111-141) for the rows [i_start, i_stop) of the item-item matrix:
+ *   S[i, j] = sum over the users u of Piu row i IN ASCENDING ORDER of Piu[i,u] * Pui[u,j], float32, every product and every
+ *   sum rounded to nearest, from +0 (scipy csr_matmat, :116);  v = (double)S[i,j] * degree[j], v[i] = 0 (:120-121);
+ *   the N = min(n_neighbors, I) largest of the whole row by (v desc, j asc) with the zeros dropped (:123-128; the
+ *   reference's argsort breaks ties as its introsort happens to), stored as (float)v.  The comparison is on the fp64 value.
+ *   Piu [I, U] and Pui [U, I] are CSRs with ascending columns and their values AS GIVEN (normalised, raised to alpha by
+ *   the caller); degree double[I].  The library takes no power.
+ * Output: list_idx int32 / list_val float [(i_stop-i_start), N] in rank order, list_cnt int32[(i_stop-i_start)].
+ * N <= 2048 (so n_neighbors >= I, the reference's neighborhood -1, needs I <= 2048).  Nothing I x I is written;
+ * ws = el_rp3_ws_bytes(I, n_neighbors, i_stop - i_start) bytes.  The same input gives the same bytes.                   */
+int el_rp3_rows(el_ctx* ctx, void* stream,
+                const int64_t* piu_indptr, const int32_t* piu_indices, const float* piu_vals,
+                const int64_t* pui_indptr, const int32_t* pui_indices, const float* pui_vals,
+                const double* degree, int64_t I, int64_t U, int32_t n_neighbors,
+                int64_t i_start, int64_t i_stop,
+                int32_t* list_idx, float* list_val, int32_t* list_cnt, void* ws, size_t ws_bytes);
+
+/* Replaces the rest of RP3beta.train (rp3beta.py:143-174) on the row lists of ALL I rows (el_rp3_rows' layout):
+ *   normalize != 0: the row-l1 of el_csr_row_l1 over each row's kept entries in ascending column order (:146-147);
+ *   per column j the entries != 0, the N largest by (float value desc, row asc) (:153-169);
+ *   W = those entries as CSR [I, I], columns ascending (:173-174): w_indptr int64[I+1], w_indices int32 / w_vals float with
+ *   room for I * min(n_neighbors, I) entries (the nnz is w_indptr[I]).  ws = el_rp3_ws_bytes(I, n_neighbors, 0) bytes.
+ * The scores and lists of the model (:176, :56-71) are el_knn_score_topk(A = R, B = W).                                 */
+int el_rp3_cut(el_ctx* ctx, void* stream, const int32_t* list_idx, const float* list_val, const int32_t* list_cnt,
+               int64_t I, int32_t n_neighbors, int normalize,
+               int64_t* w_indptr, int32_t* w_indices, float* w_vals, void* ws, size_t ws_bytes);
+
 /* ---- alternating least squares: iALS / WRMF ------------------------------------------------------------------------ */
 
 #define EL_ALS_SKIP_EMPTY 1     /* el_als_solve: rows without entries keep their X row (iALS item half, warm items only) */

@@ -1,0 +1,183 @@
+"""NumPy / scipy restatement of the RP3beta contract (elliot_amd/csrc/el_rp3.hip, include/elliot_hip.h).
+
+  Pui      = row-l1 of R as sklearn's normalize(., 'l1') computes it: s = sum |x| sequentially in fp64 in stored order,
+             float32(fp64(x) / s), rows with s == 0 left alone
+  Piu      = the same on the boolean transpose (rows = items, users ascending)
+  degree   = float64(float32(n_j) ** -beta) (np.power on a float32 array), 0 for empty columns
+  alpha    = float32 np.power on both operands' data when alpha != 1
+  S[i, j]  = scipy's own float32 csr_matmat of Piu and Pui (products added in ascending-u order from +0)
+  row cut  = v = float64(S[i, j]) * degree[j], v[i] = 0; the N largest of the WHOLE row by (v desc, j asc), zeros dropped,
+             stored as float32(v)
+  normalize_similarity = row-l1 over each row's kept entries in ascending column order
+  col cut  = per column the N largest non-zero float32 values by (value desc, row asc)
+  W        = those entries as CSR [I, I], columns ascending
+  scores   = knn_ref.scores(R, W, "item"), lists = knn_ref.topk
+
+The row stage works on a subset of rows, so large shapes stay cheap on the CPU.
+"""
+import numpy as np
+import scipy.sparse as sp
+
+
+def row_l1(indptr, data):
+    """Row-l1 of CSR values: one sequential fp64 sum of |x| per row, fp64 division rounded once to float32 (sklearn's
+    inplace_csr_row_normalize_l1 keeps its sum in a C double); out of place."""
+    data = np.ascontiguousarray(data, np.float32)
+    out = data.copy()
+    for r in range(len(indptr) - 1):
+        lo, hi = indptr[r], indptr[r + 1]
+        if hi == lo:
+            continue
+        x = data[lo:hi].astype(np.float64)
+        s = np.add.accumulate(np.abs(x))[-1]                                    # accumulate is strictly sequential
+        if s != 0:
+            out[lo:hi] = (x / s).astype(np.float32)
+    return out
+
+
+def operands(R, alpha, beta):
+    """(Piu csr [I, U], Pui csr [U, I], degree float64 [I]) of a scipy [U, I] ratings matrix, stored order of R kept."""
+    alpha, beta = float(alpha), float(beta)                     # Python floats: a NumPy float64 scalar would promote the powers
+    R = sp.csr_matrix(R, dtype=np.float32)
+    Pui = sp.csr_matrix((row_l1(R.indptr, R.data), R.indices.copy(), R.indptr.copy()), shape=R.shape)
+    X = R.transpose(copy=True).tocsr()
+    X.sort_indices()
+    X.data = np.ones(X.data.size, np.float32)
+    cnt = np.diff(X.indptr).astype(np.float32)
+    degree = np.zeros(R.shape[1])
+    nz = cnt != 0
+    degree[nz] = np.power(cnt[nz], -beta)
+    Piu = sp.csr_matrix((row_l1(X.indptr, X.data), X.indices, X.indptr), shape=X.shape)
+    if alpha != 1.:
+        Pui.data = np.power(Pui.data, alpha)
+        Piu.data = np.power(Piu.data, alpha)
+    return Piu, Pui, degree
+
+
+def _rank_row(v, i, N):
+    """Rule 3 on one fp64 row (v[i] already 0): indices of the kept entries in rank order, and whether the cut is tied."""
+    I = v.shape[0]
+    nz = np.flatnonzero(v != 0)
+    order = nz[np.lexsort((nz, -v[nz]))]                         # positives first, then negatives; zeros sit between them
+    P = int((v[order] > 0).sum())
+    Z = I - order.shape[0]
+    n_neg = max(0, N - P - Z) if P < N else 0
+    keep = np.concatenate([order[:min(N, P)], order[P:P + n_neg]])
+    tied = False
+    if N < I:
+        if P > N:
+            tied = v[order[N - 1]] == v[order[N]]
+        elif P + Z < N < I and P + n_neg < order.shape[0]:
+            tied = v[order[P + n_neg - 1]] == v[order[P + n_neg]]
+    return keep, bool(tied)
+
+
+def row_lists(Piu, Pui, degree, rows, N, block=256):
+    """Rules 2 + 3 for the given rows: (lists, tied) with lists = [(j int32 in rank order, float32 values)]."""
+    I = Pui.shape[1]
+    N = min(int(N), I)
+    rows = np.asarray(rows, np.int64)
+    out, tied = [], 0
+    for b0 in range(0, rows.shape[0], block):
+        rb = rows[b0:b0 + block]
+        S = (Piu[rb] * Pui).toarray()
+        assert S.dtype == np.float32
+        for r, i in enumerate(rb):
+            v = S[r].astype(np.float64) * degree
+            v[i] = 0
+            keep, t = _rank_row(v, i, N)
+            tied += t
+            out.append((keep.astype(np.int32), v[keep].astype(np.float32)))
+    return out, tied
+
+
+def pack_lists(lists, N):
+    """[(j, v)] -> (idx int32 [n, N], val float32 [n, N], cnt int32 [n]), the layout el_rp3_rows writes."""
+    n = len(lists)
+    idx = np.zeros((n, max(N, 1)), np.int32)
+    val = np.zeros((n, max(N, 1)), np.float32)
+    cnt = np.zeros(n, np.int32)
+    for r, (j, v) in enumerate(lists):
+        cnt[r] = len(j)
+        idx[r, :len(j)] = j
+        val[r, :len(j)] = v
+    return idx, val, cnt
+
+
+def cut(idx, val, cnt, I, N, normalize):
+    """Rules 4 + 5 on full row lists (pack_lists layout, one row per item): (W csr float32, tied column cuts)."""
+    N = min(int(N), I)
+    rows = np.repeat(np.arange(I, dtype=np.int64), cnt)
+    take = np.arange(idx.shape[1])[None, :] < cnt[:, None]
+    cols, vals = idx[take].astype(np.int64), val[take].astype(np.float32)
+    o = np.lexsort((cols, rows))                                 # COO -> CSR: columns ascending inside every row
+    rows, cols, vals = rows[o], cols[o], vals[o]
+    if normalize:
+        indptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=I))])
+        vals = row_l1(indptr, vals)
+    keep = vals != 0
+    rows, cols, vals = rows[keep], cols[keep], vals[keep]
+    o = np.lexsort((rows, -vals.astype(np.float64), cols))       # per column: value desc, row asc
+    rows, cols, vals = rows[o], cols[o], vals[o]
+    start = np.concatenate([[0], np.cumsum(np.bincount(cols, minlength=I))])
+    rank = np.arange(cols.shape[0]) - start[cols]
+    tied = 0
+    for j in np.flatnonzero(np.diff(start) > N):
+        tied += vals[start[j] + N - 1] == vals[start[j] + N]
+    sel = rank < N
+    W = sp.csr_matrix((vals[sel], (rows[sel], cols[sel])), shape=(I, I), dtype=np.float32)
+    W.sort_indices()
+    return W, int(tied)
+
+
+def build_w(Piu, Pui, degree, N, normalize):
+    """W of finished operands: (W csr float32 columns ascending, tied row cuts, tied column cuts)."""
+    I = Pui.shape[1]
+    N = I if N == -1 else int(N)
+    lists, row_ties = row_lists(Piu, Pui, degree, np.arange(I), N)
+    W, col_ties = cut(*pack_lists(lists, min(N, I)), I, N, normalize)
+    return W, row_ties, col_ties
+
+
+def build(R, N, alpha, beta, normalize):
+    Piu, Pui, degree = operands(R, alpha, beta)
+    return build_w(Piu, Pui, degree, N, normalize)[0]
+
+
+# ---- tests/golden/rp3beta_ref.npz (scripts/gen_golden_rp3beta.py) -----------------------------------------------------------
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def load_golden(golden):
+    z = golden("rp3beta_ref.npz")
+    R = sp.csr_matrix((z["R_data"], z["R_indices"], z["R_indptr"]), shape=tuple(z["shape"]))
+    return z, R
+
+
+def golden_cases(golden):
+    """[(tag, neighborhood, alpha, beta, normalize_similarity)] of tests/golden/rp3beta_ref.npz."""
+    z, _ = load_golden(golden)
+    return [(str(t), int(p[0]), float(p[1]), float(p[2]), bool(p[3])) for t, p in zip(z["cases"], z["tag_params"])]
+
+
+def case_matrix(R, tag):
+    R = R.copy()
+    if tag.startswith("bin"):
+        R.data[:] = 1.0
+    return R
+
+
+def golden_operands(z, R, tag):
+    f = tag.split("_")
+    ops = f"{f[0]}_{f[2]}"
+    U, I = R.shape
+    Pui = sp.csr_matrix((z[f"{ops}_pui_data"], R.indices, R.indptr), shape=(U, I))
+    Piu = sp.csr_matrix((z[f"{ops}_piu_data"], z["piu_indices"], z["piu_indptr"]), shape=(I, U))
+    return Piu, Pui, z[f"{tag}_degree"]
+
+
+def reference_w(z, tag, I):
+    W = sp.csc_matrix((z[f"{tag}_w_data"], z[f"{tag}_w_indices"], z[f"{tag}_w_indptr"]), shape=(I, I), dtype=np.float32).tocsr()
+    W.sort_indices()
+    return W
