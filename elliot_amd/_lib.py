@@ -22,6 +22,8 @@ EL_BPR_ATOMIC = 1
 EL_BPR_SORTED = 2
 EL_KNN_COSINE = 0
 EL_KNN_DOT = 1
+EL_SLIM_COLUMN = 0
+EL_SLIM_REFERENCE = 1
 EL_ALS_SKIP_EMPTY = 1
 EL_ALS_MAX_F = 128
 
@@ -270,6 +272,13 @@ PROTOTYPES = {
                               C.c_int32, C.c_int64, C.c_int64, _i32p, _f32p, _i32p, C.c_void_p, C.c_size_t]),
     "el_rp3_cut": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, _f32p, _i32p, C.c_int64, C.c_int32, C.c_int, _i64p, _i32p, _f32p,
                              C.c_void_p, C.c_size_t]),
+    "el_slim_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int64, C.c_int64, _i32p]),
+    "el_slim_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
+    "el_slim_fit": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _f32p, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_int32,
+                              C.c_float, _i32p, C.c_int, C.c_int64, C.c_int64, C.c_int32, _i32p, _f32p, _i32p, _i32p, _f32p,
+                              C.c_void_p, C.c_size_t]),
+    "el_slim_w": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, _f32p, _i32p, C.c_int64, C.c_int32, _i64p, _i32p, _f32p, C.c_void_p,
+                            C.c_size_t]),
     "el_als_gram_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "el_als_gram": (C.c_int, [C.c_void_p, C.c_void_p, _f64p, C.c_int64, C.c_int32, _f64p, C.c_void_p, C.c_size_t]),
     "el_als_solve_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),

@@ -427,6 +427,110 @@ def rp3_build(ctx, Piu, piu_vals, Pui, pui_vals, degree, n_neighbors, normalize)
 
 
 # ------------------------------------------------------------------------------------------
+# SLIM (latent_factor_models/Slim): elastic-net coordinate descent per item
+# ------------------------------------------------------------------------------------------
+SLIM_EXCLUSIONS = {"column": _lib.EL_SLIM_COLUMN, "reference": _lib.EL_SLIM_REFERENCE}
+SLIM_FIT_WS_BYTES = 1 << 28          # bound of el_slim_fit's workspace: longer column ranges are fitted in pieces
+SLIM_MAX_ITER, SLIM_TOL = 100, 1e-4  # the ElasticNet arguments of slim_model.py:30-39
+
+
+def slim_seed_state(seed):
+    """The xorshift state sklearn draws for every fit of ElasticNet(random_state=seed)."""
+    return int(np.random.RandomState(seed).randint(0, 2147483647))
+
+
+def slim_order(ctx, seed_state, I, n_draws):
+    """The coordinates sklearn's selection='random' visits (el_slim_order): int32 [n_draws] on the device."""
+    order = torch.empty(max(int(n_draws), 1), dtype=torch.int32, device=ctx.device)
+    check(ctx.lib.el_slim_order(ctx.handle, ctx.stream(), int(seed_state) & 0xffffffff, int(I), int(n_draws), _ptr(order, torch.int32)),
+          "el_slim_order")
+    return order[:int(n_draws)]
+
+
+def slim_csc(ctx, R):
+    """(DeviceCSR of the CSC of a scipy [U, I] matrix: row i = column i of R, its users ascending; float32 values)."""
+    import scipy.sparse as sp
+    X = sp.csc_matrix(R, dtype=np.float32)
+    X.sum_duplicates()
+    X.sort_indices()
+    return DeviceCSR(X.indptr, X.indices, R.shape[0], ctx.device), device_values(X.data, ctx.device)
+
+
+def slim_penalties(alpha, l1_ratio, U):
+    """sklearn's l1_reg, l2_reg as the float32 solver receives them: the products in Python floats, rounded once."""
+    alpha, l1_ratio = float(alpha), float(l1_ratio)
+    return float(np.float32(alpha * l1_ratio * U)), float(np.float32(alpha * (1.0 - l1_ratio) * U))
+
+
+def slim_fit(ctx, csc, csc_vals, alpha, l1_ratio, order, n_neighbors, j_start=0, j_stop=None, exclusion="column",
+             max_iter=SLIM_MAX_ITER, tol=SLIM_TOL, coef=False, ws_bytes=None):
+    """slim_model.py:58-92 for the target columns [j_start, j_stop) (el_slim_fit), in blocks that bound the workspace:
+    (idx int32 [n, N], val float32 [n, N], cnt int32 [n], n_iter int32 [n]) on the device, N = min(n_neighbors, I); with coef=True
+    also the dense weights before the cut, float32 [n, I] (tests).  ws_bytes: a workspace size to pass instead of the needed one."""
+    if exclusion not in SLIM_EXCLUSIONS:
+        raise ValueError(f"exclusion {exclusion!r} is not supported; supported: {sorted(SLIM_EXCLUSIONS)}")
+    I, U = csc.n_rows, csc.n_cols
+    n_neighbors = int(n_neighbors)
+    if n_neighbors < 1:
+        raise ValueError("neighborhood must be >= 1")
+    if order.shape[0] < int(max_iter) * I:
+        raise ValueError(f"order holds {order.shape[0]} draws, {int(max_iter) * I} needed")
+    j_stop = I if j_stop is None else int(j_stop)
+    n, N = j_stop - int(j_start), min(n_neighbors, I)
+    l1, l2 = slim_penalties(alpha, l1_ratio, U)
+    dev = ctx.device
+    idx = torch.zeros((max(n, 1), N), dtype=torch.int32, device=dev)
+    val = torch.zeros((max(n, 1), N), dtype=torch.float32, device=dev)
+    cnt = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    n_iter = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    dense = torch.zeros((max(n, 1), I), dtype=torch.float32, device=dev) if coef else None
+    per_col = max(int(ctx.lib.el_slim_ws_bytes(U, I, 2, n_neighbors)) - int(ctx.lib.el_slim_ws_bytes(U, I, 1, n_neighbors)), 1)
+    block = max(min(SLIM_FIT_WS_BYTES // per_col, n), 1)
+    need = int(ctx.lib.el_slim_ws_bytes(U, I, block, n_neighbors))
+    given = need if ws_bytes is None else int(ws_bytes)
+    ws = torch.empty(max(given, 1), dtype=torch.uint8, device=dev)
+    for c0 in range(0, n, block):
+        c1 = min(c0 + block, n)
+        check(ctx.lib.el_slim_fit(ctx.handle, ctx.stream(), _ptr(csc.indptr, torch.int64), _ptr(csc.indices, torch.int32),
+                                  _ptr(csc_vals, torch.float32), U, I, l1, l2, int(max_iter), float(tol), _ptr(order, torch.int32),
+                                  SLIM_EXCLUSIONS[exclusion], int(j_start) + c0, int(j_start) + c1, n_neighbors,
+                                  _ptr(idx[c0:], torch.int32), _ptr(val[c0:], torch.float32), _ptr(cnt[c0:], torch.int32),
+                                  _ptr(n_iter[c0:], torch.int32), _ptr(dense[c0:], torch.float32) if coef else None,
+                                  C.c_void_p(ws.data_ptr()), given), "el_slim_fit")
+    out = (idx[:n], val[:n], cnt[:n], n_iter[:n])
+    return out + (dense[:n],) if coef else out
+
+
+def slim_w(ctx, idx, val, cnt):
+    """slim_model.py:109 on the column lists of all I targets (el_slim_w): (DeviceCSR W [I, I] columns ascending, float32 values),
+    the shape knn_build returns."""
+    I, N = int(cnt.shape[0]), int(idx.shape[1])
+    if idx.shape != (I, N) or val.shape != (I, N):
+        raise ValueError(f"column lists must be [{I}, {N}], got {tuple(idx.shape)} / {tuple(val.shape)}")
+    need = int(ctx.lib.el_slim_ws_bytes(I, I, 0, N))
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=ctx.device)
+    w_indptr = torch.empty(I + 1, dtype=torch.int64, device=ctx.device)
+    w_indices = torch.empty(max(I * N, 1), dtype=torch.int32, device=ctx.device)
+    w_vals = torch.empty(max(I * N, 1), dtype=torch.float32, device=ctx.device)
+    check(ctx.lib.el_slim_w(ctx.handle, ctx.stream(), _ptr(idx, torch.int32), _ptr(val, torch.float32), _ptr(cnt, torch.int32), I, N,
+                            _ptr(w_indptr), _ptr(w_indices), _ptr(w_vals), C.c_void_p(ws.data_ptr()), need), "el_slim_w")
+    nnz = int(w_indptr[-1].item())
+    W = DeviceCSR.from_tensors(w_indptr, w_indices[:nnz], I)
+    return W, (w_vals[:nnz] if nnz else w_vals[:1])
+
+
+def slim_build(ctx, csc, csc_vals, alpha, l1_ratio, n_neighbors, seed, exclusion="column", max_iter=SLIM_MAX_ITER, tol=SLIM_TOL):
+    """W of SLIM from the CSC of R (slim_csc): slim_order + slim_fit over every column + slim_w; also the sweeps per column.
+    knn_score_topk(A = R, B = W) takes W directly."""
+    I = csc.n_rows
+    order = slim_order(ctx, slim_seed_state(seed), I, int(max_iter) * I)
+    idx, val, cnt, n_iter = slim_fit(ctx, csc, csc_vals, alpha, l1_ratio, order, n_neighbors, exclusion=exclusion,
+                                     max_iter=max_iter, tol=tol)
+    W, w_vals = slim_w(ctx, idx, val, cnt)
+    return W, w_vals, n_iter
+
+
+# ------------------------------------------------------------------------------------------
 # alternating least squares (iALS / WRMF)
 # ------------------------------------------------------------------------------------------
 ALS_PIECE_LEN = 8192          # rows longer than this are summed in pieces (el_als_solve's long-row plan)

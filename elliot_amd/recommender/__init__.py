@@ -22,7 +22,8 @@ from .knn.user_knn.user_knn import UserKNN
 from .latent_factor_models.iALS.iALS import iALS
 from .latent_factor_models.WRMF.wrmf import WRMF
 from .autoencoders.EASE_R.ease_r import EASER
+from .latent_factor_models.Slim.slim import Slim
 
 __all__ = ["BaseRecommenderModel", "init_charger", "RecMixin", "BPRMF_batch", "BPRMF", "MultiVAE", "MultiDAE", "NeuMF", "GMF",
            "MF", "PMF", "FunkSVD", "LogisticMatrixFactorization", "LMF", "CML", "MF2020", "LightGCN", "NGCF", "ProxyRecommender",
-           "ItemKNN", "UserKNN", "iALS", "WRMF", "EASER", "RP3beta"]
+           "ItemKNN", "UserKNN", "iALS", "WRMF", "EASER", "RP3beta", "Slim"]

@@ -530,6 +530,48 @@ int el_rp3_cut(el_ctx* ctx, void* stream, const int32_t* list_idx, const float* 
                int64_t I, int32_t n_neighbors, int normalize,
                int64_t* w_indptr, int32_t* w_indices, float* w_vals, void* ws, size_t ws_bytes);
 
+/* ---- SLIM (latent_factor_models/Slim): elastic-net coordinate descent per item ---------------------------------------- */
+
+#define EL_SLIM_COLUMN 0        /* the target's own column is no regressor (the model of the paper)                       */
+#define EL_SLIM_REFERENCE 1     /* slim_model.py:62-66 as written: the ratings of USER ROW j are zeroed instead           */
+
+/* The visiting order of sklearn's selection='random' (_cd_fast.pyx rand_int): from the uint32 state s (0 becomes 1) per draw
+ * s ^= s << 13; s ^= s >> 17; s ^= s << 5; order[t] = (s % 2^31) % I, for n_draws consecutive draws.  seed_state is what
+ * RandomState(seed).randint(0, 2147483647) returns; every fit of a model walks the same stream.                          */
+int el_slim_order(el_ctx* ctx, void* stream, uint32_t seed_state, int64_t I, int64_t n_draws, int32_t* order);
+
+/* Bytes of workspace: n_cols > 0 for el_slim_fit over n_cols target columns in one call, n_cols == 0 for el_slim_w.      */
+size_t el_slim_ws_bytes(int64_t U, int64_t I, int64_t n_cols, int32_t n_neighbors);
+
+/* Replaces the loop of SlimModel.train (slim_model.py:58-92) for the target columns [j_start, j_stop): per target j sklearn's
+ * sparse_enet_coordinate_descent(positive, no intercept, random selection) on the CSC of R [U, I] (csc_indptr int64[I + 1],
+ * rows ascending, values float32) with y = column j:
+ *   norm[c] = float32 sum of x * x in stored order; w = 0; r = y; l1 / l2 = alpha * l1_ratio * U / alpha * (1 - l1_ratio) * U
+ *   rounded to float32 by the caller; order int32[max_iter * I] from el_slim_order; a draw is consumed before norm[c] == 0
+ *   skips the coordinate;
+ *   step: r += w[c] X[:, c] (if w[c] != 0); tmp = (float)(X[:, c] . r), summed in fp64 in a fixed order;
+ *         w[c] = tmp < 0 ? 0 : (float)(max((double)tmp - l1, 0) / (double)(float)(norm[c] + l2)); r -= w[c] X[:, c];
+ *   after a sweep with w_max == 0, d_w_max / w_max < tol or the last one: the duality gap (positive branch) in fp64;
+ *   stop when gap < (float)(tol * y . y).  A column with y == 0 returns w = 0 and n_iter = max_iter at once.
+ *   exclusion: EL_SLIM_COLUMN -- the values of column j are zero; EL_SLIM_REFERENCE -- the values of user row j are zero in
+ *   every column and y keeps its entry (needs I <= U: the reference raises IndexError otherwise).
+ *   cut (:71-78): of the weights != 0 the min(nnz - 1, N) largest by (value desc, index asc), N = min(n_neighbors, I) <= 2048.
+ * Output: list_idx int32 / list_val float [n, N] in rank order, list_cnt int32[n], n_iter int32[n] (sweeps run) and, if
+ * coef_or_null is given, the weights before the cut float[n, I]; n = j_stop - j_start.  The residual and the weights of a
+ * target live in LDS while 4 (U + I) bytes fit in a workgroup's 160 KiB, in the workspace beyond that.
+ * ws = el_slim_ws_bytes(U, I, n, n_neighbors) bytes.  The same input gives the same bytes.                                */
+int el_slim_fit(el_ctx* ctx, void* stream, const int64_t* csc_indptr, const int32_t* csc_indices, const float* csc_vals,
+                int64_t U, int64_t I, float l1, float l2, int32_t max_iter, float tol, const int32_t* order, int exclusion,
+                int64_t j_start, int64_t j_stop, int32_t n_neighbors,
+                int32_t* list_idx, float* list_val, int32_t* list_cnt, int32_t* n_iter, float* coef_or_null,
+                void* ws, size_t ws_bytes);
+
+/* The column lists of ALL I targets (el_slim_fit's layout, width N) to W[i, j] = w_j[i] as CSR [I, I], columns ascending
+ * (slim_model.py:109): w_indptr int64[I + 1], w_indices int32 / w_vals float with room for I * N entries (the nnz is
+ * w_indptr[I]).  ws = el_slim_ws_bytes(U, I, 0, N) bytes.                                                                 */
+int el_slim_w(el_ctx* ctx, void* stream, const int32_t* list_idx, const float* list_val, const int32_t* list_cnt,
+              int64_t I, int32_t N, int64_t* w_indptr, int32_t* w_indices, float* w_vals, void* ws, size_t ws_bytes);
+
 /* ---- alternating least squares: iALS / WRMF ------------------------------------------------------------------------ */
 
 #define EL_ALS_SKIP_EMPTY 1     /* el_als_solve: rows without entries keep their X row (iALS item half, warm items only) */
