@@ -26,6 +26,7 @@ EL_SLIM_COLUMN = 0
 EL_SLIM_REFERENCE = 1
 EL_ALS_SKIP_EMPTY = 1
 EL_ALS_MAX_F = 128
+EL_PSVD_MAX_R = 256
 
 _f32p = C.c_void_p
 _i32p = C.c_void_p
@@ -295,6 +296,19 @@ PROTOTYPES = {
     "el_ease_weights": (C.c_int, [C.c_void_p, C.c_void_p, _f64p, C.c_int64, C.c_int64, _f32p, C.c_int64, C.c_void_p, C.c_size_t]),
     "el_csr_dense_scores": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _f32p, C.c_int64, C.c_int64, _f32p, C.c_int64,
                                       C.c_int64, _f32p, C.c_int64]),
+    "el_spmm_csr_f64_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "el_spmm_csr_f64": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _f32p, C.c_int64, C.c_int64, _f64p, C.c_int64, C.c_int32,
+                                  _f64p, C.c_int64, _i32p, _i64p, C.c_int64, C.c_int64, C.c_int64, _i32p, C.c_void_p, C.c_size_t]),
+    "el_gram_f64_slots": (C.c_int64, [C.c_int64]),
+    "el_gram_f64_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "el_gram_f64": (C.c_int, [C.c_void_p, C.c_void_p, _f64p, C.c_int64, C.c_int64, C.c_int32, _f64p, C.c_int64, C.c_void_p,
+                              C.c_size_t]),
+    "el_psvd_orth_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "el_psvd_orth": (C.c_int, [C.c_void_p, C.c_void_p, _f64p, C.c_int64, C.c_int64, C.c_int32, _i32p, C.c_void_p, C.c_size_t]),
+    "el_psvd_project": (C.c_int, [C.c_void_p, C.c_void_p, _f64p, C.c_int64, C.c_int64, C.c_int32, _f64p, C.c_int64, C.c_int32,
+                                  _f64p, _f64p, C.c_int64, _f32p, C.c_int64]),
+    "el_psvd_signs_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "el_psvd_signs": (C.c_int, [C.c_void_p, C.c_void_p, _f64p, C.c_int64, C.c_int64, C.c_int32, _f64p, C.c_void_p, C.c_size_t]),
 }
 
 _lib = None

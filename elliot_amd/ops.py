@@ -835,6 +835,290 @@ class EaseDeviceState:
 
 
 # ------------------------------------------------------------------------------------------
+# PureSVD (randomized truncated SVD: CSR x dense fp64, Gram, Cholesky-QR2, projection)
+# ------------------------------------------------------------------------------------------
+PSVD_PIECE_LEN = 2048         # rows longer than this are summed in pieces (el_spmm_csr_f64's long-row plan)
+PSVD_OVERSAMPLES = 10         # sklearn's n_oversamples default
+PSVD_NONE = 0x7fffffff
+
+
+class SpmmCSR:
+    """One orientation of a sparse matrix for el_spmm_csr_f64: DeviceCSR, values (None: all ones) and the long-row plan."""
+
+    def __init__(self, indptr, indices, n_cols, device, vals=None, piece_len=PSVD_PIECE_LEN):
+        self.csr = DeviceCSR(indptr, indices, n_cols, device)
+        self.vals = None if vals is None else device_values(vals, device)
+        rows, first, self.n_pieces = als_plan(indptr, piece_len)
+        self.piece_len = int(piece_len)
+        self.n_long = int(rows.shape[0])
+        self.long_rows = torch.from_numpy(rows if rows.size else np.zeros(1, np.int32)).to(device)
+        self.long_first = torch.from_numpy(first).to(device)
+        self.n_rows, self.n_cols, self.nnz = self.csr.n_rows, self.csr.n_cols, self.csr.nnz
+
+
+def _rows_ptr(t, dtype, name):
+    """Pointer of a 2-D device tensor whose rows may be strided (unit column stride): the kernels take a leading dimension."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.ElliotHipError(f"{name}: expected a tensor on the GPU")
+    if t.dtype != dtype or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or t.stride(0) < t.shape[1]:
+        raise TypeError(f"{name}: expected a 2-D {dtype} tensor with unit column stride")
+    return C.c_void_p(t.data_ptr())
+
+
+def spmm_csr_f64(ctx, A, X, out=None, holder=None, verify=True):
+    """Y = A X (el_spmm_csr_f64) for a SpmmCSR A and an fp64 [n_cols, R] device tensor X (rows may be strided): stored order inside
+    a row, long rows in pieces.  verify: read the status back and raise on a plan or column-index fault."""
+    R = int(X.shape[1])
+    if X.shape[0] != A.n_cols:
+        raise ValueError(f"spmm_csr_f64: X has {X.shape[0]} rows, the matrix {A.n_cols} columns")
+    if out is None:
+        out = torch.empty((A.n_rows, R), dtype=torch.float64, device=ctx.device)
+    holder = holder if holder is not None else ctx
+    ws, need = _als_ws(ctx, holder, "_spmm64_ws", int(ctx.lib.el_spmm_csr_f64_ws_bytes(int(A.n_pieces), R)))
+    status = getattr(holder, "_spmm64_status", None)
+    if status is None:
+        status = holder._spmm64_status = torch.empty(2, dtype=torch.int32, device=ctx.device)
+    check(ctx.lib.el_spmm_csr_f64(ctx.handle, ctx.stream(), _ptr(A.csr.indptr, torch.int64), _ptr(A.csr.indices, torch.int32),
+                                  _ptr(A.vals, torch.float32) if A.vals is not None else None, int(A.n_rows), int(A.n_cols),
+                                  _rows_ptr(X, torch.float64, "X"), int(X.stride(0)), R, _rows_ptr(out, torch.float64, "Y"),
+                                  int(out.stride(0)),
+                                  _ptr(A.long_rows, torch.int32), _ptr(A.long_first, torch.int64), A.n_long, A.n_pieces,
+                                  A.piece_len, _ptr(status, torch.int32), ws, need), "el_spmm_csr_f64")
+    if verify:
+        plan, col = (int(v) for v in status.cpu().tolist())
+        if plan != PSVD_NONE:
+            raise _lib.ElliotHipError(f"el_spmm_csr_f64: the long-row plan does not describe row {plan}")
+        if col != PSVD_NONE:
+            raise _lib.ElliotHipError(f"el_spmm_csr_f64: row {col} holds a column index outside the matrix")
+    return out
+
+
+def gram_f64(ctx, Y, out=None, holder=None):
+    """G = Y^T Y (fp64 [R, R], el_gram_f64): the fp64 matrix instruction, fixed slots, symmetric bit for bit."""
+    n, R = int(Y.shape[0]), int(Y.shape[1])
+    if out is None:
+        out = torch.empty((R, R), dtype=torch.float64, device=ctx.device)
+    ws, need = _als_ws(ctx, holder if holder is not None else ctx, "_gram64_ws", int(ctx.lib.el_gram_f64_ws_bytes(n, R)))
+    check(ctx.lib.el_gram_f64(ctx.handle, ctx.stream(), _rows_ptr(Y, torch.float64, "Y"), int(Y.stride(0)), n, R,
+                              _ptr(out, torch.float64, "G"), int(out.stride(0)), ws, need), "el_gram_f64")
+    return out
+
+
+def psvd_orth(ctx, Y, holder=None, status=None):
+    """Orthonormalise the columns of fp64 Y [n, R] in place (el_psvd_orth: Cholesky-QR twice).  Returns the device status tensor
+    (int32[1]: the smallest refused column, 0x7fffffff = none); reading it is the caller's synchronisation."""
+    n, R = int(Y.shape[0]), int(Y.shape[1])
+    holder = holder if holder is not None else ctx
+    ws, need = _als_ws(ctx, holder, "_orth_ws", int(ctx.lib.el_psvd_orth_ws_bytes(n, R)))
+    if status is None:
+        status = torch.empty(1, dtype=torch.int32, device=ctx.device)
+    check(ctx.lib.el_psvd_orth(ctx.handle, ctx.stream(), _rows_ptr(Y, torch.float64, "Y"), int(Y.stride(0)), n, R,
+                               _ptr(status, torch.int32), ws, need), "el_psvd_orth")
+    return status
+
+
+def psvd_project(ctx, Y, W, col_scale=None, out64=None, out32=None, f64=True, f32=False):
+    """T = (Y W) diag(col_scale) (el_psvd_project) for fp64 Y [n, R] and W [R, k]: (T64 or None, T32 or None), each rounded once."""
+    n, R = int(Y.shape[0]), int(Y.shape[1])
+    k = int(W.shape[1])
+    if W.shape[0] != R:
+        raise ValueError("psvd_project: Y / W inner dimensions differ")
+    if out64 is None and f64:
+        out64 = torch.empty((n, k), dtype=torch.float64, device=ctx.device)
+    if out32 is None and f32:
+        out32 = torch.empty((n, k), dtype=torch.float32, device=ctx.device)
+    check(ctx.lib.el_psvd_project(ctx.handle, ctx.stream(), _rows_ptr(Y, torch.float64, "Y"), int(Y.stride(0)), n, R,
+                                  _rows_ptr(W, torch.float64, "W"), int(W.stride(0)), k, _ptr(col_scale, torch.float64, "col_scale"),
+                                  _rows_ptr(out64, torch.float64, "T64"), int(out64.stride(0)) if out64 is not None else 0,
+                                  _rows_ptr(out32, torch.float32, "T32"), int(out32.stride(0)) if out32 is not None else 0),
+          "el_psvd_project")
+    return out64, out32
+
+
+def psvd_signs(ctx, T, holder=None):
+    """svd_flip's signs of the columns of fp64 T [n, k] (el_psvd_signs): a device tensor double[k] of +-1."""
+    n, k = int(T.shape[0]), int(T.shape[1])
+    signs = torch.empty(k, dtype=torch.float64, device=ctx.device)
+    ws, need = _als_ws(ctx, holder if holder is not None else ctx, "_signs_ws", int(ctx.lib.el_psvd_signs_ws_bytes(n, k)))
+    check(ctx.lib.el_psvd_signs(ctx.handle, ctx.stream(), _rows_ptr(T, torch.float64, "T"), int(T.stride(0)), n, k,
+                                _ptr(signs, torch.float64), ws, need), "el_psvd_signs")
+    return signs
+
+
+def psvd_plan(U, I, factors):
+    """The shape rules of sklearn's randomized_svd at its defaults and this library's refusals: (R, n_iter, transposed).
+    transposed: the method runs on A^T (more items than users)."""
+    U, I = int(U), int(I)
+    try:
+        f = int(factors)
+    except (TypeError, ValueError):
+        raise ValueError(f"PureSVD: factors={factors!r} is not an integer") from None
+    if f != factors or f < 1:
+        raise ValueError(f"PureSVD: factors={factors!r} must be an integer >= 1")
+    R = f + PSVD_OVERSAMPLES
+    if R > _lib.EL_PSVD_MAX_R:
+        raise ValueError(f"PureSVD: factors={f} needs a table of factors + {PSVD_OVERSAMPLES} = {R} columns; the kernels hold at most "
+                         f"{_lib.EL_PSVD_MAX_R} (factors <= {_lib.EL_PSVD_MAX_R - PSVD_OVERSAMPLES})")
+    if R > min(U, I):
+        raise ValueError(f"PureSVD: factors + {PSVD_OVERSAMPLES} = {R} exceeds min(users, items) = {min(U, I)}: the basis would be "
+                         f"thinner than the method asks for (the reference degrades there; this implementation refuses)")
+    n_iter = 7 if f < 0.1 * min(U, I) else 4
+    return R, n_iter, U < I
+
+
+def psvd_check_rank(col, R):
+    """The status of el_psvd_orth as the model's refusal: a set status names the column whose pivot was refused (NaN, not positive,
+    or small against its diagonal entry: rank deficiency, or a condition number beyond what Cholesky-QR2 is proved for)."""
+    if int(col) != PSVD_NONE:
+        raise ValueError(f"PureSVD: the orthonormalisation refused the pivot of column {int(col)} of {int(R)} (relative test: not "
+                         f"above 8 (n R + R (R + 1)) 2^-53 times its diagonal entry): the train matrix has numerical rank below "
+                         f"factors + {PSVD_OVERSAMPLES} = {int(R)}, or its power iterates are too ill-conditioned for Cholesky-QR "
+                         f"(the reference's LU / QR normalisers tolerate both)")
+
+
+def psvd_start_matrix(n, R, seed):
+    """The reference's only randomness: RandomState(seed).normal(size=(n, R)) rounded to float32 (its matrix is float32), as fp64."""
+    return np.random.RandomState(seed).normal(size=(int(n), int(R))).astype(np.float32).astype(np.float64)
+
+
+def psvd_small_svd(G, factors, transposed):
+    """Host step: from G = Z^T Z (R x R, symmetric) the leading eigenpairs by numpy.linalg.eigh -> (s, W_user, W_item), the
+    singular values and the two [R, factors] matrices that turn the orthonormal basis Q and Z = M^T Q into the tables:
+    not transposed  user = Q U^,       item = Z U^            (U = Q U^, diag(s) Vt = (Z U^)^T)
+    transposed      user = Z U^ / s,   item = Q U^ s."""
+    lam, vec = np.linalg.eigh(np.asarray(G, dtype=np.float64))
+    order = np.argsort(lam)[::-1][:int(factors)]
+    s = np.sqrt(np.maximum(lam[order], 0.0))
+    Uh = np.ascontiguousarray(vec[:, order])
+    if not transposed:
+        return s, Uh, Uh.copy()
+    return s, np.ascontiguousarray(Uh / s[None, :]), np.ascontiguousarray(Uh * s[None, :])
+
+
+def psvd_memory_need(U, I, nnz, factors, n_long=0, n_pieces=0):
+    """Device bytes PureSvdDeviceState needs at its peak: both orientations of the pattern with their long-row plans (n_long long
+    rows in all), the two R-wide fp64 tables, the product's piece slots (n_pieces: the larger orientation's), the Gram /
+    orthonormalisation workspace, the fp64 user-side projection the signs are read from with its block maxima, the float32 tables."""
+    U, I, nnz, f = int(U), int(I), int(nnz), int(factors)
+    R = f + PSVD_OVERSAMPLES
+    csr = 2 * (4 * nnz) + 8 * (U + I + 2) + 12 * (int(n_long) + 2)
+    tables = 8 * R * (U + I)
+    slots = min(max((max(U, I) + 1023) // 1024, 1), 256)
+    ws = 8 * R * R * (slots + 3) + 8 * R * int(n_pieces) + 8 * f * ((U + 511) // 512)
+    out = 8 * f * U + 4 * f * (U + I)
+    return csr + tables + ws + out
+
+
+class PureSvdDeviceState:
+    """The PureSVD tables (float32 user_vec [U, factors], item_vec [I, factors]) in HBM.
+
+    build() restates sklearn's randomized_svd at its defaults: the host draws the Gaussian start matrix exactly as the reference
+    does, the device runs the power iterations (el_spmm_csr_f64 + el_psvd_orth instead of the LU / QR normalisers), the host
+    takes the R x R eigenproblem of Z^T Z (numpy.linalg.eigh), the device projects (el_psvd_project) and flips the signs
+    (el_psvd_signs).  The train pattern is on the device, in both orientations, for the build only.  recommend() is el_score_topk with a
+    zero bias and el_topk_pad.  The device memory is checked first."""
+
+    def __init__(self, ctx, sp_i_train, factors, seed, piece_len=PSVD_PIECE_LEN):
+        import scipy.sparse as sp
+        self.ctx = ctx
+        A = sp.csr_matrix(sp_i_train, dtype=np.float32)
+        self.U, self.I = int(A.shape[0]), int(A.shape[1])
+        self.R, self.n_iter, self.transposed = psvd_plan(self.U, self.I, factors)
+        self.factors, self.seed = int(factors), seed
+        self._piece_len = int(piece_len)
+        plans = [als_plan(np.concatenate(([0], np.cumsum(lens))), self._piece_len)
+                 for lens in (np.diff(A.indptr), np.bincount(A.indices, minlength=self.I))]
+        self.need = psvd_memory_need(self.U, self.I, A.nnz, self.factors, n_long=sum(p[0].shape[0] for p in plans),
+                                     n_pieces=max(p[2] for p in plans))
+        free, _total = torch.cuda.mem_get_info(ctx.device)
+        if self.need > free:
+            raise ValueError(f"PureSVD: {self.U} x {self.I} with factors={self.factors} needs {self.need} bytes of device memory "
+                             f"(two orientations of the pattern, two fp64 tables of {self.R} columns, workspaces, the tables); "
+                             f"{free} bytes are free")
+        self._host = A
+        self.user_vec = self.item_vec = None
+        self.user_vec64 = self.item_vec64 = None
+        self.sigma = None
+        self._zero_bias = None
+        self._oriented = None
+
+    def upload(self):
+        """Both orientations of the pattern on the device, (M, M^T): transposed on the host, uploaded here, released by build()."""
+        if self._oriented is not None:
+            return self._oriented
+        A = self._host if self._host.has_sorted_indices else self._host.sorted_indices()    # never reorders the caller's arrays
+        At = A.T.tocsr()
+        At.sort_indices()
+        dev = self.ctx.device
+        ones = lambda m: None if np.all(m.data == 1.0) else m.data
+        a = SpmmCSR(A.indptr, A.indices, self.I, dev, vals=ones(A), piece_len=self._piece_len)
+        at = SpmmCSR(At.indptr, At.indices, self.U, dev, vals=ones(At), piece_len=self._piece_len)
+        self._oriented = (at, a) if self.transposed else (a, at)
+        return self._oriented
+
+    def build(self, keep_f64=False):
+        """Runs the method; leaves user_vec / item_vec (float32, rounded once from fp64) on the device and sigma on the host, and
+        releases the device copies of the pattern and the workspaces.  keep_f64: also keep the fp64 tables (user_vec64 / item_vec64)."""
+        ctx, dev = self.ctx, self.ctx.device
+        M, Mt = self.upload()
+        Qn = torch.from_numpy(psvd_start_matrix(M.n_cols, self.R, self.seed)).to(dev)        # [M.shape[1], R]
+        Qm = torch.empty((M.n_rows, self.R), dtype=torch.float64, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        bad = torch.full((1,), PSVD_NONE, dtype=torch.int32, device=dev)
+
+        def orth(Y):
+            psvd_orth(ctx, Y, holder=self, status=status)
+            torch.minimum(bad, status, out=bad)                  # (buffer plumbing: the smallest refused column of any call)
+
+        for it in range(self.n_iter + 1):                        # the last round is Q = qr(M Q), Z = M^T Q (B = Q^T M transposed)
+            spmm_csr_f64(ctx, M, Qn, out=Qm, holder=self, verify=it == 0)
+            orth(Qm)
+            spmm_csr_f64(ctx, Mt, Qm, out=Qn, holder=self, verify=it == 0)
+            if it < self.n_iter:
+                orth(Qn)
+        psvd_check_rank(int(bad.item()), self.R)
+        G = gram_f64(ctx, Qn, holder=self)
+        self.sigma, w_user, w_item = psvd_small_svd(G.cpu().numpy(), self.factors, self.transposed)
+        Wu, Wi = torch.from_numpy(w_user).to(dev), torch.from_numpy(w_item).to(dev)
+        Yu, Yi = (Qn, Qm) if self.transposed else (Qm, Qn)         # the user-side and the item-side basis
+        T, _ = psvd_project(ctx, Yu, Wu)
+        signs = psvd_signs(ctx, T, holder=self)                  # svd_flip decides on the user-side table in both orientations
+        del T
+        self.user_vec64, self.user_vec = psvd_project(ctx, Yu, Wu, col_scale=signs, f64=keep_f64, f32=True)
+        self.item_vec64, self.item_vec = psvd_project(ctx, Yi, Wi, col_scale=signs, f64=keep_f64, f32=True)
+        self._oriented = None                                    # recommend() does not need the pattern: its HBM is released
+        for name in ("_spmm64_ws", "_gram64_ws", "_orth_ws", "_signs_ws"):
+            if hasattr(self, name):
+                delattr(self, name)
+        return self.user_vec, self.item_vec
+
+    def set_weights(self, user_vec, item_vec):
+        u = np.ascontiguousarray(user_vec, dtype=np.float32)
+        i = np.ascontiguousarray(item_vec, dtype=np.float32)
+        if u.ndim != 2 or i.ndim != 2 or u.shape[0] != self.U or i.shape[0] != self.I or u.shape[1] != i.shape[1]:
+            raise ValueError(f"PureSVD tables have shapes {u.shape} / {i.shape}, the model expects ({self.U}, f) / ({self.I}, f)")
+        self.user_vec = torch.from_numpy(u).to(self.ctx.device)
+        self.item_vec = torch.from_numpy(i).to(self.ctx.device)
+        self.user_vec64 = self.item_vec64 = None
+
+    def recommend(self, mask, k, start, stop):
+        """user_vec item_vec^T for users [start, stop) and the masked top-k (el_score_topk with a zero bias); lists short of k are
+        padded with (-1, -inf) (el_topk_pad): (idx, val) [n, k] on the device."""
+        if self.user_vec is None:
+            raise _lib.ElliotHipError("PureSVD: recommend() before build() or set_weights()")
+        kind, csr = mask if mask is not None else (None, None)
+        if self._zero_bias is None:
+            self._zero_bias = torch.zeros(self.I, dtype=torch.float32, device=self.ctx.device)
+        idx, val = score_topk(self.ctx, self.user_vec, self.item_vec, self._zero_bias, start, stop, k,
+                              excl=csr if kind == "excl" else None, cand=csr if kind == "cand" else None)
+        check(self.ctx.lib.el_topk_pad(self.ctx.handle, self.ctx.stream(), _ptr(idx, torch.int32), _ptr(val, torch.float32),
+                                       int(idx.numel())), "el_topk_pad")
+        return idx, val
+
+
+# ------------------------------------------------------------------------------------------
 # accuracy metrics on the device (SURVEY 8f, N1)
 # ------------------------------------------------------------------------------------------
 METRIC_NAMES = ("nDCG", "Precision", "Recall", "HR", "MAP", "MRR", "F1")

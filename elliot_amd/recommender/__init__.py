@@ -23,7 +23,8 @@ from .latent_factor_models.iALS.iALS import iALS
 from .latent_factor_models.WRMF.wrmf import WRMF
 from .autoencoders.EASE_R.ease_r import EASER
 from .latent_factor_models.Slim.slim import Slim
+from .latent_factor_models.PureSVD.pure_svd import PureSVD
 
 __all__ = ["BaseRecommenderModel", "init_charger", "RecMixin", "BPRMF_batch", "BPRMF", "MultiVAE", "MultiDAE", "NeuMF", "GMF",
            "MF", "PMF", "FunkSVD", "LogisticMatrixFactorization", "LMF", "CML", "MF2020", "LightGCN", "NGCF", "ProxyRecommender",
-           "ItemKNN", "UserKNN", "iALS", "WRMF", "EASER", "RP3beta", "Slim"]
+           "ItemKNN", "UserKNN", "iALS", "WRMF", "EASER", "RP3beta", "Slim", "PureSVD"]

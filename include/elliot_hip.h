@@ -650,6 +650,60 @@ int el_csr_dense_scores(el_ctx* ctx, void* stream, const int64_t* indptr, const 
  * value is -inf into (-1, -inf), the padding of the KNN and ALS lists.  idx int32[n], val float[n].                        */
 int el_topk_pad(el_ctx* ctx, void* stream, int32_t* idx, const float* val, int64_t n);
 
+/* ---- PureSVD: tall-skinny fp64 linear algebra for the randomized truncated SVD ------------------------------------ */
+
+#define EL_PSVD_MAX_R 256      /* widest table: factors + 10 (sklearn's oversampling)                                   */
+
+/* Replaces the products A @ Q and A.T @ Q of sklearn's randomized_range_finder (safe_sparse_dot on a CSR):
+ *   Y[n_rows, R] = A X for a plain CSR A (indptr int64, indices int32, vals float or NULL = all ones) and fp64 row-major
+ *   X[n_cols, R] (ldx), Y (ldy); 1 <= R <= EL_PSVD_MAX_R.
+ * A row's terms vals[e] * X[indices[e], :] (round-to-nearest multiply, then add) are added in stored order from +0.  A row
+ * of more than piece_len entries is cut into pieces of piece_len; piece p is summed into slot p of the workspace and the
+ * row is the sum of its slots in piece order from +0.  The plan comes from the host: long_rows int32[n_long] ascending
+ * (the rows longer than piece_len) and long_first int64[n_long + 1] (first slot of each; slots of a row consecutive,
+ * ceil(len / piece_len) of them; long_first[n_long] = n_pieces).  ws = el_spmm_csr_f64_ws_bytes(n_pieces, R) bytes.
+ * status int32[2] on the device, written by the call: [0] the smallest long row the plan does not describe, [1] the
+ * smallest row holding a column index outside [0, n_cols); 0x7fffffff = none.  Such rows' Y are undefined; nothing is
+ * read or written out of bounds.  No atomics on floating-point data: the same input gives the same bits on every run.     */
+size_t el_spmm_csr_f64_ws_bytes(int64_t n_pieces, int32_t R);
+int el_spmm_csr_f64(el_ctx* ctx, void* stream, const int64_t* indptr, const int32_t* indices, const float* vals,
+                    int64_t n_rows, int64_t n_cols, const double* X, int64_t ldx, int32_t R, double* Y, int64_t ldy,
+                    const int32_t* long_rows, const int64_t* long_first, int64_t n_long, int64_t n_pieces,
+                    int64_t piece_len, int32_t* status, void* ws, size_t ws_bytes);
+
+/* G[R, R] (ldg) = Y^T Y for fp64 Y[n, R] (ldy), 1 <= R <= EL_PSVD_MAX_R, on v_mfma_f64_16x16x4_f64.  The rows are summed
+ * in el_gram_f64_slots(n) slots of consecutive rows (a count that depends on n only), each from +0 in row order, and the
+ * slots are added in slot order from +0.  Only the upper triangle is computed; the lower one is its copy: G is symmetric
+ * bit for bit, and the same input gives the same bits on every run.  ws = el_gram_f64_ws_bytes(n, R) bytes.                */
+int64_t el_gram_f64_slots(int64_t n);
+size_t el_gram_f64_ws_bytes(int64_t n, int32_t R);
+int el_gram_f64(el_ctx* ctx, void* stream, const double* Y, int64_t ldy, int64_t n, int32_t R, double* G, int64_t ldg,
+                void* ws, size_t ws_bytes);
+
+/* Replaces the LU / QR normalisers of randomized_range_finder: orthonormalises the columns of Y[n, R] (ldy) in place by
+ * Cholesky-QR run twice.  Each pass: G = Y^T Y (el_gram_f64), the fp64 Cholesky G = L L^T, W = L^-T by substitution, and
+ * Y <- Y W on v_mfma_f64_16x16x4_f64.  A pivot is refused when it is NaN, non-positive, or below
+ * 8 (n R + R (R + 1)) 2^-53 times its own diagonal entry of G (the breakdown bound of Cholesky-QR2: the numerical rank
+ * of Y is below R).  status int32[1] on the device, written by the call: the smallest refused column of either pass,
+ * 0x7fffffff = none; Y is undefined when it is set.  ws = el_psvd_orth_ws_bytes(n, R) bytes.                               */
+size_t el_psvd_orth_ws_bytes(int64_t n, int32_t R);
+int el_psvd_orth(el_ctx* ctx, void* stream, double* Y, int64_t ldy, int64_t n, int32_t R, int32_t* status, void* ws,
+                 size_t ws_bytes);
+
+/* T[n, k] = (Y[n, R] W[R, k]) diag(col_scale) for fp64 Y (ldy) and W (ldw), k <= R <= EL_PSVD_MAX_R, terms in ascending
+ * order of the inner index inside the matrix instruction's groups of four.  col_scale double[k] on the device (NULL:
+ * ones); written as fp64 T64 (ldt64) and / or as float T32 (ldt32), each rounded once; either pointer may be NULL.
+ * T64 == Y is allowed when k == R and ldt64 == ldy (every row is read whole before it is written).                        */
+int el_psvd_project(el_ctx* ctx, void* stream, const double* Y, int64_t ldy, int64_t n, int32_t R, const double* W,
+                    int64_t ldw, int32_t k, const double* col_scale, double* T64, int64_t ldt64, float* T32, int64_t ldt32);
+
+/* Replaces sklearn's svd_flip: signs[c] = -1 when the entry of largest magnitude of column c of T[n, k] (ldt) is negative,
+ * +1 otherwise; among equal magnitudes the smallest row decides (numpy.argmax).  signs double[k] on the device.
+ * ws = el_psvd_signs_ws_bytes(n, k) bytes.                                                                                 */
+size_t el_psvd_signs_ws_bytes(int64_t n, int32_t k);
+int el_psvd_signs(el_ctx* ctx, void* stream, const double* T, int64_t ldt, int64_t n, int32_t k, double* signs, void* ws,
+                  size_t ws_bytes);
+
 /* ---- dense layers: fp32 MFMA GEMM with fused bias + activation (K9, K12) ----------------- */
 
 /* Replaces: keras.layers.Dense forward/backward products of the neural latent-factor models
