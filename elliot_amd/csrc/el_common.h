@@ -172,6 +172,17 @@ typedef unsigned int u32;
 
 // ---- workspace carving (host) -------------------------------------------------------
 static inline size_t el_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// the smallest power of two >= x
+static inline int el_pow2(int x) {
+    int v = 1;
+    while (v < x) v <<= 1;
+    return v;
+}
+// slots of a one-wave running best-k (ElWaveSelect and its like: a pass appends up to 64 keys before it compacts)
+static inline int el_select_cap(int k) {
+    const int c = el_pow2(k + 64);
+    return c < 128 ? 128 : c;
+}
 // key bits of a radix sort over keys in [0, n)
 static inline int el_bits_for(int64_t n) {
     int b = 1;

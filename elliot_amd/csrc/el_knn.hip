@@ -22,7 +22,7 @@
 #define KNN_BUILD_THREADS 256
 #define KNN_TILE_BYTES 65536                      // LDS accumulator tile of both kernels
 #define KNN_MAX_NEIGHBORS 2048                    // running top-N lives in LDS next to the tile
-#define KNN_MAX_K 4032                            // running top-k of the scoring wave (cap = next_pow2(k + 64) <= 4096)
+#define KNN_MAX_K 4032                            // running top-k of the scoring wave (cap = el_select_cap(k) <= 4096)
 
 namespace {
 
@@ -198,8 +198,7 @@ __global__ __launch_bounds__(64) void k_knn_score(KnnScore p) {
         e1 = p.excl_indptr[u + 1];
     }
     const bool tiled = p.tile < p.I;
-    int cnt = 0;
-    float tau = -INFINITY;
+    ElWaveSelect sel(keys, cnt_s, p.cap, p.k);
     for (int64_t i0 = 0; i0 < p.I; i0 += p.tile) {
         const int64_t i1 = (i0 + p.tile < p.I) ? i0 + p.tile : p.I;
         const int w = (int)(i1 - i0);
@@ -237,25 +236,13 @@ __global__ __launch_bounds__(64) void k_knn_score(KnnScore p) {
             if (pos < s1) {
                 item = use_cand ? p.cand_indices[pos] : (int32_t)(i0 + pos);
                 s = acc[item - i0] + 0.0f;
-                hit = (s == s) && s >= tau;
+                hit = (s == s) && s >= sel.tau;
             }
-            const u64 bal = __ballot(hit);
-            if (bal) {
-                const int offp = __popcll(bal & ((1ull << lane) - 1ull));
-                if (hit) keys[cnt + offp] = el_make_key(s, item);
-                cnt += __popcll(bal);
-            }
-            if (cnt > p.cap - 64) {
-                if (lane == 0) *cnt_s = cnt;
-                tau = el_wave_compact(keys, cnt_s, p.cap, p.k, lane);
-                cnt = cnt < p.k ? cnt : p.k;
-            }
+            sel.push(hit, s, item, lane);
         }
         el_wave_lds_sync();
     }
-    if (lane == 0) *cnt_s = cnt;
-    el_wave_compact(keys, cnt_s, p.cap, p.k, lane);
-    const int nv = cnt < p.k ? cnt : p.k;
+    const int nv = sel.finish(lane);
     for (int t = lane; t < p.k; t += 64) {
         int32_t oi = -1;
         float ov = -INFINITY;
@@ -268,22 +255,14 @@ __global__ __launch_bounds__(64) void k_knn_score(KnnScore p) {
     }
 }
 
-int knn_pow2(int x) {
-    int v = 1;
-    while (v < x) v <<= 1;
-    return v;
-}
-
-int knn_build_cap(int N) { return knn_pow2(2 * N + KNN_BUILD_THREADS); }
-
-size_t knn_align(size_t b) { return (b + 255) & ~(size_t)255; }
+int knn_build_cap(int N) { return el_pow2(2 * N + KNN_BUILD_THREADS); }
 
 }  // namespace
 
 extern "C" size_t el_knn_ws_bytes(int64_t n, int32_t n_neighbors) {
     if (n <= 0 || n_neighbors <= 0) return 0;
     const int64_t N = n_neighbors < n ? n_neighbors : n;
-    return knn_align(n * 8) + knn_align(n * 4) * 2 + knn_align(n * 8) + knn_align(n * N * 4) * 4;
+    return el_align256(n * 8) + el_align256(n * 4) * 2 + el_align256(n * N * 4) * 2 + el_knn_csr_ws_bytes(n, (int)N);
 }
 
 extern "C" int el_knn_build(el_ctx* ctx, void* stream, const int64_t* p_indptr, const int32_t* p_indices, const int32_t* p_vals,
@@ -310,14 +289,11 @@ extern "C" int el_knn_build(el_ctx* ctx, void* stream, const int64_t* p_indptr, 
                el_knn_ws_bytes(n, n_neighbors));
     hipStream_t st = (hipStream_t)stream;
     char* w = (char*)ws;
-    int64_t* nrm = (int64_t*)w;      w += knn_align(n * 8);
-    int32_t* lcnt = (int32_t*)w;     w += knn_align(n * 4);
-    int32_t* rowcnt = (int32_t*)w;   w += knn_align(n * 4);
-    int64_t* cursor = (int64_t*)w;   w += knn_align(n * 8);
-    int32_t* lx = (int32_t*)w;       w += knn_align((size_t)n * N * 4);
-    float* lv = (float*)w;           w += knn_align((size_t)n * N * 4);
-    int32_t* tc = (int32_t*)w;       w += knn_align((size_t)n * N * 4);
-    float* tv = (float*)w;
+    int64_t* nrm = (int64_t*)w;      w += el_align256(n * 8);
+    int32_t* lcnt = (int32_t*)w;     w += el_align256(n * 4);
+    int32_t* rowcnt = (int32_t*)w;   w += el_align256(n * 4);
+    int32_t* lx = (int32_t*)w;       w += el_align256((size_t)n * N * 4);
+    float* lv = (float*)w;           w += el_align256((size_t)n * N * 4);
     EL_CHECK_HIP(hipMemsetAsync(rowcnt, 0, (size_t)n * 4, st));
     EL_LAUNCH("k_knn_norms", k_knn_norms, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p_indptr, p_vals, n, nrm);
     EL_CHECK_LAUNCH();
@@ -339,16 +315,7 @@ extern "C" int el_knn_build(el_ctx* ctx, void* stream, const int64_t* p_indptr, 
         EL_LAUNCH("k_knn_topn", k_knn_topn<int>, dim3((unsigned)n), dim3(KNN_BUILD_THREADS), lds, st, p);
     }
     EL_CHECK_LAUNCH();
-    EL_LAUNCH("k_knn_scan", k_knn_scan, dim3(1), dim3(1024), 0, st, (const int32_t*)rowcnt, n, w_indptr, cursor);
-    EL_CHECK_LAUNCH();
-    const int64_t slots = n * N;
-    EL_LAUNCH("k_knn_place", k_knn_place, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, (const int32_t*)lx,
-              (const float*)lv, (const int32_t*)lcnt, n, N, cursor, tc, tv);
-    EL_CHECK_LAUNCH();
-    EL_LAUNCH("k_knn_rank", k_knn_rank, dim3((unsigned)n), dim3(256), 0, st, (const int64_t*)w_indptr, (const int32_t*)tc,
-              (const float*)tv, n, w_indices, w_vals);
-    EL_CHECK_LAUNCH();
-    return 0;
+    return el_knn_csr_launch(st, lx, lv, lcnt, n, N, rowcnt, w_indptr, w_indices, w_vals, w);
 }
 
 extern "C" int el_knn_score_topk(el_ctx* ctx, void* stream, const int64_t* a_indptr, const int32_t* a_indices, const float* a_vals,
@@ -372,8 +339,7 @@ extern "C" int el_knn_score_topk(el_ctx* ctx, void* stream, const int64_t* a_ind
     p.excl_indptr = excl_indptr, p.excl_indices = excl_indices;
     p.cand_indptr = cand_indptr, p.cand_indices = cand_indices;
     p.k = k;
-    p.cap = knn_pow2(k + 64);
-    if (p.cap < 128) p.cap = 128;
+    p.cap = el_select_cap(k);
     const int64_t max_tile = KNN_TILE_BYTES / 4;
     p.tile = (int)(I < max_tile ? ((I + 63) / 64) * 64 : max_tile);
     p.out_idx = out_idx, p.out_val = out_val;

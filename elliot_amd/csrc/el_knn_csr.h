@@ -1,15 +1,27 @@
-// Per-column neighbour lists -> W as CSR with ascending columns: shared by el_knn.hip (ItemKNN / UserKNN) and el_rp3.hip
-// (RP3beta, which also uses scan + place as its counting sort by column).
+// Per-column neighbour lists -> W as CSR with ascending columns: shared by el_knn.hip (ItemKNN / UserKNN), el_slim.hip (SLIM)
+// and el_rp3.hip (RP3beta, which also uses scan + place as its counting sort by column).
 //   lists     lx / lv [n, N] with lcnt[c] entries for target column c, rowcnt[x] = entries that name row x
+//   k_knn_count  rowcnt of finished lists (a kernel that writes its lists may count as it goes instead)
 //   k_knn_scan   rowcnt -> indptr, cursor
 //   k_knn_place  every list entry to its row (arbitrary order inside the row)
 //   k_knn_rank   orders each row by column
+//   el_knn_csr_launch  scan, place and rank on a workspace of el_knn_csr_ws_bytes
 #pragma once
 #include "el_common.h"
 
 #define KNN_RANK_WORDS 2048                       // transpose: presence bitmap of 2048 * 32 targets per pass
 
 namespace {
+
+// entries of the lists per row of W (integer atomics: any order, the same counts)
+__global__ __launch_bounds__(256) void k_knn_count(const int32_t* __restrict__ lx, const int32_t* __restrict__ lcnt, int64_t n,
+                                                   int N, int32_t* __restrict__ rowcnt) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * N) return;
+    const int64_t c = e / N;
+    if ((int)(e - c * N) >= lcnt[c]) return;
+    atomicAdd(&rowcnt[lx[e]], 1);
+}
 
 // indptr[0] = 0, indptr[x + 1] = sum rowcnt[0 .. x]; cursor[x] = indptr[x].  One workgroup of 1024 threads.
 __global__ __launch_bounds__(1024) void k_knn_scan(const int32_t* __restrict__ rowcnt, int64_t n, int64_t* __restrict__ indptr,
@@ -107,6 +119,39 @@ __global__ __launch_bounds__(256) void k_knn_rank(const int64_t* __restrict__ in
         base += total;
         __syncthreads();
     }
+}
+
+// what scan / place / rank need beside the lists and W: the rows' cursors and the placed, not yet ordered entries
+struct KnnCsrWs {
+    int64_t* cursor;     // [n]
+    int32_t* tc;         // [n, N]
+    float* tv;           // [n, N]
+};
+
+size_t el_knn_csr_ws_bytes(int64_t n, int N) { return el_align256((size_t)n * 8) + el_align256((size_t)n * N * 4) * 2; }
+
+KnnCsrWs el_knn_csr_carve(void* ws, int64_t n, int N) {
+    char* w = (char*)ws;
+    KnnCsrWs c;
+    c.cursor = (int64_t*)w;   w += el_align256((size_t)n * 8);
+    c.tc = (int32_t*)w;       w += el_align256((size_t)n * N * 4);
+    c.tv = (float*)w;
+    return c;
+}
+
+// lists + filled rowcnt -> W (w_indptr [n + 1], w_indices / w_vals [n * N]); ws: el_knn_csr_ws_bytes(n, N)
+int el_knn_csr_launch(hipStream_t st, const int32_t* lx, const float* lv, const int32_t* lcnt, int64_t n, int N,
+                      const int32_t* rowcnt, int64_t* w_indptr, int32_t* w_indices, float* w_vals, void* ws) {
+    const KnnCsrWs c = el_knn_csr_carve(ws, n, N);
+    EL_LAUNCH("k_knn_scan", k_knn_scan, dim3(1), dim3(1024), 0, st, rowcnt, n, w_indptr, c.cursor);
+    EL_CHECK_LAUNCH();
+    EL_LAUNCH("k_knn_place", k_knn_place, dim3((unsigned)((n * N + 255) / 256)), dim3(256), 0, st, lx, lv, lcnt, n, N, c.cursor, c.tc,
+              c.tv);
+    EL_CHECK_LAUNCH();
+    EL_LAUNCH("k_knn_rank", k_knn_rank, dim3((unsigned)n), dim3(256), 0, st, (const int64_t*)w_indptr, (const int32_t*)c.tc,
+              (const float*)c.tv, n, w_indices, w_vals);
+    EL_CHECK_LAUNCH();
+    return 0;
 }
 
 }  // namespace

@@ -278,16 +278,6 @@ __global__ __launch_bounds__(64) void k_rp3_list_l1(const int32_t* __restrict__ 
     }
 }
 
-// entries per column of the row lists (integer atomics: any order, the same counts)
-__global__ __launch_bounds__(256) void k_rp3_colcount(const int32_t* __restrict__ lx, const int32_t* __restrict__ lcnt, int64_t n,
-                                                      int N, int32_t* __restrict__ colcnt) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n * N) return;
-    const int64_t r = e / N;
-    if ((int)(e - r * N) >= lcnt[r]) return;
-    atomicAdd(&colcnt[lx[e]], 1);
-}
-
 // One wave per column j: its bucket of (row, value) in any order -> the N largest non-zero values by (value desc, row asc),
 // as the per-column list k_knn_scan / k_knn_place / k_knn_rank turn into W's rows.
 __global__ __launch_bounds__(64) void k_rp3_coltop(const int64_t* __restrict__ colptr, const int32_t* __restrict__ tc,
@@ -299,8 +289,7 @@ __global__ __launch_bounds__(64) void k_rp3_coltop(const int64_t* __restrict__ c
     const int lane = threadIdx.x;
     const int64_t j = blockIdx.x;
     const int64_t e0 = colptr[j], e1 = colptr[j + 1];
-    int cnt = 0;
-    float tau = -INFINITY;
+    ElWaveSelect sel(keys, cnt_s, cap, N);
     for (int64_t base = e0; base < e1; base += 64) {
         const int64_t e = base + lane;
         bool hit = false;
@@ -309,23 +298,11 @@ __global__ __launch_bounds__(64) void k_rp3_coltop(const int64_t* __restrict__ c
         if (e < e1) {
             v = tv[e];
             r = tc[e];
-            hit = v != 0.f && v >= tau;
+            hit = v != 0.f && v >= sel.tau;
         }
-        const u64 bal = __ballot(hit);
-        if (bal) {
-            const int offp = __popcll(bal & ((1ull << lane) - 1ull));
-            if (hit) keys[cnt + offp] = el_make_key(v, r);
-            cnt += __popcll(bal);
-        }
-        if (cnt > cap - 64) {
-            if (lane == 0) *cnt_s = cnt;
-            tau = el_wave_compact(keys, cnt_s, cap, N, lane);
-            cnt = cnt < N ? cnt : N;
-        }
+        sel.push(hit, v, r, lane);
     }
-    if (lane == 0) *cnt_s = cnt;
-    el_wave_compact(keys, cnt_s, cap, N, lane);
-    const int m = cnt < N ? cnt : N;
+    const int m = sel.finish(lane);
     for (int t = lane; t < m; t += 64) {
         const int32_t r = el_key_item(keys[t]);
         cx[j * N + t] = r;
@@ -333,17 +310,6 @@ __global__ __launch_bounds__(64) void k_rp3_coltop(const int64_t* __restrict__ c
         atomicAdd(&rowcnt[r], 1);
     }
     if (lane == 0) ccnt[j] = m;
-}
-
-int rp3_pow2(int x) {
-    int v = 1;
-    while (v < x) v <<= 1;
-    return v;
-}
-
-int rp3_cap(int N) {
-    const int c = rp3_pow2(N + 64);
-    return c < 128 ? 128 : c;
 }
 
 // slices of the catalogue: as few as the tile allows, but a catalogue narrower than RP3_SPREAD tiles is still spread
@@ -365,8 +331,8 @@ size_t rp3_rows_ws(int64_t I, int N, int64_t n_rows) {
 }
 
 size_t rp3_cut_ws(int64_t I, int N) {
-    const size_t L = (size_t)I * N;
-    return el_align256((size_t)I * 4) * 3 + el_align256((size_t)(I + 1) * 8) + el_align256((size_t)I * 8) + el_align256(L * 4) * 5;
+    return el_align256((size_t)I * 4) * 3 + el_align256((size_t)(I + 1) * 8) + el_align256((size_t)I * N * 4) * 3 +
+           el_knn_csr_ws_bytes(I, N);
 }
 
 }  // namespace
@@ -415,7 +381,7 @@ extern "C" int el_rp3_rows(el_ctx* ctx, void* stream, const int64_t* piu_indptr,
     p.pp = piu_indptr, p.pi = piu_indices, p.pv = piu_vals;
     p.qp = pui_indptr, p.qi = pui_indices, p.qv = pui_vals;
     p.deg = degree, p.I = I, p.i_start = i_start, p.N = N;
-    p.cap = rp3_cap(N);
+    p.cap = el_select_cap(N);
     const size_t slots = (size_t)rows * p.S;
     char* w = (char*)ws;
     p.sk = (u64*)w;       w += el_align256(slots * N * 8);
@@ -450,17 +416,15 @@ extern "C" int el_rp3_cut(el_ctx* ctx, void* stream, const int32_t* list_idx, co
     int32_t* ccnt = (int32_t*)w;     w += el_align256((size_t)I * 4);
     int32_t* rowcnt = (int32_t*)w;   w += el_align256((size_t)I * 4);
     int64_t* colptr = (int64_t*)w;   w += el_align256((size_t)(I + 1) * 8);
-    int64_t* cursor = (int64_t*)w;   w += el_align256((size_t)I * 8);
     float* ln = (float*)w;           w += el_align256(L * 4);
-    int32_t* tc = (int32_t*)w;       w += el_align256(L * 4);
-    float* tv = (float*)w;           w += el_align256(L * 4);
     int32_t* cx = (int32_t*)w;       w += el_align256(L * 4);
-    float* cv = (float*)w;
-    const int cap = rp3_cap(N);
+    float* cv = (float*)w;           w += el_align256(L * 4);
+    const KnnCsrWs b = el_knn_csr_carve(w, I, N);              // the buckets of the counting sort; el_knn_csr_launch reuses them
+    const int cap = el_select_cap(N);
     const unsigned eblocks = (unsigned)((L + 255) / 256);
     const float* lv = list_val;
     if (normalize) {
-        const int ncap = rp3_pow2(N < 64 ? 64 : N);
+        const int ncap = el_pow2(N < 64 ? 64 : N);
         EL_LAUNCH("k_rp3_list_l1", k_rp3_list_l1, dim3((unsigned)I), dim3(64), (size_t)ncap * 8 + 16, st, list_idx, list_val, list_cnt,
                   N, ncap, ln);
         EL_CHECK_LAUNCH();
@@ -468,26 +432,18 @@ extern "C" int el_rp3_cut(el_ctx* ctx, void* stream, const int32_t* list_idx, co
     }
     EL_CHECK_HIP(hipMemsetAsync(colcnt, 0, (size_t)I * 4, st));
     EL_CHECK_HIP(hipMemsetAsync(rowcnt, 0, (size_t)I * 4, st));
-    EL_LAUNCH("k_rp3_colcount", k_rp3_colcount, dim3(eblocks), dim3(256), 0, st, list_idx, list_cnt, I, N, colcnt);
+    EL_LAUNCH("k_knn_count", k_knn_count, dim3(eblocks), dim3(256), 0, st, list_idx, list_cnt, I, N, colcnt);
     EL_CHECK_LAUNCH();
     // counting sort of the row lists by column: bucket j = (row, value) of every entry in column j
-    EL_LAUNCH("k_knn_scan", k_knn_scan, dim3(1), dim3(1024), 0, st, (const int32_t*)colcnt, I, colptr, cursor);
+    EL_LAUNCH("k_knn_scan", k_knn_scan, dim3(1), dim3(1024), 0, st, (const int32_t*)colcnt, I, colptr, b.cursor);
     EL_CHECK_LAUNCH();
-    EL_LAUNCH("k_knn_place", k_knn_place, dim3(eblocks), dim3(256), 0, st, list_idx, lv, list_cnt, I, N, cursor, tc, tv);
+    EL_LAUNCH("k_knn_place", k_knn_place, dim3(eblocks), dim3(256), 0, st, list_idx, lv, list_cnt, I, N, b.cursor, b.tc, b.tv);
     EL_CHECK_LAUNCH();
     EL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rp3_coltop), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)((size_t)cap * 8 + 16)));
     EL_LAUNCH("k_rp3_coltop", k_rp3_coltop, dim3((unsigned)I), dim3(64), (size_t)cap * 8 + 16, st, (const int64_t*)colptr,
-              (const int32_t*)tc, (const float*)tv, N, cap, cx, cv, ccnt, rowcnt);
+              (const int32_t*)b.tc, (const float*)b.tv, N, cap, cx, cv, ccnt, rowcnt);
     EL_CHECK_LAUNCH();
-    // the per-column lists to W's rows, columns ascending (the buckets are free again: tc / tv are reused)
-    EL_LAUNCH("k_knn_scan", k_knn_scan, dim3(1), dim3(1024), 0, st, (const int32_t*)rowcnt, I, w_indptr, cursor);
-    EL_CHECK_LAUNCH();
-    EL_LAUNCH("k_knn_place", k_knn_place, dim3(eblocks), dim3(256), 0, st, (const int32_t*)cx, (const float*)cv, (const int32_t*)ccnt,
-              I, N, cursor, tc, tv);
-    EL_CHECK_LAUNCH();
-    EL_LAUNCH("k_knn_rank", k_knn_rank, dim3((unsigned)I), dim3(256), 0, st, (const int64_t*)w_indptr, (const int32_t*)tc,
-              (const float*)tv, I, w_indices, w_vals);
-    EL_CHECK_LAUNCH();
-    return 0;
+    // the per-column lists to W's rows, columns ascending (the buckets are free again)
+    return el_knn_csr_launch(st, cx, cv, ccnt, I, N, rowcnt, w_indptr, w_indices, w_vals, w);
 }

@@ -277,27 +277,14 @@ __global__ __launch_bounds__(64) void k_slim_fit(SlimFit p) {
         return;
     }
     slim_sync<LDS>();
-    int cnt = 0;
-    float tau = -INFINITY;
+    ElWaveSelect sel(keys, cnt_s, p.cap, K);
     for (int64_t base = 0; base < I; base += 64) {
         const int64_t i = base + lane;
         float v = 0.f;
         if (i < I) v = w[i];
-        const bool hit = v != 0.f && v >= tau;
-        const u64 bal = __ballot(hit);
-        if (bal) {
-            const int offp = __popcll(bal & ((1ull << lane) - 1ull));
-            if (hit) keys[cnt + offp] = el_make_key(v, (int32_t)i);
-            cnt += __popcll(bal);
-        }
-        if (cnt > p.cap - 64) {
-            if (lane == 0) *cnt_s = cnt;
-            tau = el_wave_compact(keys, cnt_s, p.cap, K, lane);
-            cnt = cnt < K ? cnt : K;
-        }
+        sel.push(v != 0.f && v >= sel.tau, v, (int32_t)i, lane);
     }
-    if (lane == 0) *cnt_s = cnt;
-    el_wave_compact(keys, cnt_s, p.cap, K, lane);
+    sel.finish(lane);                                          // K <= nnz - 1: the stream holds more than K
     for (int q = lane; q < K; q += 64) {
         p.lx[t * p.N + q] = el_key_item(keys[q]);
         p.lv[t * p.N + q] = el_key_score(keys[q]);
@@ -319,28 +306,7 @@ __global__ __launch_bounds__(64) void k_slim_norm_ref(const int64_t* __restrict_
     norm[t * I + c] = s;
 }
 
-// entries of the lists per row of W (integer atomics: any order, the same counts)
-__global__ __launch_bounds__(256) void k_slim_count(const int32_t* __restrict__ lx, const int32_t* __restrict__ lcnt, int64_t n,
-                                                    int N, int32_t* __restrict__ rowcnt) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n * N) return;
-    const int64_t c = e / N;
-    if ((int)(e - c * N) >= lcnt[c]) return;
-    atomicAdd(&rowcnt[lx[e]], 1);
-}
-
-int slim_pow2(int x) {
-    int v = 1;
-    while (v < x) v <<= 1;
-    return v;
-}
-
-int slim_cap(int N) {
-    const int c = slim_pow2(N + 64);
-    return c < 128 ? 128 : c;
-}
-
-size_t slim_cut_lds(int N) { return (size_t)slim_cap(N) * 8 + 16; }
+size_t slim_cut_lds(int N) { return (size_t)el_select_cap(N) * 8 + 16; }
 
 size_t slim_w_bytes(int64_t I) { return ((size_t)I * 4 + 15) & ~(size_t)15; }
 
@@ -357,10 +323,7 @@ size_t slim_fit_ws(int64_t U, int64_t I, int N, int64_t n) {
     return b;
 }
 
-size_t slim_w_ws(int64_t I, int N) {
-    const size_t L = (size_t)I * N;
-    return el_align256((size_t)I * 4) + el_align256((size_t)I * 8) + el_align256(L * 4) * 2;
-}
+size_t slim_w_ws(int64_t I, int N) { return el_align256((size_t)I * 4) + el_knn_csr_ws_bytes(I, N); }
 
 }  // namespace
 
@@ -420,7 +383,7 @@ extern "C" int el_slim_fit(el_ctx* ctx, void* stream, const int64_t* csc_indptr,
     }
     p.U = U, p.I = I, p.j_start = j_start;
     p.l1 = l1, p.l2 = l2, p.tol = tol, p.max_iter = max_iter, p.reference = ref ? 1 : 0;
-    p.N = N, p.cap = slim_cap(N), p.w_bytes = (int)slim_w_bytes(I);
+    p.N = N, p.cap = el_select_cap(N), p.w_bytes = (int)slim_w_bytes(I);
     p.lx = list_idx, p.lv = list_val, p.lcnt = list_cnt, p.n_iter = n_iter, p.coef = coef_or_null;
     if (ref) {
         EL_LAUNCH("k_slim_norm_ref", k_slim_norm_ref, dim3((unsigned)((I + 63) / 64), (unsigned)n), dim3(64), 0, st, csc_indptr,
@@ -449,22 +412,11 @@ extern "C" int el_slim_w(el_ctx* ctx, void* stream, const int32_t* list_idx, con
     EL_REQUIRE(N >= 1 && N <= I && N <= SLIM_MAX_NEIGHBORS, "el_slim_w: list width %d outside [1, min(I, %d)]", N, SLIM_MAX_NEIGHBORS);
     EL_REQUIRE(ws != nullptr && ws_bytes >= slim_w_ws(I, N), "el_slim_w: workspace too small (need %zu bytes)", slim_w_ws(I, N));
     hipStream_t st = (hipStream_t)stream;
-    const size_t L = (size_t)I * N;
-    char* w = (char*)ws;
-    int32_t* rowcnt = (int32_t*)w;   w += el_align256((size_t)I * 4);
-    int64_t* cursor = (int64_t*)w;   w += el_align256((size_t)I * 8);
-    int32_t* tc = (int32_t*)w;       w += el_align256(L * 4);
-    float* tv = (float*)w;
-    const unsigned eblocks = (unsigned)((L + 255) / 256);
+    int32_t* rowcnt = (int32_t*)ws;
     EL_CHECK_HIP(hipMemsetAsync(rowcnt, 0, (size_t)I * 4, st));
-    EL_LAUNCH("k_slim_count", k_slim_count, dim3(eblocks), dim3(256), 0, st, list_idx, list_cnt, I, N, rowcnt);
+    EL_LAUNCH("k_knn_count", k_knn_count, dim3((unsigned)(((size_t)I * N + 255) / 256)), dim3(256), 0, st, list_idx, list_cnt, I, N,
+              rowcnt);
     EL_CHECK_LAUNCH();
-    EL_LAUNCH("k_knn_scan", k_knn_scan, dim3(1), dim3(1024), 0, st, (const int32_t*)rowcnt, I, w_indptr, cursor);
-    EL_CHECK_LAUNCH();
-    EL_LAUNCH("k_knn_place", k_knn_place, dim3(eblocks), dim3(256), 0, st, list_idx, list_val, list_cnt, I, N, cursor, tc, tv);
-    EL_CHECK_LAUNCH();
-    EL_LAUNCH("k_knn_rank", k_knn_rank, dim3((unsigned)I), dim3(256), 0, st, (const int64_t*)w_indptr, (const int32_t*)tc,
-              (const float*)tv, I, w_indices, w_vals);
-    EL_CHECK_LAUNCH();
-    return 0;
+    return el_knn_csr_launch(st, list_idx, list_val, list_cnt, I, N, rowcnt, w_indptr, w_indices, w_vals,
+                             (char*)ws + el_align256((size_t)I * 4));
 }

@@ -552,18 +552,6 @@ __global__ __launch_bounds__(64) void k_topk_wave_f64(TopkParams64 p, int cap) {
 // =====================================================================================
 // host side
 // =====================================================================================
-static int next_pow2(int x) {
-    int p = 1;
-    while (p < x) p <<= 1;
-    return p;
-}
-
-static int wave_cap_for_k(int k) {
-    int cap = next_pow2(k + 64);
-    return cap < 128 ? 128 : cap;
-}
-
-
 static bool mfma_eligible(int F, int k, const void* cand) { return cand == nullptr && F >= 1 && F <= 256 && k >= 1 && k <= 40; }
 
 // el_topk_screen.hip
@@ -717,10 +705,10 @@ int el_topk_run_list(const TopkParams& p0, void* scratch, size_t scratch_bytes, 
             d.out_idx = part_idx;
             d.out_val = part_val;
         }
-        const int wcap = wave_cap_for_k(p0.k);
+        const int wcap = el_select_cap(p0.k);
         EL_LAUNCH("k_topk_wave", k_topk_wave<true>, dim3(LIST_DENSE, DS > 1 ? DS : 1), dim3(64), (size_t)wcap * 8 + 16, st, d, wcap);
         if (DS > 1) {
-            int mcap = next_pow2(DS * p0.k);
+            int mcap = el_pow2(DS * p0.k);
             if (mcap < 64) mcap = 64;
             EL_LAUNCH("k_topk_merge", k_topk_merge, dim3(LIST_DENSE), dim3(64), (size_t)mcap * 8, st, (const int32_t*)part_idx,
                       (const float*)part_val, DS, (int64_t)LIST_DENSE, p0.k, mcap, p0.out_idx, p0.out_val, p0.ulist, p0.ulist_n, 0);
@@ -730,7 +718,7 @@ int el_topk_run_list(const TopkParams& p0, void* scratch, size_t scratch_bytes, 
     const int skip1 = p0.I_local > 0 ? LIST_DENSE : 0;
     if (!mfma_eligible(p0.F, p0.k, p0.cand_indptr)) {       // large k: the wave kernel takes the rest of the list
         if (n_users > skip1) {
-            const int wcap = wave_cap_for_k(p0.k);
+            const int wcap = el_select_cap(p0.k);
             int WS = (int)((p0.I_local + 1023) / 1024);             // item slices: one wave per (entry, slice) + merge
             if (WS > LIST_SPLIT) WS = LIST_SPLIT;
             while (WS > 1 && WS * p0.k > 8192) --WS;                // merge buffer limit
@@ -746,7 +734,7 @@ int el_topk_run_list(const TopkParams& p0, void* scratch, size_t scratch_bytes, 
             const int64_t rows = (n_users - skip1) < cap ? (n_users - skip1) : cap;
             EL_LAUNCH("k_topk_wave", k_topk_wave<false>, dim3((unsigned)rows, WS > 1 ? WS : 1), dim3(64), (size_t)wcap * 8 + 16, st, q, wcap);
             if (WS > 1) {
-                int mcap = next_pow2(WS * p0.k);
+                int mcap = el_pow2(WS * p0.k);
                 if (mcap < 64) mcap = 64;
                 EL_LAUNCH("k_topk_merge", k_topk_merge, dim3((unsigned)rows), dim3(64), (size_t)mcap * 8, st, (const int32_t*)part_idx,
                           (const float*)part_val, WS, cap, p0.k, mcap, p0.out_idx, p0.out_val, p0.ulist, p0.ulist_n, skip1);
@@ -777,7 +765,7 @@ int el_topk_run_list(const TopkParams& p0, void* scratch, size_t scratch_bytes, 
     }
     if (int rc = el_topk_launch_mfma(p, st)) return rc;
     if (S > 1) {
-        int mcap = next_pow2((int)S * p0.k);
+        int mcap = el_pow2((int)S * p0.k);
         if (mcap < 64) mcap = 64;
         EL_LAUNCH("k_topk_merge", k_topk_merge, dim3((unsigned)cap), dim3(64), (size_t)mcap * 8, st, (const int32_t*)part_idx,
                   (const float*)part_val, (int)S, cap, p0.k, mcap, p0.out_idx, p0.out_val, p0.ulist, p0.ulist_n, skip1);
@@ -838,7 +826,7 @@ extern "C" int el_score_topk(el_ctx* ctx, void* stream, const float* Gu, const f
     if (algo == EL_TOPK_MFMA) EL_REQUIRE(elig, "el_score_topk: MFMA kernel needs F<=256, k<=40 and no candidate list");
     bool use_mfma = (algo == EL_TOPK_MFMA) || (algo == EL_TOPK_AUTO && elig);
     if (use_mfma) return el_topk_launch_mfma(p, st);
-    int cap = wave_cap_for_k(k);
+    int cap = el_select_cap(k);
     EL_LAUNCH("k_topk_wave", k_topk_wave<false>, dim3((unsigned)(u_stop - u_start)), dim3(64), (size_t)cap * 8 + 16, st, p, cap);
     EL_CHECK_LAUNCH();
     return 0;
@@ -868,7 +856,7 @@ extern "C" int el_dense_topk(el_ctx* ctx, void* stream, const float* preds, int6
     p.out_val = out_val;
     p.preds = preds;
     p.ld = ld;
-    int cap = wave_cap_for_k(k);
+    int cap = el_select_cap(k);
     EL_LAUNCH("k_topk_wave", k_topk_wave<true>, dim3((unsigned)(u_stop - u_start)), dim3(64), (size_t)cap * 8 + 16,
                        (hipStream_t)stream, p, cap);
     EL_CHECK_LAUNCH();
@@ -900,7 +888,7 @@ extern "C" int el_score_topk_f64(el_ctx* ctx, void* stream, const double* P, con
     p.k = k;
     p.out_idx = out_idx;
     p.out_val = out_val;
-    int cap = wave_cap_for_k(k);
+    int cap = el_select_cap(k);
     EL_LAUNCH("k_topk_wave_f64", k_topk_wave_f64, dim3((unsigned)(u_stop - u_start)), dim3(64), (size_t)cap * 12,
                        (hipStream_t)stream, p, cap);
     EL_CHECK_LAUNCH();
@@ -914,7 +902,7 @@ extern "C" int el_topk_merge(el_ctx* ctx, void* stream, const int32_t* parts_idx
     EL_REQUIRE(G >= 1 && k >= 1 && (int64_t)G * k <= 8192, "el_topk_merge: G*k=%lld unsupported (<=8192)",
                (long long)G * k);
     if (n_users <= 0) return 0;
-    int cap = next_pow2(G * k);
+    int cap = el_pow2(G * k);
     if (cap < 64) cap = 64;
     EL_LAUNCH("k_topk_merge", k_topk_merge, dim3((unsigned)n_users), dim3(64), (size_t)cap * 8, (hipStream_t)stream,
                        parts_idx, parts_val, G, n_users, k, cap, out_idx, out_val, (const int32_t*)nullptr, (const int32_t*)nullptr, 0);

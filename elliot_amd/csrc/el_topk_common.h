@@ -1,4 +1,5 @@
-// Shared pieces of the top-k kernels (el_topk.hip, el_topk_screen.hip).
+// Shared pieces of the top-k kernels (el_topk.hip, el_topk_screen.hip) and of the one-wave selections of el_knn.hip, el_slim.hip,
+// el_rp3.hip.
 #pragma once
 #include "el_common.h"
 
@@ -71,6 +72,41 @@ __device__ __forceinline__ float el_wave_compact(u64* kb, int* cp, int cap, int 
     el_wave_lds_sync();
     return nt;
 }
+
+// The running best k of a stream of (value, index) pairs in one wave: keys[cap] and one int in LDS, cnt and tau in registers
+// (cap = el_select_cap(k) or any power of two >= k + 64).  The caller's hit predicate decides what enters and should refuse
+// what falls below tau; every lane calls push in every pass, all members but the pushed pair wave-uniform.
+struct ElWaveSelect {
+    u64* keys;
+    int* cnt_s;
+    int cap, k;
+    int cnt;
+    float tau;
+
+    __device__ __forceinline__ ElWaveSelect(u64* keys_, int* cnt_s_, int cap_, int k_)
+        : keys(keys_), cnt_s(cnt_s_), cap(cap_), k(k_), cnt(0), tau(-INFINITY) {}
+
+    __device__ __forceinline__ void push(bool hit, float v, int32_t index, int lane) {
+        const u64 bal = __ballot(hit);
+        if (bal) {
+            const int offp = __popcll(bal & ((1ull << lane) - 1ull));
+            if (hit) keys[cnt + offp] = el_make_key(v, index);
+            cnt += __popcll(bal);
+        }
+        if (cnt > cap - 64) {
+            if (lane == 0) *cnt_s = cnt;
+            tau = el_wave_compact(keys, cnt_s, cap, k, lane);
+            cnt = cnt < k ? cnt : k;
+        }
+    }
+
+    // sorts what is left: keys[0 .. returned count) are the best, (value desc, index asc)
+    __device__ __forceinline__ int finish(int lane) {
+        if (lane == 0) *cnt_s = cnt;
+        el_wave_compact(keys, cnt_s, cap, k, lane);
+        return cnt < k ? cnt : k;
+    }
+};
 
 // Same, but first drops keys whose item is in the (sorted) exclusion row idx[e0,e1): the MFMA kernel
 // inserts candidates unchecked and pays the membership test (a chain of dependent global loads) once

@@ -250,6 +250,23 @@ def device_values(values, device):
     return torch.from_numpy(v if v.shape[0] else np.zeros(1, np.float32)).to(device)
 
 
+def _workspace(ctx, need):
+    return torch.empty(max(int(need), 1), dtype=torch.uint8, device=ctx.device)
+
+
+def _w_alloc(ctx, n, N):
+    """(w_indptr, w_indices, w_vals) for a W of n rows with at most n * N entries (never a zero-length buffer)."""
+    return (torch.empty(n + 1, dtype=torch.int64, device=ctx.device), torch.empty(max(n * N, 1), dtype=torch.int32, device=ctx.device),
+            torch.empty(max(n * N, 1), dtype=torch.float32, device=ctx.device))
+
+
+def _w_result(w_indptr, w_indices, w_vals):
+    """(DeviceCSR W [n, n], float32 values) of filled _w_alloc arrays: what knn_build, rp3_cut and slim_w return."""
+    nnz = int(w_indptr[-1].item())
+    W = DeviceCSR.from_tensors(w_indptr, w_indices[:nnz], w_indptr.shape[0] - 1)
+    return W, (w_vals[:nnz] if nnz else w_vals[:1])
+
+
 def knn_integer_ratings(values):
     """(scale, int32 values): ratings times 1 (integers) or 2 (half steps), exactly.  Anything else is refused."""
     v = np.asarray(values, dtype=np.float64)
@@ -285,19 +302,14 @@ def knn_build(ctx, R, side, n_neighbors, sim):
     qvt = torch.from_numpy(qv if qv.size else np.zeros(1, np.int32)).to(dev)
     max_deg = int(np.diff(P.indptr).max()) if n else 0
     max_abs = int(np.abs(pv).max()) if pv.size else 0
-    N = min(int(n_neighbors), n)
     need = int(ctx.lib.el_knn_ws_bytes(int(n), int(n_neighbors)))
-    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-    w_indptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    w_indices = torch.empty(max(n * N, 1), dtype=torch.int32, device=dev)
-    w_vals = torch.empty(max(n * N, 1), dtype=torch.float32, device=dev)
+    ws = _workspace(ctx, need)
+    w_indptr, w_indices, w_vals = _w_alloc(ctx, n, min(int(n_neighbors), n))
     check(ctx.lib.el_knn_build(ctx.handle, ctx.stream(), _ptr(Pc.indptr), _ptr(Pc.indices), _ptr(pvt), _ptr(Qc.indptr),
                                _ptr(Qc.indices), _ptr(qvt), int(n), int(n_other), int(n_neighbors), KNN_SIMILARITIES[sim],
                                int(scale), max_deg, max_abs, _ptr(w_indptr), _ptr(w_indices), _ptr(w_vals),
                                C.c_void_p(ws.data_ptr()), need), "el_knn_build")
-    nnz = int(w_indptr[-1].item())
-    W = DeviceCSR.from_tensors(w_indptr, w_indices[:nnz], n)
-    return W, (w_vals[:nnz] if nnz else w_vals[:1])
+    return _w_result(w_indptr, w_indices, w_vals)
 
 
 def knn_score_topk(ctx, A, A_vals, B, B_vals, u_start, u_stop, k, excl=None, cand=None, out_idx=None, out_val=None):
@@ -388,7 +400,7 @@ def rp3_rows(ctx, Piu, piu_vals, Pui, pui_vals, degree, n_neighbors, i_start=0, 
     per_row = max(int(ctx.lib.el_rp3_ws_bytes(I, n_neighbors, 1)), 1)
     block = max(min(RP3_ROWS_WS_BYTES // per_row, n), 1)
     need = int(ctx.lib.el_rp3_ws_bytes(I, n_neighbors, block))
-    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=ctx.device)
+    ws = _workspace(ctx, need)
     for r0 in range(0, n, block):
         r1 = min(r0 + block, n)
         check(ctx.lib.el_rp3_rows(ctx.handle, ctx.stream(), _ptr(Piu.indptr, torch.int64), _ptr(Piu.indices, torch.int32),
@@ -408,16 +420,12 @@ def rp3_cut(ctx, idx, val, cnt, n_neighbors, normalize):
     if idx.shape != (I, N) or val.shape != (I, N):
         raise ValueError(f"row lists must be [{I}, {N}], got {tuple(idx.shape)}")
     need = int(ctx.lib.el_rp3_ws_bytes(I, n_neighbors, 0))
-    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=ctx.device)
-    w_indptr = torch.empty(I + 1, dtype=torch.int64, device=ctx.device)
-    w_indices = torch.empty(max(I * N, 1), dtype=torch.int32, device=ctx.device)
-    w_vals = torch.empty(max(I * N, 1), dtype=torch.float32, device=ctx.device)
+    ws = _workspace(ctx, need)
+    w_indptr, w_indices, w_vals = _w_alloc(ctx, I, N)
     check(ctx.lib.el_rp3_cut(ctx.handle, ctx.stream(), _ptr(idx, torch.int32), _ptr(val, torch.float32), _ptr(cnt, torch.int32), I,
                              n_neighbors, 1 if normalize else 0, _ptr(w_indptr), _ptr(w_indices), _ptr(w_vals),
                              C.c_void_p(ws.data_ptr()), need), "el_rp3_cut")
-    nnz = int(w_indptr[-1].item())
-    W = DeviceCSR.from_tensors(w_indptr, w_indices[:nnz], I)
-    return W, (w_vals[:nnz] if nnz else w_vals[:1])
+    return _w_result(w_indptr, w_indices, w_vals)
 
 
 def rp3_build(ctx, Piu, piu_vals, Pui, pui_vals, degree, n_neighbors, normalize):
@@ -488,7 +496,7 @@ def slim_fit(ctx, csc, csc_vals, alpha, l1_ratio, order, n_neighbors, j_start=0,
     block = max(min(SLIM_FIT_WS_BYTES // per_col, n), 1)
     need = int(ctx.lib.el_slim_ws_bytes(U, I, block, n_neighbors))
     given = need if ws_bytes is None else int(ws_bytes)
-    ws = torch.empty(max(given, 1), dtype=torch.uint8, device=dev)
+    ws = _workspace(ctx, given)
     for c0 in range(0, n, block):
         c1 = min(c0 + block, n)
         check(ctx.lib.el_slim_fit(ctx.handle, ctx.stream(), _ptr(csc.indptr, torch.int64), _ptr(csc.indices, torch.int32),
@@ -508,15 +516,11 @@ def slim_w(ctx, idx, val, cnt):
     if idx.shape != (I, N) or val.shape != (I, N):
         raise ValueError(f"column lists must be [{I}, {N}], got {tuple(idx.shape)} / {tuple(val.shape)}")
     need = int(ctx.lib.el_slim_ws_bytes(I, I, 0, N))
-    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=ctx.device)
-    w_indptr = torch.empty(I + 1, dtype=torch.int64, device=ctx.device)
-    w_indices = torch.empty(max(I * N, 1), dtype=torch.int32, device=ctx.device)
-    w_vals = torch.empty(max(I * N, 1), dtype=torch.float32, device=ctx.device)
+    ws = _workspace(ctx, need)
+    w_indptr, w_indices, w_vals = _w_alloc(ctx, I, N)
     check(ctx.lib.el_slim_w(ctx.handle, ctx.stream(), _ptr(idx, torch.int32), _ptr(val, torch.float32), _ptr(cnt, torch.int32), I, N,
                             _ptr(w_indptr), _ptr(w_indices), _ptr(w_vals), C.c_void_p(ws.data_ptr()), need), "el_slim_w")
-    nnz = int(w_indptr[-1].item())
-    W = DeviceCSR.from_tensors(w_indptr, w_indices[:nnz], I)
-    return W, (w_vals[:nnz] if nnz else w_vals[:1])
+    return _w_result(w_indptr, w_indices, w_vals)
 
 
 def slim_build(ctx, csc, csc_vals, alpha, l1_ratio, n_neighbors, seed, exclusion="column", max_iter=SLIM_MAX_ITER, tol=SLIM_TOL):

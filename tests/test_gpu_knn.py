@@ -107,6 +107,47 @@ def test_scoring_on_device_w_matches_restatement(ctx, golden, side, sim, binary)
     assert (idx[:, 6:] == -1).all() and np.isneginf(val[:, 6:]).all()
 
 
+SELECT_I = 1000
+
+
+@pytest.fixture(scope="module")
+def select_case():
+    """Three users with one entry of A each, onto three dense rows of B: strictly ascending in the item index (every element beats
+    the threshold, the buffer compacts in every pass), strictly descending (nothing enters after the first compaction), long runs
+    of equal values (the index decides).  Returns (A, B, preds = scipy's A.dot(B))."""
+    item = np.arange(SELECT_I)
+    rows = np.stack([(item + 1) / 8.0, (SELECT_I - item) / 8.0, ((item // 97) * 7 % 5 + 1) / 4.0]).astype(np.float32)
+    A = sp.csr_matrix((np.array([1.0, 2.0, 0.5], np.float32), np.arange(3), np.arange(4)), shape=(3, 3))
+    B = sp.csr_matrix(rows)
+    assert B.nnz == 3 * SELECT_I
+    return A, B, np.asarray(A.dot(B).toarray(), np.float32)
+
+
+@pytest.mark.parametrize("k", [1, 63, 64, 65, 448])
+def test_running_selection_at_its_capacity_steps(ctx, select_case, k):
+    """The one-wave stream-select of k_knn_score at k = 1, around the step of its capacity from 128 to 256 slots (63, 64, 65) and at
+    448 (512 slots exactly), on the three orders of `select_case`; once with an exclusion row, once with k - 1 candidates, so that
+    every list ends in (-1, -inf).  (k = 10 and 140 on rating data: test_scoring_on_device_w_matches_restatement.)"""
+    from elliot_amd import ops
+    A, B, preds = select_case
+    Ad, Av = ops.DeviceCSR(A.indptr, A.indices, 3, ctx.device), ops.device_values(A.data, ctx.device)
+    Bd, Bv = ops.DeviceCSR(B.indptr, B.indices, SELECT_I, ctx.device), ops.device_values(B.data, ctx.device)
+    rs = np.random.RandomState(k)
+    users = np.arange(3)
+    for kind, per_user in (("excl", 37), ("cand", k - 1)):
+        rows = [np.sort(rs.choice(SELECT_I, size=per_user, replace=False)).astype(np.int32) for _ in users]
+        if kind == "excl":
+            rows = [np.union1d(r, [0, SELECT_I - 1]).astype(np.int32) for r in rows]         # the best item of two of the rows
+        m = (np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64), np.concatenate(rows).astype(np.int32))
+        dm = ops.DeviceCSR(m[0], m[1], SELECT_I, ctx.device)
+        idx, val = ops.knn_score_topk(ctx, Ad, Av, Bd, Bv, 0, 3, k, **{kind: dm})
+        ei, ev = knn_ref.topk(preds, users, k, **{kind: m})
+        assert np.array_equal(idx.cpu().numpy(), ei), kind
+        assert same_bits(val.cpu().numpy(), ev), kind
+        if kind == "cand":
+            assert (ei[:, k - 1] == -1).all() and np.isneginf(ev[:, k - 1]).all()
+
+
 def test_large_catalogue_tiles_build_and_scoring(ctx):
     """120 K items: more than one LDS tile in both kernels (64 KiB of accumulators = 16 K items).  64 sampled columns of W and
     256 sampled users' lists bit-exact against the restatement."""

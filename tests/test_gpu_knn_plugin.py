@@ -161,6 +161,7 @@ def test_save_restore_round_trip(ctx, tmp_path, model_name):
     again = cls(data=data, config=cfg, params=params(neighbors=15, similarity="cosine", meta={"restore": True}))
     again.train()
     assert again.get_recommendations(10)[1] == before
+    assert set(again._model.get_model_state()) == {"_W_data", "_W_indices", "_W_indptr", "_similarity", "_num_neighbors", "_implicit"}
 
 
 def test_reference_pickle_loads_and_recommends(ctx, tmp_path):

@@ -127,3 +127,5 @@ def test_save_restore_round_trip(ctx, tmp_path):
     again = RP3beta(data=data, config=cfg, params=params(neighborhood=15, normalize_similarity=True, meta={"restore": True}))
     again.train()
     assert again.get_recommendations(10)[1] == before
+    assert set(again._model.get_model_state()) == {"_W_data", "_W_indices", "_W_indptr", "_neighborhood", "_alpha", "_beta",
+                                                   "_normalize_similarity"}

@@ -119,17 +119,9 @@ def test_cut_equals_the_golden_w(ctx, golden, n):
     assert fragile <= I // 20
 
 
-def test_w_from_host_lists_is_the_scipy_transpose(ctx):
+def check_w_from_host_lists(ctx, idx, val, cnt):
     from elliot_amd import ops
-    rs = np.random.RandomState(3)
-    I, N = 3000, 24
-    cnt = rs.randint(0, N + 1, I).astype(np.int32)
-    cnt[:5] = [0, N, 1, 0, N]
-    idx = np.zeros((I, N), np.int32)
-    val = rs.uniform(1e-4, 1.0, (I, N)).astype(np.float32)
-    pop = 1.0 / np.arange(1, I + 1)
-    for j in range(I):
-        idx[j, :cnt[j]] = rs.choice(I, cnt[j], replace=False, p=pop / pop.sum())
+    I, N = idx.shape
     idx[:, N - 1][cnt < N] = 2 ** 30                                                         # beyond cnt: never read
     W, Wv = ops.slim_w(ctx, *(torch.from_numpy(a).to(ctx.device) for a in (idx, val, cnt)))
     take = np.arange(N)[None, :] < cnt[:, None]
@@ -139,6 +131,41 @@ def test_w_from_host_lists_is_the_scipy_transpose(ctx):
     assert np.array_equal(W.indptr.cpu().numpy(), E.indptr)
     assert np.array_equal(W.indices[:W.nnz].cpu().numpy(), E.indices)
     assert np.array_equal(bits(Wv[:W.nnz].cpu().numpy()), bits(E.data))
+    return E
+
+
+def test_w_from_host_lists_is_the_scipy_transpose(ctx):
+    rs = np.random.RandomState(3)
+    I, N = 3000, 24
+    cnt = rs.randint(0, N + 1, I).astype(np.int32)
+    cnt[:5] = [0, N, 1, 0, N]
+    idx = np.zeros((I, N), np.int32)
+    val = rs.uniform(1e-4, 1.0, (I, N)).astype(np.float32)
+    pop = 1.0 / np.arange(1, I + 1)
+    for j in range(I):
+        idx[j, :cnt[j]] = rs.choice(I, cnt[j], replace=False, p=pop / pop.sum())
+    check_w_from_host_lists(ctx, idx, val, cnt)
+
+
+def test_w_from_host_lists_is_the_scipy_transpose_beyond_one_rank_pass(ctx):
+    """70 001 targets: one more than the 65 536 one bitmap pass of k_knn_rank covers, so rows of W continue in a second pass at its
+    `base` offset.  Row j's columns are start + t * step modulo I: distinct, since N * step < I; the starts favour the low rows,
+    and the targets from 65 000 on all start at row 7, whose entries therefore lie on both sides of the pass boundary."""
+    rs = np.random.RandomState(4)
+    I, N = 70001, 24
+    cnt = rs.randint(0, N + 1, I).astype(np.int32)
+    cnt[:5] = [0, N, 1, 0, N]
+    cnt[[65535, 65536, I - 1]] = N
+    start = (I * rs.uniform(0, 1, I) ** 3).astype(np.int64)
+    start[65000:] = 7
+    step = rs.randint(1, 2001, I)
+    idx = ((start[:, None] + step[:, None] * np.arange(N)[None, :]) % I).astype(np.int32)
+    idx = np.take_along_axis(idx, rs.uniform(size=(I, N)).argsort(1), 1)                     # the lists are in no column order
+    val = rs.uniform(1e-4, 1.0, (I, N)).astype(np.float32)
+    assert (np.diff(np.sort(idx, 1), axis=1) > 0).all()
+    E = check_w_from_host_lists(ctx, idx, val, cnt)
+    row7 = E.indices[E.indptr[7]:E.indptr[8]]
+    assert (row7 < 65536).sum() > 256 and (row7 >= 65536).sum() > 256                        # more than one stride of the block, twice
 
 
 def check_columns(ops, ctx, R, columns, alpha, l1_ratio, exclusion, expect_lds):

@@ -125,6 +125,8 @@ def test_save_restore_round_trip(ctx, tmp_path):
     again.train()
     assert again.get_recommendations(10)[1] == before
     assert again._model.get_model_state()["_exclusion"] == "column"
+    assert set(again._model.get_model_state()) == {"_W_data", "_W_indices", "_W_indptr", "_l1_ratio", "_alpha", "_neighborhood", "_seed",
+                                                   "_exclusion"}
 
 
 @pytest.mark.parametrize("tag", ["ref_a0.001_l0.001_n10", "ref_a0.01_l0.1_n10"])
