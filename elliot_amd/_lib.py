@@ -118,6 +118,7 @@ class PwmfState(C.Structure):
 
 
 EL_TOPK_ITEMS_UNCHANGED = 0x100
+EL_BEYOND_HIST_DIRECT = 1
 EL_NMF_SCREEN = 0x200
 EL_PW_MSE, EL_PW_MSE_SIGMOID, EL_PW_LOGISTIC = 0, 1, 2
 EL_PW_ADAM, EL_PW_ADAGRAD = 0, 1
@@ -194,6 +195,13 @@ PROTOTYPES = {
                                   C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
     "el_rec_metrics": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, C.c_int64, C.c_int64, C.c_int64, _i64p, _i32p, _f32p,
                                  C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "el_beyond_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "el_beyond_metrics": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, C.c_int64, C.c_int64, C.c_int64, _i64p, _i32p, _f32p,
+                                    C.c_double, C.c_int32, _i64p, _i32p, C.c_int64, C.c_int64, _i32p, C.c_void_p, _f64p, _f64p,
+                                    _f64p, _i32p, _f64p, _f64p, C.c_int32, C.c_void_p, C.c_size_t]),
+    "el_beyond_hist_finish": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, C.c_int64, _i64p, _f64p, C.c_void_p, C.c_size_t]),
+    "el_beyond_entropy": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, C.c_int64, C.c_int64, C.c_int64, _i64p, C.c_int32, C.c_int64,
+                                    _f64p, _f64p, C.c_void_p, C.c_size_t]),
     "el_score_topk_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int]),
     "el_topk_screen_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "el_score_topk": (C.c_int, [C.c_void_p, C.c_void_p, _f32p, _f32p, _f32p, C.c_int64, C.c_int64, C.c_int64,

@@ -13,6 +13,7 @@
 // One wave per user; the per-user rows are reduced by a fixed-shape tree so that the sums are run-to-run identical.
 #include "el_common.h"
 #include "el_topk_common.h"
+#include "el_metrics_tree.h"
 
 #define MET_N 8          // nDCG, Precision, Recall, HR, MAP, MRR, F1, valid
 #define MET_BUF 1024     // LDS gain buffer per wave (kept <= 512 + incoming)
@@ -114,47 +115,9 @@ __global__ __launch_bounds__(256) void k_rec_metrics(const int32_t* __restrict__
     }
 }
 
-// sums over the valid users, fixed shape: G workgroups x contiguous row ranges -> partial[G][8]; then one wave adds the G rows
-__global__ __launch_bounds__(256) void k_metrics_partial(const double* __restrict__ rows, int64_t n, int64_t per, double* __restrict__ part) {
-    __shared__ double sh[256];
-    const int64_t lo = (int64_t)blockIdx.x * per, hi = (lo + per < n) ? lo + per : n;
-    double acc[MET_N];
-#pragma unroll
-    for (int m = 0; m < MET_N; ++m) acc[m] = 0.0;
-    for (int64_t r = lo + threadIdx.x; r < hi; r += 256) {
-        const double v = rows[r * MET_N + 7];
-        if (v != 0.0) {
-#pragma unroll
-            for (int m = 0; m < MET_N; ++m) acc[m] += rows[r * MET_N + m];
-        }
-    }
-    for (int m = 0; m < MET_N; ++m) {
-        sh[threadIdx.x] = acc[m];
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) part[(int64_t)blockIdx.x * MET_N + m] = sh[0];
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(64) void k_metrics_final(const double* __restrict__ part, int G, double* __restrict__ out) {
-    const int m = threadIdx.x;
-    if (m >= MET_N) return;
-    double a = 0.0;
-    for (int g = 0; g < G; ++g) a += part[(int64_t)g * MET_N + m];
-    out[m] += a;
-}
-
-static int met_groups(int64_t n) {
-    int64_t g = (n + 4095) / 4096;
-    return (int)(g < 1 ? 1 : (g > 1024 ? 1024 : g));
-}
-
+// sums over the valid users: the fixed-shape partial / final tree of el_metrics_tree.h, rows gated by column 7
 extern "C" size_t el_rec_metrics_ws_bytes(int64_t n_users) {
-    return n_users <= 0 ? 0 : ((size_t)n_users * MET_N * 8 + (size_t)met_groups(n_users) * MET_N * 8);
+    return n_users <= 0 ? 0 : ((size_t)n_users * MET_N * 8 + met_tree_bytes(n_users, MET_N));
 }
 
 extern "C" int el_rec_metrics(el_ctx* ctx, void* stream, const int32_t* rec_idx, int64_t ld, int64_t u_start, int64_t u_stop,
@@ -174,10 +137,7 @@ extern "C" int el_rec_metrics(el_ctx* ctx, void* stream, const int32_t* rec_idx,
     double* part = (double*)((char*)ws + (size_t)n * MET_N * 8);
     EL_LAUNCH("k_rec_metrics", k_rec_metrics, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, rec_idx, ld, u_start, n, test_indptr,
               test_indices, test_ratings, threshold, (int)cutoff, discount, rows);
-    const int G = met_groups(n);
-    const int64_t per = (n + G - 1) / G;
-    EL_LAUNCH("k_metrics_partial", k_metrics_partial, dim3(G), dim3(256), 0, st, (const double*)rows, n, per, part);
-    EL_LAUNCH("k_metrics_final", k_metrics_final, dim3(1), dim3(64), 0, st, (const double*)part, G, sums);
+    met_tree_sum<MET_N, 7>(st, rows, n, part, sums);
     EL_CHECK_LAUNCH();
     return 0;
 }

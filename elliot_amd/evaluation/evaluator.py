@@ -1,5 +1,7 @@
 """Stand-alone evaluator with the interface of elliot/evaluation/evaluator.py:37-162 for the accuracy
-metrics a latent-factor experiment normally asks for (nDCG, Precision, Recall, HR, MAP, MRR, F1).
+metrics a latent-factor experiment normally asks for (nDCG, Precision, Recall, HR, MAP, MRR, F1) and the
+beyond-accuracy metrics of the reference's default configuration (ItemCoverage, UserCoverage, NumRetrieved, Gini,
+SEntropy, EFD, EPC, ARP, APLT, ACLT, PopREO, PopRSP: evaluation/beyond.py).
 
 Definitions follow the reference:
   relevance          test items with rating >= relevance_threshold            relevance.py:87-96
@@ -8,16 +10,23 @@ Definitions follow the reference:
   Precision / Recall hits / cutoff ; hits / #relevant                         precision.py:66, recall.py:66
   HR, MAP, MRR, F1   hit_rate.py:66, map.py:69-80, mrr.py:63-70, f1.py:56-68
   averaging          over users that have recommendations AND >= 1 relevant test item (ndcg.py:124-125)
-Computation is vectorised over an [n_users, k] item matrix instead of per-user Python loops.  The other
-metric families of the reference (coverage, diversity, novelty, bias, fairness) are out of scope here; inside
-an Elliot process the genuine Evaluator is used instead (recommender/_compat.py).
+Computation is vectorised over an [n_users, k] item matrix instead of per-user Python loops.  The remaining
+metrics of the reference (nDCGRendle2020, MAR, the AUC family, DSC, the rating-error metrics, fairness and the other
+complex_metrics, paired tests) are out of scope here; inside an Elliot process the genuine Evaluator is used instead
+(recommender/_compat.py).
+
+The accuracy metrics average over the users with >= 1 relevant held-out item; the beyond-accuracy metrics see every
+user whose held-out row is non-empty (evaluator.py:121) and average over either population, as their classes do.
 """
 import math
 from types import SimpleNamespace
 
 import numpy as np
 
-SUPPORTED = ("nDCG", "Precision", "Recall", "HR", "MAP", "MRR", "F1")
+from . import beyond
+
+ACCURACY = ("nDCG", "Precision", "Recall", "HR", "MAP", "MRR", "F1")
+SUPPORTED = ACCURACY + beyond.NAMES
 
 
 def _canon(name):
@@ -47,6 +56,10 @@ class Evaluator:
             raise Exception("Cutoff values must be smaller than recommendation list length (top_k)")
         self._rel_threshold = getattr(cfg.evaluation, "relevance_threshold", 0)
         self._metrics = [_canon(m) for m in cfg.evaluation.simple_metrics]
+        self._accuracy = [m for m in self._metrics if m in ACCURACY]
+        self._beyond = [m for m in self._metrics if m in beyond.NAMES]
+        self._item_tables = None
+        self._host_csr = {}
         self._dict_splits = None          # the dict-based form is only built when eval() is handed recommendation dicts
         self._needed_recommendations = cfg.top_k
 
@@ -94,7 +107,8 @@ class Evaluator:
         return data.get_test()
 
     @staticmethod
-    def _split_to_csr(ops, data, split, device):
+    def _split_arrays(data, split):
+        """A {public_user: {public_item: rating}} split as CSR arrays in private ids (what DataSet.split_csr returns)."""
         pu, pi = data.public_users, data.public_items
         U, I = data.num_users, data.num_items
         rows = [[] for _ in range(U)]
@@ -115,26 +129,78 @@ class Evaluator:
             indptr[u + 1] = indptr[u] + len(r)
             cols.extend(c for c, _ in r)
             vals.extend(v for _, v in r)
-        return ops.DeviceTestSet(indptr, np.asarray(cols, dtype=np.int32), np.asarray(vals, dtype=np.float32), device)
+        return indptr, np.asarray(cols, dtype=np.int32), np.asarray(vals, dtype=np.float32)
+
+    @classmethod
+    def _split_to_csr(cls, ops, data, split, device):
+        return ops.DeviceTestSet(*cls._split_arrays(data, split), device)
+
+    def item_tables(self, data):
+        """Popularity, short head and the two novelty tables of the data set (beyond.ItemTables), built once."""
+        if self._item_tables is None:
+            self._item_tables = beyond.ItemTables(data.sp_i_train, data.transactions, data.num_users)
+        return self._item_tables
 
     def eval_device(self, ctx, data, blocks):
         """blocks: iterable of (first_private_user, idx_val, idx_test) with [n, k] int32 device tensors (idx_val may be
-        the same tensor).  Returns the same structure as eval()."""
+        the same tensor).  Returns the same structure as eval().
+
+        The accuracy kernel runs as before.  When a beyond-accuracy metric is asked for, el_beyond_metrics runs beside it
+        into one item histogram (int32[num_items]) and one row of sums per (split, cutoff); the histograms are finished
+        after the last block.  SEntropy needs the finished histogram and therefore a second pass over the lists: only when
+        it is requested the blocks' index tensors are kept alive until then -- users x top_k x 4 bytes per split (400 MB at
+        10 M users x 10)."""
         from .. import ops
         import torch
         sets = self.device_sets(data, ctx.device)
-        acc = {(sp, c): torch.zeros(8, dtype=torch.float64, device=ctx.device)
-               for sp in ("val", "test") if sets[sp] is not None for c in self._k}
+        keys = [(sp, c) for sp in ("val", "test") if sets[sp] is not None for c in self._k]
+        acc = {key: torch.zeros(8, dtype=torch.float64, device=ctx.device) for key in keys}
+        bey = None
+        if self._beyond:
+            from ..recommender.masks import device_masks
+            train = device_masks(data, ctx).train
+            tables = getattr(self, "_dev_tables", None)
+            if tables is None or tables.pop.device != ctx.device:
+                tables = self._dev_tables = ops.DeviceItemTables(self.item_tables(data), ctx.device)
+            bey = {key: (torch.zeros(ops.BEYOND_SUMS, dtype=torch.float64, device=ctx.device),
+                         torch.zeros(tables.num_items, dtype=torch.int32, device=ctx.device)) for key in keys}
+        kept = {"val": [], "test": []} if "SEntropy" in self._beyond else None
         for first, idx_val, idx_test in blocks:
-            for (sp, c), sums in acc.items():
-                ops.rec_metrics(ctx, idx_val if sp == "val" else idx_test, sets[sp], self._rel_threshold, c, u_start=first, sums=sums)
+            for sp, c in keys:
+                idx = idx_val if sp == "val" else idx_test
+                if self._accuracy:
+                    ops.rec_metrics(ctx, idx, sets[sp], self._rel_threshold, c, u_start=first, sums=acc[(sp, c)])
+                if bey is not None:
+                    ops.beyond_metrics(ctx, idx, sets[sp], train, tables, self._rel_threshold, c, u_start=first,
+                                       sums=bey[(sp, c)][0], hist=bey[(sp, c)][1])
+            if kept is not None:
+                for sp in kept:
+                    if sets[sp] is not None:
+                        kept[sp].append((first, idx_val if sp == "val" else idx_test))
+        extra = {}
+        if bey is not None:
+            for (sp, c), (sums, hist) in bey.items():
+                stats, nov = ops.beyond_hist_finish(ctx, hist)
+                ent = torch.zeros(1, dtype=torch.float64, device=ctx.device)
+                if kept is not None:
+                    for first, idx in kept[sp]:
+                        ops.beyond_entropy(ctx, idx, sets[sp], nov, c, u_start=first, total=ent)
+                extra[(sp, c)] = (sums.cpu().numpy(), stats.cpu().numpy(), float(ent.cpu()[0]))
         host = {key: v.cpu().numpy() for key, v in acc.items()}
 
         def means(sp, c):
-            s = host[(sp, c)]
-            if s[7] == 0:
-                return {}
-            return {m: float(s[ops.METRIC_NAMES.index(m)] / s[7]) for m in self._metrics}
+            out = {}
+            if self._accuracy:
+                s = host[(sp, c)]
+                if s[7] == 0:
+                    return {}
+                out = {m: float(s[ops.METRIC_NAMES.index(m)] / s[7]) for m in self._accuracy}
+            if self._beyond:
+                sums, stats, ent = extra[(sp, c)]
+                if sums[0] == 0:
+                    return {}
+                out.update(beyond.finish(self._beyond, sums, int(stats[0]), int(stats[1]), int(stats[2]), ent, data.num_items))
+            return {m: out[m] for m in self._metrics}
 
         res = {}
         for c in self._k:
@@ -146,8 +212,47 @@ class Evaluator:
         return res
 
     # ---------------------------------------------------------------------------------------------
-    def _eval_split(self, recs, split, cutoff):
+    def _eval_split(self, recs, split, cutoff, validation=False):
         """recs: {public_user: [(public_item, score), ...]}"""
+        out = self._eval_accuracy(recs, split, cutoff) if self._accuracy else {}
+        if self._accuracy and not out:
+            return {}
+        if self._beyond:
+            more = self._eval_beyond(recs, cutoff, validation)
+            if not more:
+                return {}
+            out.update(more)
+        return {m: out[m] for m in self._metrics}
+
+    def _host_split_csr(self, validation):
+        if validation not in self._host_csr:
+            data = self._data
+            if hasattr(data, "split_csr"):
+                self._host_csr[validation] = data.split_csr(validation)
+            else:
+                self._host_csr[validation] = self._split_arrays(data, self._test_dict_raw(data, validation))
+        return self._host_csr[validation]
+
+    def _eval_beyond(self, recs, cutoff, validation):
+        """The beyond-accuracy metrics of one split from the recommendation dicts, in NumPy (beyond.numpy_terms)."""
+        data = self._data
+        pu, pi = data.public_users, data.public_items
+        users = [u for u in recs if u in pu]
+        lists = np.full((len(users), cutoff), -1, dtype=np.int64)
+        for r, u in enumerate(users):
+            row = [pi.get(item, -1) for item, _ in recs[u][:cutoff]]
+            lists[r, :len(row)] = row
+        train = data.sp_i_train.tocsr()
+        train.sort_indices()
+        tables = self.item_tables(data)
+        sums, hist, ent = beyond.numpy_terms(lists, np.array([pu[u] for u in users], dtype=np.int64), self._host_split_csr(validation),
+                                             self._rel_threshold, (train.indptr.astype(np.int64), train.indices), tables, cutoff)
+        if sums[0] == 0:
+            return {}
+        n, free, G = beyond.gini_numerator(hist, data.num_items)
+        return beyond.finish(self._beyond, sums, n, free, G, ent, data.num_items)
+
+    def _eval_accuracy(self, recs, split, cutoff):
         users = [u for u in recs if u in split.row]
         if not users:
             return {}
@@ -170,7 +275,7 @@ class Evaluator:
                     gains[r, c] = 2 ** (s - thr + 1) - 1
         nh = hits.sum(1)
         out = {}
-        for m in self._metrics:
+        for m in self._accuracy:
             if m == "nDCG":
                 dcg = gains @ disc
                 v = np.where(dcg > 0, dcg / np.where(idcg > 0, idcg, 1.0), 0.0)
@@ -196,7 +301,7 @@ class Evaluator:
         exactly as evaluator.py:79-92 (a missing validation split mirrors the test results)."""
         res = {}
         for k in self._k:
-            val = self._eval_split(recommendations[0], self._val, k) if self._val else None
+            val = self._eval_split(recommendations[0], self._val, k, validation=True) if self._val else None
             test = self._eval_split(recommendations[1], self._test, k)
             if not val:
                 val = test

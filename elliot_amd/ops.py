@@ -1180,6 +1180,83 @@ def rec_metrics(ctx, rec_idx, test, threshold, cutoff, u_start=0, sums=None, per
     return (sums, rows) if per_user else sums
 
 
+# ------------------------------------------------------------------------------------------
+# beyond-accuracy metrics on the device: coverage, concentration, novelty, popularity bias
+# ------------------------------------------------------------------------------------------
+BEYOND_METRIC_NAMES = ("ItemCoverage", "UserCoverage", "NumRetrieved", "Gini", "SEntropy", "EFD", "EPC", "ARP", "APLT", "ACLT",
+                       "PopREO", "PopRSP")
+BEYOND_SUMS = 18        # el_beyond_metrics' sums (include/elliot_hip.h lists the slots)
+
+
+class DeviceItemTables:
+    """The per-item tables of evaluation/beyond.py::ItemTables in HBM: pop int32, head uint8, efd / epc float64."""
+
+    def __init__(self, tables, device):
+        self.host = tables
+        self.num_items, self.n_head = int(tables.num_items), int(tables.n_head)
+        self.pop = torch.from_numpy(tables.pop.astype(np.int32)).to(device)
+        self.head = torch.from_numpy(tables.head.astype(np.uint8)).to(device)
+        self.efd = torch.from_numpy(np.ascontiguousarray(tables.efd, dtype=np.float64)).to(device)
+        self.epc = torch.from_numpy(np.ascontiguousarray(tables.epc, dtype=np.float64)).to(device)
+
+
+def _beyond_ws(ctx, n_users, n_items):
+    need = int(ctx.lib.el_beyond_ws_bytes(int(n_users), int(n_items)))
+    ws = getattr(ctx, "_beyond_ws", None)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=ctx.device)
+        ctx._beyond_ws = ws
+    return ws
+
+
+def beyond_metrics(ctx, rec_idx, test, train, tables, threshold, cutoff, u_start=0, hist=None, sums=None, per_user=False, direct=False):
+    """First pass of the beyond-accuracy metrics over the users of rec_idx's rows (absolute ids u_start ...): their terms ADDED to
+    `sums` (float64[BEYOND_SUMS]) and their lists to the item histogram `hist` (int32[num_items]); train = the DeviceCSR of the
+    train interactions.  direct=True: one integer add per list entry instead of one per distinct id of a tile."""
+    n, ld = rec_idx.shape
+    I = tables.num_items
+    if sums is None:
+        sums = torch.zeros(BEYOND_SUMS, dtype=torch.float64, device=ctx.device)
+    if hist is None:
+        hist = torch.zeros(I, dtype=torch.int32, device=ctx.device)
+    rows = torch.empty((n, BEYOND_SUMS), dtype=torch.float64, device=ctx.device) if per_user else None
+    ws = _beyond_ws(ctx, n, I)
+    disc = discount_table(cutoff, ctx.device)
+    check(ctx.lib.el_beyond_metrics(ctx.handle, ctx.stream(), _ptr(rec_idx, torch.int32), int(ld), int(u_start), int(u_start + n),
+                                    _ptr(test.indptr, torch.int64), _ptr(test.indices, torch.int32),
+                                    _ptr(test.ratings, torch.float32), float(threshold), int(cutoff),
+                                    _ptr(train.indptr, torch.int64), _ptr(train.indices, torch.int32), int(I), int(tables.n_head),
+                                    _ptr(tables.pop, torch.int32), _ptr(tables.head, torch.uint8), _ptr(tables.efd, torch.float64),
+                                    _ptr(tables.epc, torch.float64), C.c_void_p(disc.data_ptr()), _ptr(hist, torch.int32),
+                                    _ptr(sums, torch.float64), C.c_void_p(rows.data_ptr()) if rows is not None else None,
+                                    _lib.EL_BEYOND_HIST_DIRECT if direct else 0, C.c_void_p(ws.data_ptr()), int(ws.numel())),
+          "el_beyond_metrics")
+    return (sums, hist, rows) if per_user else (sums, hist)
+
+
+def beyond_hist_finish(ctx, hist):
+    """(stats int64[4] = #items in a list, free = sum of the counts, the exact Gini numerator G, 0;  nov float64[I] = -log2(hist / free))"""
+    I = int(hist.shape[0])
+    stats = torch.empty(4, dtype=torch.int64, device=ctx.device)
+    nov = torch.empty(I, dtype=torch.float64, device=ctx.device)
+    ws = _beyond_ws(ctx, 0, I)
+    check(ctx.lib.el_beyond_hist_finish(ctx.handle, ctx.stream(), _ptr(hist, torch.int32), I, _ptr(stats, torch.int64),
+                                        _ptr(nov, torch.float64), C.c_void_p(ws.data_ptr()), int(ws.numel())), "el_beyond_hist_finish")
+    return stats, nov
+
+
+def beyond_entropy(ctx, rec_idx, test, nov, cutoff, u_start=0, total=None):
+    """Sum over the users of the block that have a held-out row of (1 / n_u) sum of nov over the list, ADDED to `total` (float64[1])."""
+    n, ld = rec_idx.shape
+    if total is None:
+        total = torch.zeros(1, dtype=torch.float64, device=ctx.device)
+    ws = _beyond_ws(ctx, n, int(nov.shape[0]))
+    check(ctx.lib.el_beyond_entropy(ctx.handle, ctx.stream(), _ptr(rec_idx, torch.int32), int(ld), int(u_start), int(u_start + n),
+                                    _ptr(test.indptr, torch.int64), int(cutoff), int(nov.shape[0]), _ptr(nov, torch.float64),
+                                    _ptr(total, torch.float64), C.c_void_p(ws.data_ptr()), int(ws.numel())), "el_beyond_entropy")
+    return total
+
+
 def topk_screen_stats(ctx):
     """Diagnostics of the last screened score_topk call (el_topk_screen_stats; synchronises): users of the block, records the bf16 pass
     kept for them, users that took the exact fallback."""

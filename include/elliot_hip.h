@@ -1060,6 +1060,57 @@ int el_rec_metrics(el_ctx* ctx, void* stream, const int32_t* rec_idx, int64_t ld
                    double threshold, int32_t cutoff, const double* discount, double* sums, double* per_user,
                    void* ws, size_t ws_bytes);
 
+/* ---- beyond-accuracy metrics from the top-k index tensor -------------------------------
+ * Replaces: the coverage / diversity / novelty / bias metric classes behind Evaluator._process_test_data
+ * (evaluation/evaluator.py:117-147): metrics/coverage/{item_coverage,user_coverage,num_retrieved},
+ * metrics/diversity/gini_index/gini_index.py, metrics/diversity/shannon_entropy/shannon_entropy.py,
+ * metrics/novelty/EFD/efd.py, metrics/novelty/EPC/epc.py, metrics/bias/{arp,aplt,aclt,pop_reo,pop_rsp}, with the
+ * item tables of popularity_utils/popularity.py.  Populations: A = users whose held-out row is non-empty
+ * (evaluator.py:121), R = users of A with an item rated >= threshold.  A list = the ids in [0, n_items) among the first
+ * `cutoff` columns (n_u of them; -1 pads the end).
+ *
+ * el_beyond_metrics, users [u_start, u_stop):
+ *   rec_idx, test CSR, threshold, cutoff, discount   as el_rec_metrics
+ *   train CSR   rows by absolute user id, indices ascending (the exclusion mask of the scoring kernels)
+ *   pop    int32[n_items]  users that hold the item in train               popularity.py:25-29
+ *   head   uint8[n_items]  1 = short head, 0 = long tail; n_head = #1      popularity.py:37-53
+ *   efd    double[n_items] -log2(pop / sum pop) (efd.py), epc double[n_items] 1 - pop / #train users (epc.py)
+ *   hist   int32[n_items], ADDED to: number of lists of users of A that hold the item
+ *   sums   double[18], ADDED to (every integer below is exact in fp64):
+ *            0 |A|   1 |R|   2 #users of A with n_u > 0 (UserCoverage)   3 sum over A of n_u
+ *            4 ARP   sum over A of (sum of pop over the list) / n_u
+ *            5 APLT  sum over A of (tail entries) / n_u          6 ACLT  sum over A of tail entries
+ *            7 NumRetrieved  sum over R of n_u
+ *            8 EFD   sum over R of  sum_r hit(r) discount[r] efd[item_r] / sum_{r < n_u} discount[r];  9 EPC likewise
+ *            10..13 PopRSP over A: list entries in head, in tail; |head - train_u|, |tail - train_u|
+ *            14..17 PopREO over R: relevant list entries in head, in tail; relevant items of the user in head, in tail
+ *                   that are not in train_u
+ *          a user with n_u = 0 adds 0 to every ratio (the reference divides by zero there) and is still counted
+ *   per_user  optional device double[(u_stop-u_start), 18] with the individual rows
+ *   flags  EL_BEYOND_HIST_DIRECT: one integer add per list entry; default: a tile of list entries is sorted in LDS and
+ *          adds once per distinct id (a popular item sits in most lists of a block)
+ * el_beyond_hist_finish: stats int64[4] (overwritten) = #{hist > 0} (ItemCoverage), free = sum hist,
+ *   G = sum_j (2 (j + I - n + 1) - I - 1) c_(j) over the n non-zero counts ascending (gini_index.py:82, its numerator
+ *   before the division by free; Gini = 1 - G / free / (I - 1)), 0;  nov double[n_items] = -log2(hist / free), 0 where
+ *   hist = 0 (shannon_entropy.py:87-88)
+ * el_beyond_entropy: sum double[1], ADDED to: sum over the users of A of (1 / n_u) sum of nov over the list
+ *   (SEntropy = sum / |A|: shannon_entropy.py:90-98 with the two sums exchanged)
+ * fp64 arithmetic, fixed-shape reductions, integer atomics only: the same input gives the same bytes.  cutoff <= 512.
+ * One workspace size serves the three calls.                                                                     */
+enum { EL_BEYOND_HIST_DIRECT = 1 };
+size_t el_beyond_ws_bytes(int64_t n_users, int64_t n_items);
+int el_beyond_metrics(el_ctx* ctx, void* stream, const int32_t* rec_idx, int64_t ld, int64_t u_start, int64_t u_stop,
+                      const int64_t* test_indptr, const int32_t* test_indices, const float* test_ratings,
+                      double threshold, int32_t cutoff, const int64_t* train_indptr, const int32_t* train_indices,
+                      int64_t n_items, int64_t n_head, const int32_t* pop, const unsigned char* head, const double* efd,
+                      const double* epc, const double* discount, int32_t* hist, double* sums, double* per_user,
+                      int32_t flags, void* ws, size_t ws_bytes);
+int el_beyond_hist_finish(el_ctx* ctx, void* stream, const int32_t* hist, int64_t n_items, int64_t* stats, double* nov,
+                          void* ws, size_t ws_bytes);
+int el_beyond_entropy(el_ctx* ctx, void* stream, const int32_t* rec_idx, int64_t ld, int64_t u_start, int64_t u_stop,
+                      const int64_t* test_indptr, int32_t cutoff, int64_t n_items, const double* nov, double* sum,
+                      void* ws, size_t ws_bytes);
+
 /* Fragile-user report (BASELINE.md "fragile near-tie users reported separately").  The reference scores
  * with tf.matmul (BPRMF_batch_model.py:83-84), whose fp32 summation order is unknowable here; the kernels pin the k-ordered
  * fma chain.  Any two fp32 evaluations of <u,i> differ by at most F 2^-23 |u||i|, so a user's top-k SET does not depend on
