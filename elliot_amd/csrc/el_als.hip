@@ -40,8 +40,6 @@ int64_t als_gram_rows_per_slot(int64_t n) {
     return c < ALS_GRAM_MIN_ROWS ? ALS_GRAM_MIN_ROWS : c;
 }
 
-size_t als_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // ---- Gram ----------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_als_gram_part(const double* __restrict__ Y, int64_t n, int F, int64_t chunk,
                                                        double* __restrict__ part) {
@@ -322,7 +320,7 @@ extern "C" size_t el_als_gram_ws_bytes(int64_t n, int32_t F) {
     if (n <= 0 || F <= 0 || F > ALS_MAX_F) return 0;
     const int64_t chunk = als_gram_rows_per_slot(n);
     const int64_t nslots = (n + chunk - 1) / chunk;
-    return als_align((size_t)nslots * (size_t)(F * (F + 1) / 2) * sizeof(double));
+    return el_align256((size_t)nslots * (size_t)(F * (F + 1) / 2) * sizeof(double));
 }
 
 extern "C" int el_als_gram(el_ctx* ctx, void* stream, const double* Y, int64_t n, int32_t F, double* G, void* ws, size_t ws_bytes) {
@@ -349,7 +347,7 @@ extern "C" int el_als_gram(el_ctx* ctx, void* stream, const double* Y, int64_t n
 
 extern "C" size_t el_als_solve_ws_bytes(int64_t n_pieces, int32_t F) {
     if (n_pieces <= 0 || F <= 0 || F > ALS_MAX_F) return 0;
-    return als_align((size_t)n_pieces * (size_t)(F * (F + 1) / 2 + F) * sizeof(double));
+    return el_align256((size_t)n_pieces * (size_t)(F * (F + 1) / 2 + F) * sizeof(double));
 }
 
 extern "C" int el_als_solve(el_ctx* ctx, void* stream, const int64_t* indptr, const int32_t* indices, int64_t n_rows,

@@ -634,21 +634,12 @@ static int launch_rows_apply(const el_bprmf_state& st, const int32_t* u, const i
     return 0;
 }
 
-static unsigned stream_grid(el_ctx* ctx, int64_t n_threads) {
-    int64_t blocks = (n_threads + 255) / 256;
-    const int mult = 8;                                     // workgroups per CU of the streaming passes
-    int64_t cap = (int64_t)ctx->cus * mult;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return (unsigned)blocks;
-}
-
 // TF-dense Adam on the item side alone (Gi, Bi): what is left of the optimiser phase after the fused user-side kernel
 int el_bprmf_apply_items_adam(el_ctx* ctx, hipStream_t s, const el_bprmf_state& st, float lr_t) {
     const float b1 = 0.9f, b2 = 0.999f, eps = 1e-7f;
     const int64_t ni = st.I * (int64_t)st.F;
     // the factors and the bias vector in ONE launch (the bias pass is 8 us of work behind a launch gap of its own)
-    EL_LAUNCH("k_adam_dense_Gi", k_adam_dense_pair, dim3(stream_grid(ctx, ni / 4 + 1)), dim3(256), 0, s, st.Gi, st.gGi, st.mGi, st.vGi, ni, st.Bi,
+    EL_LAUNCH("k_adam_dense_Gi", k_adam_dense_pair, dim3(el_stream_grid(ctx, ni / 4 + 1)), dim3(256), 0, s, st.Gi, st.gGi, st.mGi, st.vGi, ni, st.Bi,
               st.gBi, st.mBi, st.vBi, st.I, lr_t, b1, b2, eps);
     EL_CHECK_LAUNCH();
     return 0;
@@ -696,17 +687,17 @@ int el_bprmf_apply_optimizer(el_ctx* ctx, hipStream_t s, const el_bprmf_state& s
             int sh = -1;
             if ((F4 & (F4 - 1)) == 0) { sh = 0; while ((1 << sh) < F4) ++sh; }
             if (ctx->tuning) {
-                EL_LAUNCH("k_adam_rows_Gu", (k_adam_rows<2, true>), dim3(stream_grid(ctx, nu / 4 + 1)), dim3(256), 0, s, st.Gu, st.gGu_rows, st.uslot,
+                EL_LAUNCH("k_adam_rows_Gu", (k_adam_rows<2, true>), dim3(el_stream_grid(ctx, nu / 4 + 1)), dim3(256), 0, s, st.Gu, st.gGu_rows, st.uslot,
                           st.mGu, st.vGu, nu / 4, F4, sh, step, lr_t, b1, b2, eps);
-                EL_LAUNCH("k_adam_dense_Gi", k_adam_dense_tune, dim3(stream_grid(ctx, ni / 4 + 1)), dim3(256), 0, s, st.Gi, st.gGi, st.mGi, st.vGi, ni, lr_t, b1, b2, eps);
-                EL_LAUNCH("k_adam_dense_Bi", k_adam_dense_tune, dim3(stream_grid(ctx, st.I / 4 + 1)), dim3(256), 0, s, st.Bi, st.gBi, st.mBi, st.vBi, st.I, lr_t, b1, b2, eps);
+                EL_LAUNCH("k_adam_dense_Gi", k_adam_dense_tune, dim3(el_stream_grid(ctx, ni / 4 + 1)), dim3(256), 0, s, st.Gi, st.gGi, st.mGi, st.vGi, ni, lr_t, b1, b2, eps);
+                EL_LAUNCH("k_adam_dense_Bi", k_adam_dense_tune, dim3(el_stream_grid(ctx, st.I / 4 + 1)), dim3(256), 0, s, st.Bi, st.gBi, st.mBi, st.vBi, st.I, lr_t, b1, b2, eps);
                 EL_CHECK_LAUNCH();
                 return 0;
             }
-            EL_LAUNCH("k_adam_rows_Gu", (k_adam_rows<2, false>), dim3(stream_grid(ctx, nu / 4 + 1)), dim3(256), 0, s, st.Gu, st.gGu_rows, st.uslot,
+            EL_LAUNCH("k_adam_rows_Gu", (k_adam_rows<2, false>), dim3(el_stream_grid(ctx, nu / 4 + 1)), dim3(256), 0, s, st.Gu, st.gGu_rows, st.uslot,
                       st.mGu, st.vGu, nu / 4, F4, sh, step, lr_t, b1, b2, eps);
-            EL_LAUNCH("k_adam_dense_Gi", k_adam_dense, dim3(stream_grid(ctx, ni / 4 + 1)), dim3(256), 0, s, st.Gi, st.gGi, st.mGi, st.vGi, ni, lr_t, b1, b2, eps);
-            EL_LAUNCH("k_adam_dense_Bi", k_adam_dense, dim3(stream_grid(ctx, st.I / 4 + 1)), dim3(256), 0, s, st.Bi, st.gBi, st.mBi, st.vBi, st.I, lr_t, b1, b2, eps);
+            EL_LAUNCH("k_adam_dense_Gi", k_adam_dense, dim3(el_stream_grid(ctx, ni / 4 + 1)), dim3(256), 0, s, st.Gi, st.gGi, st.mGi, st.vGi, ni, lr_t, b1, b2, eps);
+            EL_LAUNCH("k_adam_dense_Bi", k_adam_dense, dim3(el_stream_grid(ctx, st.I / 4 + 1)), dim3(256), 0, s, st.Bi, st.gBi, st.mBi, st.vBi, st.I, lr_t, b1, b2, eps);
             EL_CHECK_LAUNCH();
             return 0;
         }
@@ -714,20 +705,20 @@ int el_bprmf_apply_optimizer(el_ctx* ctx, hipStream_t s, const el_bprmf_state& s
             al16(st.mGi) && al16(st.vGi) && al16(st.Bi) && al16(st.gBi) && al16(st.mBi) && al16(st.vBi)) {
             AdamTriple t = {{st.Gu, st.Gi, st.Bi}, {st.gGu, st.gGi, st.gBi}, {st.mGu, st.mGi, st.mBi}, {st.vGu, st.vGi, st.vBi}, {nu, ni, st.I}};
             const int64_t big = nu > ni ? nu : ni;
-            EL_LAUNCH("k_adam_dense3", k_adam_dense3, dim3(stream_grid(ctx, big / 4 + 1)), dim3(256), 0, s, t, lr_t, b1, b2, eps);
+            EL_LAUNCH("k_adam_dense3", k_adam_dense3, dim3(el_stream_grid(ctx, big / 4 + 1)), dim3(256), 0, s, t, lr_t, b1, b2, eps);
             EL_CHECK_LAUNCH();
             return 0;
         }
         if (ctx->tuning) {
-            EL_LAUNCH("k_adam_dense_Gu", k_adam_dense_tune, dim3(stream_grid(ctx, nu / 4 + 1)), dim3(256), 0, s, st.Gu, st.gGu, st.mGu, st.vGu, nu, lr_t, b1, b2, eps);
-            EL_LAUNCH("k_adam_dense_Gi", k_adam_dense_tune, dim3(stream_grid(ctx, ni / 4 + 1)), dim3(256), 0, s, st.Gi, st.gGi, st.mGi, st.vGi, ni, lr_t, b1, b2, eps);
-            EL_LAUNCH("k_adam_dense_Bi", k_adam_dense_tune, dim3(stream_grid(ctx, st.I / 4 + 1)), dim3(256), 0, s, st.Bi, st.gBi, st.mBi, st.vBi, st.I, lr_t, b1, b2, eps);
+            EL_LAUNCH("k_adam_dense_Gu", k_adam_dense_tune, dim3(el_stream_grid(ctx, nu / 4 + 1)), dim3(256), 0, s, st.Gu, st.gGu, st.mGu, st.vGu, nu, lr_t, b1, b2, eps);
+            EL_LAUNCH("k_adam_dense_Gi", k_adam_dense_tune, dim3(el_stream_grid(ctx, ni / 4 + 1)), dim3(256), 0, s, st.Gi, st.gGi, st.mGi, st.vGi, ni, lr_t, b1, b2, eps);
+            EL_LAUNCH("k_adam_dense_Bi", k_adam_dense_tune, dim3(el_stream_grid(ctx, st.I / 4 + 1)), dim3(256), 0, s, st.Bi, st.gBi, st.mBi, st.vBi, st.I, lr_t, b1, b2, eps);
             EL_CHECK_LAUNCH();
             return 0;
         }
-        EL_LAUNCH("k_adam_dense_Gu", k_adam_dense, dim3(stream_grid(ctx, nu / 4 + 1)), dim3(256), 0, s, st.Gu, st.gGu, st.mGu, st.vGu, nu, lr_t, b1, b2, eps);
-        EL_LAUNCH("k_adam_dense_Gi", k_adam_dense, dim3(stream_grid(ctx, ni / 4 + 1)), dim3(256), 0, s, st.Gi, st.gGi, st.mGi, st.vGi, ni, lr_t, b1, b2, eps);
-        EL_LAUNCH("k_adam_dense_Bi", k_adam_dense, dim3(stream_grid(ctx, st.I / 4 + 1)), dim3(256), 0, s, st.Bi, st.gBi, st.mBi, st.vBi, st.I, lr_t, b1, b2, eps);
+        EL_LAUNCH("k_adam_dense_Gu", k_adam_dense, dim3(el_stream_grid(ctx, nu / 4 + 1)), dim3(256), 0, s, st.Gu, st.gGu, st.mGu, st.vGu, nu, lr_t, b1, b2, eps);
+        EL_LAUNCH("k_adam_dense_Gi", k_adam_dense, dim3(el_stream_grid(ctx, ni / 4 + 1)), dim3(256), 0, s, st.Gi, st.gGi, st.mGi, st.vGi, ni, lr_t, b1, b2, eps);
+        EL_LAUNCH("k_adam_dense_Bi", k_adam_dense, dim3(el_stream_grid(ctx, st.I / 4 + 1)), dim3(256), 0, s, st.Bi, st.gBi, st.mBi, st.vBi, st.I, lr_t, b1, b2, eps);
         EL_CHECK_LAUNCH();
         return 0;
     }
@@ -739,18 +730,12 @@ int el_bprmf_apply_optimizer(el_ctx* ctx, hipStream_t s, const el_bprmf_state& s
                    : launch_rows_apply<1, false>(st, u, i, j, B, step, lr, lr_t, s);
     }
     const int64_t nu = st.U * (int64_t)st.F, ni = st.I * (int64_t)st.F;
-    EL_LAUNCH("k_sgd_dense", k_sgd_dense, dim3(stream_grid(ctx, nu)), dim3(256), 0, s, st.Gu, st.gGu, nu, lr);
-    EL_LAUNCH("k_sgd_dense", k_sgd_dense, dim3(stream_grid(ctx, ni)), dim3(256), 0, s, st.Gi, st.gGi, ni, lr);
-    EL_LAUNCH("k_sgd_dense", k_sgd_dense, dim3(stream_grid(ctx, st.I)), dim3(256), 0, s, st.Bi, st.gBi, st.I, lr);
+    EL_LAUNCH("k_sgd_dense", k_sgd_dense, dim3(el_stream_grid(ctx, nu)), dim3(256), 0, s, st.Gu, st.gGu, nu, lr);
+    EL_LAUNCH("k_sgd_dense", k_sgd_dense, dim3(el_stream_grid(ctx, ni)), dim3(256), 0, s, st.Gi, st.gGi, ni, lr);
+    EL_LAUNCH("k_sgd_dense", k_sgd_dense, dim3(el_stream_grid(ctx, st.I)), dim3(256), 0, s, st.Bi, st.gBi, st.I, lr);
     EL_CHECK_LAUNCH();
     return 0;
 }
-
-extern "C" __attribute__((visibility("hidden"))) int el_bprmf_train_step_sorted(el_ctx* ctx, void* stream, const el_bprmf_state* stp, const int32_t* u,
-                                          const int32_t* i, const int32_t* j, int64_t B, float lr, float l_w,
-                                          float l_b, int opt, int32_t step, float lr_t, double* loss_out, void* ws,
-                                          size_t ws_bytes);
-extern "C" size_t el_bprmf_ws_bytes(int64_t B, int64_t U, int64_t I, int32_t F);
 
 extern "C" int el_bprmf_train_step(el_ctx* ctx, void* stream, const el_bprmf_state* stp, const int32_t* u,
                                    const int32_t* i, const int32_t* j, int64_t B, float lr, float l_w, float l_b,
@@ -991,12 +976,25 @@ static int64_t loop_cap(int64_t events, int64_t B) {
     const int64_t want = ((events + B - 1) / B) * B;
     return want < most ? (want < B ? B : want) : most;
 }
-static size_t loop_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct LoopWs {
+    int32_t* bu;         // [3, cap] the sampled triplets: users, positives, negatives
+    float* lr_tab;       // [steps] Adam step sizes
+    LoopCtl* ctl;        // the graph's per-step scalars, in a 256-byte block of their own
+};
+
+static size_t loop_carve(int64_t events, int64_t B, void* base, LoopWs* w) {
+    ElCarve c{(char*)base};
+    w->bu = c.take<int32_t>((size_t)loop_cap(events, B) * 3);
+    w->lr_tab = c.take<float>((size_t)((events + B - 1) / B));
+    w->ctl = (LoopCtl*)c.take<char>(256);
+    return c.off;
+}
 
 extern "C" size_t el_bprmf_train_loop_ws_bytes(int64_t events, int64_t B) {
     if (events <= 0 || B <= 0) return 0;
-    const int64_t steps = (events + B - 1) / B;
-    return loop_align((size_t)loop_cap(events, B) * 12) + loop_align((size_t)steps * 4) + 256;
+    LoopWs w;
+    return loop_carve(events, B, nullptr, &w);
 }
 
 struct LoopGraphKey {
@@ -1063,17 +1061,14 @@ extern "C" int el_bprmf_train_loop(el_ctx* ctx, void* stream, const el_bprmf_sta
     if (int rc = el_bind(ctx)) return rc;
     EL_REQUIRE(stp != nullptr && B >= 1 && events >= 0, "el_bprmf_train_loop: bad arguments");
     if (events == 0) return 0;
-    const size_t need = el_bprmf_train_loop_ws_bytes(events, B);
+    LoopWs w;
+    const size_t need = loop_carve(events, B, loop_ws, &w);
     EL_REQUIRE(loop_ws != nullptr && loop_ws_bytes >= need, "el_bprmf_train_loop: loop workspace too small (%zu < %zu)", loop_ws_bytes, need);
     const bool adam = (opt == EL_OPT_ADAM_TF_DENSE || opt == EL_OPT_ADAM_LAZY);
     EL_REQUIRE(!adam || lr_t_host != nullptr, "el_bprmf_train_loop: lr_t_host is required for the Adam modes");
     hipStream_t s = (hipStream_t)stream;
     const int64_t cap = loop_cap(events, B), steps = (events + B - 1) / B;
-    int32_t* bu = (int32_t*)loop_ws;
-    int32_t* bi = bu + cap;
-    int32_t* bj = bu + 2 * cap;
-    float* lr_tab = (float*)((char*)loop_ws + loop_align((size_t)cap * 12));
-    LoopCtl* ctl = (LoopCtl*)((char*)lr_tab + loop_align((size_t)steps * 4));
+    int32_t *bu = w.bu, *bi = bu + cap, *bj = bu + 2 * cap;
 
     // graph form: small batch (the atomic gradient kernel is what AUTO picks below 2048), TF-dense Adam on a model small
     // enough for the fused three-tensor pass, no per-kernel timing requested
@@ -1093,13 +1088,13 @@ extern "C" int el_bprmf_train_loop(el_ctx* ctx, void* stream, const el_bprmf_sta
         memset(&key, 0, sizeof(key));
         key.st = st;
         key.st.tGu = key.st.tGi = key.st.tBi = nullptr;
-        key.bu = bu, key.cap = cap, key.B = B, key.l_w = l_w, key.l_b = l_b, key.loss_out = loss_out, key.lr_tab = lr_tab, key.ctl = ctl;
+        key.bu = bu, key.cap = cap, key.B = B, key.l_w = l_w, key.l_b = l_b, key.loss_out = loss_out, key.lr_tab = w.lr_tab, key.ctl = w.ctl;
         key.vec = vec ? 1 : 0;
         key.lpt = el_pick_lpt(st.F, vec ? 4 : 1, &key.cpl);
         EL_REQUIRE(key.cpl <= 4, "el_bprmf_train_loop: F=%d too large for this build", st.F);
         key.grid_f = (unsigned)((B * key.lpt + 255) / 256);
         const int64_t big = nu > ni ? nu : ni;
-        key.grid_a = stream_grid(ctx, big / 4 + 1);
+        key.grid_a = el_stream_grid(ctx, big / 4 + 1);
         AdamTriple t = {{st.Gu, st.Gi, st.Bi}, {st.gGu, st.gGi, st.gBi}, {st.mGu, st.mGi, st.mBi}, {st.vGu, st.vGi, st.vBi}, {nu, ni, st.I}};
         if (loop_graph_get(ctx, s, key, t, bi, bj)) use_graph = false;     // capture unavailable: eager path, same results
         else {
@@ -1113,7 +1108,7 @@ extern "C" int el_bprmf_train_loop(el_ctx* ctx, void* stream, const el_bprmf_sta
                 ctx->lr_pinned_cap = (size_t)steps;
             }
             memcpy(ctx->lr_pinned, lr_t_host, (size_t)steps * 4);
-            EL_CHECK_HIP(hipMemcpyAsync(lr_tab, ctx->lr_pinned, (size_t)steps * 4, hipMemcpyHostToDevice, s));
+            EL_CHECK_HIP(hipMemcpyAsync(w.lr_tab, ctx->lr_pinned, (size_t)steps * 4, hipMemcpyHostToDevice, s));
             EL_CHECK_HIP(hipEventRecord(ctx->lr_copied, s));
         }
     }
@@ -1127,7 +1122,7 @@ extern "C" int el_bprmf_train_loop(el_ctx* ctx, void* stream, const el_bprmf_sta
             return rc;
         const int64_t csteps = (cn + B - 1) / B;
         if (use_graph) {
-            hipLaunchKernelGGL(k_loop_ctl_set, dim3(1), dim3(1), 0, s, ctl, cn, (int32_t)k);
+            hipLaunchKernelGGL(k_loop_ctl_set, dim3(1), dim3(1), 0, s, w.ctl, cn, (int32_t)k);
             for (int64_t g = 0; g < csteps; g += LOOP_GRAPH_STEPS) EL_CHECK_HIP(hipGraphLaunch((hipGraphExec_t)ctx->loop_graph_exec, s));
             k += csteps;
             continue;

@@ -993,37 +993,32 @@ struct SortedWs {
 
 // F = 0: the part of the layout the sort needs (el_bprmf_presort does not know the factor count); F > 0: + the partial rows of the cut
 // item segments at the END (the arrays in front of them sit at the same offsets either way)
-static int carve_ws(int64_t B, int64_t U, int64_t I, char* base, SortedWs* w, int F = 0) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base ? base + off : nullptr;
-        off += el_align256(bytes);
-        return p;
-    };
+static int carve_ws(int64_t B, int64_t U, int64_t I, void* base, SortedWs* w, int F = 0) {
+    ElCarve c{(char*)base};
     // users [0, B) and items [B, 3B) share one array each, so that one radix sort of 3B keys (users as u, items as
     // U + item) orders both sides: half the launches of two sorts, and these small sorts are launch-bound
     u32** slots[4] = {&w->keyU_in, &w->valU_in, &w->keyU, &w->valU};
     u32** islots[4] = {&w->keyI_in, &w->valI_in, &w->keyI, &w->valI};
     for (int k = 0; k < 4; ++k) {
-        *slots[k] = (u32*)take((size_t)B * 12);
+        *slots[k] = c.take<u32>((size_t)B * 3);
         *islots[k] = base ? *slots[k] + B : nullptr;
     }
-    w->s = (float*)take((size_t)B * 4);
+    w->s = c.take<float>((size_t)B);
     size_t t1 = 0, t2 = 0;
     u32* np = nullptr;
     if (rocprim::radix_sort_pairs(nullptr, t1, np, np, np, np, (unsigned)(3 * B), 0, el_bits_for(U + I), (hipStream_t)0) != hipSuccess) return 1;
     if (rocprim::radix_sort_pairs(nullptr, t2, np, np, np, np, (unsigned)(2 * B), 0, el_bits_for(I), (hipStream_t)0) != hipSuccess) return 1;
     w->tmp_bytes = t1 > t2 ? t1 : t2;
-    w->tmp = take(w->tmp_bytes);
-    w->rowptr = (int32_t*)take((size_t)(U + 1) * 4);
-    w->hpos = (int32_t*)take((size_t)B * 4);
-    w->split_long = (int32_t*)take((size_t)(2 * (B / 8 + 4) + 4) * 4);
+    w->tmp = c.take<char>(w->tmp_bytes);
+    w->rowptr = c.take<int32_t>((size_t)(U + 1));
+    w->hpos = c.take<int32_t>((size_t)B);
+    w->split_long = c.take<int32_t>((size_t)(2 * (B / 8 + 4) + 4));
     w->part = w->part_b = nullptr;
     if (F > 0) {                                         // (lane groups: at most 2 B / 16 -- item_chunk_for never goes below 16 positions)
-        w->part = (float*)take((size_t)2 * (B / 8 + 1) * (size_t)F * 4);
-        w->part_b = (float*)take((size_t)2 * (B / 8 + 1) * 4);
+        w->part = c.take<float>((size_t)2 * (B / 8 + 1) * (size_t)F);
+        w->part_b = c.take<float>((size_t)2 * (B / 8 + 1));
     }
-    w->total = off;
+    w->total = c.off;
     return 0;
 }
 
@@ -1052,15 +1047,6 @@ extern "C" size_t el_bprmf_ws_bytes(int64_t B, int64_t U, int64_t I, int32_t F) 
 
 // 1: the sorted step sums every gradient row in a fixed order (no floating-point atomics on rows): same batches, same bits
 extern "C" int el_bprmf_deterministic(void) { return 1; }
-
-// defined in el_bpr.hip
-int el_bprmf_apply_optimizer(el_ctx* ctx, hipStream_t s, const el_bprmf_state& st, const int32_t* u, const int32_t* i,
-                             const int32_t* j, int64_t B, float lr, int opt, int32_t step, float lr_t);
-int el_bprmf_check_state(const el_bprmf_state* stp, const int32_t* u, const int32_t* i, const int32_t* j,
-                         double* loss_out, int opt, int32_t step, bool* vec, bool* rows_mode);
-int el_pick_lpt(int F, int vw, int* cpl);
-
-int el_bprmf_apply_items_adam(el_ctx* ctx, hipStream_t s, const el_bprmf_state& st, float lr_t);      // el_bpr.hip
 
 // user side of the step as ONE kernel (el_bprmf_state.Gu_next): rowptr, then segments + Adam over every user row
 static int launch_flush_users(const el_bprmf_state& st, hipStream_t s, int32_t t) {
@@ -1343,7 +1329,7 @@ static int sorted_step(el_ctx* ctx, void* stream, const el_bprmf_state* stp, con
     EL_REQUIRE(B < (1LL << 30), "el_bprmf_train_step_sorted: batch too large");
     const el_bprmf_state st = *stp;
     SortedWs w;
-    EL_REQUIRE(carve_ws(B, st.U, st.I, (char*)ws, &w, st.F) == 0, "el_bprmf_train_step_sorted: rocprim size query failed");
+    EL_REQUIRE(carve_ws(B, st.U, st.I, ws, &w, st.F) == 0, "el_bprmf_train_step_sorted: rocprim size query failed");
     EL_REQUIRE(ws != nullptr && ws_bytes >= w.total, "el_bprmf_train_step_sorted: workspace too small (%zu < %zu)",
                ws_bytes, w.total);
     hipStream_t s = (hipStream_t)stream;
@@ -1425,7 +1411,7 @@ int el_bpr_sorted_cml_grads(el_ctx* ctx, hipStream_t s, const el_bprmf_state& st
                             const int32_t* j, int64_t B, float l_w, float l_b, float* cD, const float* cE, void* ws,
                             size_t ws_bytes) {
     SortedWs w;
-    EL_REQUIRE(carve_ws(B, st.U, st.I, (char*)ws, &w, st.F) == 0, "el_cml_train_step: rocprim size query failed");
+    EL_REQUIRE(carve_ws(B, st.U, st.I, ws, &w, st.F) == 0, "el_cml_train_step: rocprim size query failed");
     EL_REQUIRE(ws != nullptr && ws_bytes >= w.total, "el_cml_train_step: segment workspace too small (%zu < %zu)", ws_bytes, w.total);
     if (int rc = sort_batch(s, w, u, i, j, B, st.U, st.I, false)) return rc;
     SegParams base;
@@ -1455,7 +1441,7 @@ extern "C" int el_bprmf_presort(el_ctx* ctx, void* stream, const int32_t* u, con
     if (int rc = el_bind(ctx)) return rc;
     EL_REQUIRE(u && i && j && B >= 1 && B < (1LL << 30) && U >= 1 && I >= 1, "el_bprmf_presort: bad arguments");
     SortedWs w;
-    EL_REQUIRE(carve_ws(B, U, I, (char*)ws, &w) == 0, "el_bprmf_presort: rocprim size query failed");
+    EL_REQUIRE(carve_ws(B, U, I, ws, &w) == 0, "el_bprmf_presort: rocprim size query failed");
     EL_REQUIRE(ws != nullptr && ws_bytes >= w.total, "el_bprmf_presort: workspace too small (%zu < %zu)", ws_bytes, w.total);
     return sort_batch((hipStream_t)stream, w, u, i, j, B, U, I, true);
 }
@@ -1629,7 +1615,7 @@ extern "C" int el_bprmf_shard_grads(el_ctx* ctx, void* stream, const el_bprmf_st
     const el_bprmf_state st = *stp;
     vec = vec && (((uintptr_t)dU) % 16 == 0);
     SortedWs w;
-    EL_REQUIRE(carve_ws(B, st.U, st.I, (char*)ws, &w, st.F) == 0, "el_bprmf_shard_grads: rocprim size query failed");
+    EL_REQUIRE(carve_ws(B, st.U, st.I, ws, &w, st.F) == 0, "el_bprmf_shard_grads: rocprim size query failed");
     EL_REQUIRE(ws != nullptr && ws_bytes >= w.total, "el_bprmf_shard_grads: workspace too small (%zu < %zu)", ws_bytes, w.total);
     hipStream_t s = (hipStream_t)stream;
     int cpl = 1;
@@ -1696,24 +1682,19 @@ extern "C" int el_bprmf_shard_grads(el_ctx* ctx, void* stream, const el_bprmf_st
     return 0;
 }
 
-static int carve_rows_ws(int64_t n, int64_t n_ids, char* base, u32** kin, u32** vin, u32** kout, u32** vout, void** tmp,
+static int carve_rows_ws(int64_t n, int64_t n_ids, void* base, u32** kin, u32** vin, u32** kout, u32** vout, void** tmp,
                          size_t* tmp_bytes, size_t* total) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base ? base + off : nullptr;
-        off += el_align256(bytes);
-        return p;
-    };
-    *kin = (u32*)take((size_t)n * 4);
-    *vin = (u32*)take((size_t)n * 4);
-    *kout = (u32*)take((size_t)n * 4);
-    *vout = (u32*)take((size_t)n * 4);
+    ElCarve c{(char*)base};
+    *kin = c.take<u32>((size_t)n);
+    *vin = c.take<u32>((size_t)n);
+    *kout = c.take<u32>((size_t)n);
+    *vout = c.take<u32>((size_t)n);
     size_t t1 = 0;
     u32* np = nullptr;
     if (rocprim::radix_sort_pairs(nullptr, t1, np, np, np, np, (unsigned)n, 0, el_bits_for(n_ids), (hipStream_t)0) != hipSuccess) return 1;
     *tmp_bytes = t1;
-    *tmp = take(t1);
-    *total = off;
+    *tmp = c.take<char>(t1);
+    *total = c.off;
     return 0;
 }
 
@@ -1736,7 +1717,7 @@ extern "C" int el_rows_segment_sum(el_ctx* ctx, void* stream, const int32_t* ids
     u32 *kin, *vin, *kout, *vout;
     void* tmp;
     size_t tb, total;
-    EL_REQUIRE(carve_rows_ws(n, n_ids, (char*)ws, &kin, &vin, &kout, &vout, &tmp, &tb, &total) == 0, "el_rows_segment_sum: size query failed");
+    EL_REQUIRE(carve_rows_ws(n, n_ids, ws, &kin, &vin, &kout, &vout, &tmp, &tb, &total) == 0, "el_rows_segment_sum: size query failed");
     EL_REQUIRE(ws != nullptr && ws_bytes >= total, "el_rows_segment_sum: workspace too small (%zu < %zu)", ws_bytes, total);
     hipStream_t s = (hipStream_t)stream;
     EL_LAUNCH("k_iota_keys", k_iota_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ids, n, kin, vin);

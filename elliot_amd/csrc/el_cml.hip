@@ -21,13 +21,6 @@
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 
-int el_pick_lpt(int F, int vw, int* cpl);                                                                       // el_bpr.hip
-int el_bpr_sorted_cml_grads(el_ctx* ctx, hipStream_t s, const el_bprmf_state& st, const int32_t* u, const int32_t* i,
-                            const int32_t* j, int64_t B, float l_w, float l_b, float* cD, const float* cE, void* ws,
-                            size_t ws_bytes);                                                                    // el_bpr_sorted.hip
-int el_bprmf_apply_optimizer(el_ctx* ctx, hipStream_t s, const el_bprmf_state& st, const int32_t* u, const int32_t* i,
-                             const int32_t* j, int64_t B, float lr, int opt, int32_t step, float lr_t);          // el_bpr.hip
-
 namespace {
 
 struct CmlArgs {
@@ -204,8 +197,6 @@ __global__ __launch_bounds__(256) void k_cml_rescore(const float* __restrict__ G
     if (lane == 0) val[r * ld + c] = it >= 0 ? Bi[it] - s : -INFINITY;
 }
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct CmlWs {
     float *D, *E, *Ds, *Es, *cD, *cE;
     void* tmp;
@@ -213,22 +204,17 @@ struct CmlWs {
 };
 
 int carve(int64_t B, int64_t B_all, char* base, CmlWs* w) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base ? base + off : nullptr;
-        off += al256(bytes);
-        return p;
-    };
+    ElCarve c{base};
     float** slots[4] = {&w->D, &w->E, &w->cD, &w->cE};
-    for (auto s : slots) *s = (float*)take((size_t)B * 4);
-    w->Ds = (float*)take((size_t)B_all * 4);
-    w->Es = (float*)take((size_t)B_all * 4);
+    for (auto s : slots) *s = c.take<float>((size_t)B);
+    w->Ds = c.take<float>((size_t)B_all);
+    w->Es = c.take<float>((size_t)B_all);
     size_t t = 0;
     float* np = nullptr;
     if (rocprim::radix_sort_keys(nullptr, t, np, np, (unsigned)B_all, 0, 32, (hipStream_t)0) != hipSuccess) return 1;
     w->tmp_bytes = t;
-    w->tmp = take(t);
-    w->total = off;
+    w->tmp = c.take<char>(t);
+    w->total = c.off;
     return 0;
 }
 

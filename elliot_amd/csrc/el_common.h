@@ -123,6 +123,23 @@ __attribute__((visibility("hidden"))) int el_gemm_f32_x(el_ctx* ctx, void* strea
                                                         float* colsum_part, void* ws, size_t ws_bytes, int* fused);
 // out[c] = sum of part[0 .. P, c] in a fixed order (el_gemm.hip)
 __attribute__((visibility("hidden"))) int el_colsum_finish(void* stream, const float* part, int P, int64_t C, float* out);
+// (el_bpr.hip) lanes per row of the row kernels, the optimiser phase and the argument checks of a BPR step
+int el_pick_lpt(int F, int vw, int* cpl);
+int el_bprmf_apply_optimizer(el_ctx* ctx, hipStream_t s, const el_bprmf_state& st, const int32_t* u, const int32_t* i,
+                             const int32_t* j, int64_t B, float lr, int opt, int32_t step, float lr_t);
+int el_bprmf_apply_items_adam(el_ctx* ctx, hipStream_t s, const el_bprmf_state& st, float lr_t);
+int el_bprmf_check_state(const el_bprmf_state* stp, const int32_t* u, const int32_t* i, const int32_t* j,
+                         double* loss_out, int opt, int32_t step, bool* vec, bool* rows_mode);
+__global__ void k_adam_dense(float* th, float* g, float* m, float* v, int64_t n, float lr_t, float b1, float b2, float eps);
+// (el_bpr_sorted.hip)
+extern "C" __attribute__((visibility("hidden"))) int el_bprmf_train_step_sorted(el_ctx* ctx, void* stream, const el_bprmf_state* stp, const int32_t* u,
+                                          const int32_t* i, const int32_t* j, int64_t B, float lr, float l_w, float l_b, int opt,
+                                          int32_t step, float lr_t, double* loss_out, void* ws, size_t ws_bytes);
+int el_bpr_sorted_cml_grads(el_ctx* ctx, hipStream_t s, const el_bprmf_state& st, const int32_t* u, const int32_t* i, const int32_t* j,
+                            int64_t B, float l_w, float l_b, float* cD, const float* cE, void* ws, size_t ws_bytes);
+// (el_vae.hip) TF dense ApplyAdam; (el_topk_screen.hip) hash of the item tables
+__global__ void k_adam_apply_dense(float* th, float* g, float* m, float* v, int64_t n, float alpha, float b1, float b2, float eps, int zero_g);
+__global__ void k_items_hash(const float* __restrict__ Gi, const float* __restrict__ Bi, int64_t n_g, int64_t n_b, unsigned long long* ctl);
 
 #define EL_CHECK_HIP(expr)                                                                \
     do {                                                                                  \
@@ -172,6 +189,25 @@ typedef unsigned int u32;
 
 // ---- workspace carving (host) -------------------------------------------------------
 static inline size_t el_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// Lays buffers out one behind the other from `base`.  A workspace's layout function is written once with it: called with a
+// null base it only measures (that is the *_ws_bytes query), called with the caller's pointer it hands the buffers out.
+// A layout nested in another takes the outer ElCarve by reference.
+struct ElCarve {
+    char* base;
+    size_t off = 0;
+    // `count` elements of T; the next buffer starts `align` (a power of two) bytes aligned behind them
+    template <class T>
+    T* take(size_t count, size_t align = 256) {
+        T* p = base ? (T*)(base + off) : nullptr;
+        off += (count * sizeof(T) + align - 1) & ~(align - 1);
+        return p;
+    }
+};
+// blocks of 256 threads of a streaming pass over n threads' work: at most eight workgroups per CU
+static inline unsigned el_stream_grid(el_ctx* ctx, int64_t n) {
+    const int64_t blocks = (n + 255) / 256, cap = (int64_t)ctx->cus * 8;
+    return (unsigned)(blocks < 1 ? 1 : (blocks < cap ? blocks : cap));
+}
 // the smallest power of two >= x
 static inline int el_pow2(int x) {
     int v = 1;

@@ -26,7 +26,6 @@
 
 #define SPMM_CH 512
 
-int el_pick_lpt(int F, int vw, int* cpl);      // el_bpr.hip
 
 struct SpmmParams {
     const int64_t* indptr;     // [N + 1]
@@ -240,10 +239,24 @@ extern "C" int el_spmm_csr_f32(el_ctx* ctx, void* stream, const el_graph_csr* g,
     return spmm_launch((hipStream_t)stream, p);
 }
 
+struct LightgcnWs {
+    float* T;           // [U + I, F] the result (it replaces Gu / Gi at the end) -- and the running sum
+    float* P[2];        // the layers' ping-pong tables: one from two layers, both from three
+};
+
+static size_t lightgcn_carve(int64_t U, int64_t I, int F, int n_layers, void* base, LightgcnWs* w) {
+    ElCarve c{(char*)base};
+    const size_t tab = (size_t)(U + I) * F;
+    w->T = n_layers >= 1 ? c.take<float>(tab) : nullptr;
+    w->P[0] = n_layers >= 2 ? c.take<float>(tab) : nullptr;
+    w->P[1] = n_layers >= 3 ? c.take<float>(tab) : nullptr;
+    return c.off;
+}
+
 extern "C" size_t el_lightgcn_ws_bytes(int64_t U, int64_t I, int32_t F, int32_t n_layers) {
     if (U < 0 || I < 0 || F < 1 || n_layers < 0) return 0;
-    const size_t tab = (((size_t)(U + I) * F * 4) + 255) & ~(size_t)255;
-    return n_layers == 0 ? 0 : (n_layers == 1 ? tab : (n_layers == 2 ? 2 * tab : 3 * tab));
+    LightgcnWs w;
+    return lightgcn_carve(U, I, F, n_layers, nullptr, &w);
 }
 
 // [Gu; Gi] <- mean_k alpha_k L^k [Gu; Gi], alpha_0 = 1, alpha_k = 1 / (1 + k)   (LightGCN_model.py:68-94), in place
@@ -254,33 +267,31 @@ extern "C" int el_lightgcn_propagate(el_ctx* ctx, void* stream, const el_graph_c
     EL_REQUIRE(Gu && Gi && n_layers >= 0 && n_layers <= 16, "el_lightgcn_propagate: bad arguments");
     if (n_layers == 0) return 0;                               // mean of the one-element stack [E * 1]
     const int64_t U = g->n0, I = g->N - g->n0;
-    const size_t need = el_lightgcn_ws_bytes(U, I, F, n_layers);
+    LightgcnWs w;
+    const size_t need = lightgcn_carve(U, I, F, n_layers, ws, &w);
     EL_REQUIRE(ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0, "el_lightgcn_propagate: workspace too small (%zu < %zu)", ws_bytes, need);
     EL_REQUIRE((((uintptr_t)Gu | (uintptr_t)Gi | (uintptr_t)g->part) & 15) == 0, "el_lightgcn_propagate: tables must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    const size_t tab = (((size_t)(U + I) * F * 4) + 255) & ~(size_t)255;
-    float* T = (float*)ws;                                     // the result (it replaces Gu / Gi at the end) -- and the running sum
-    float* P[2] = {n_layers >= 2 ? (float*)((char*)ws + tab) : nullptr, n_layers >= 3 ? (float*)((char*)ws + 2 * tab) : nullptr};
     for (int k = 1; k <= n_layers; ++k) {
         SpmmParams p;
         spmm_fill(p, g, F);
-        const float* in0 = k == 1 ? Gu : P[(k - 2) % (n_layers >= 3 ? 2 : 1)];
+        const float* in0 = k == 1 ? Gu : w.P[(k - 2) % (n_layers >= 3 ? 2 : 1)];
         p.X0 = in0, p.X1 = k == 1 ? Gi : in0 + (size_t)U * F;
         p.S0 = Gu, p.S1 = Gi;
         p.first = k == 1, p.last = k == n_layers;
         p.alpha = (float)(1.0 / (1.0 + (double)k));            // (Python float 1 / (1 + k), cast to fp32 at the multiplication)
         p.n_terms = (float)(n_layers + 1);
-        p.ACC = T;
+        p.ACC = w.T;
         if (!p.last) {
-            float* out = P[(k - 1) % (n_layers >= 3 ? 2 : 1)];
+            float* out = w.P[(k - 1) % (n_layers >= 3 ? 2 : 1)];
             p.Y0 = out, p.Y1 = out + (size_t)U * F;
         } else {
-            p.O0 = T, p.O1 = T + (size_t)U * F;
+            p.O0 = w.T, p.O1 = w.T + (size_t)U * F;
         }
         if (int rc = spmm_launch(s, p)) return rc;
     }
-    EL_CHECK_HIP(hipMemcpyAsync(Gu, T, (size_t)U * F * 4, hipMemcpyDeviceToDevice, s));
-    EL_CHECK_HIP(hipMemcpyAsync(Gi, T + (size_t)U * F, (size_t)I * F * 4, hipMemcpyDeviceToDevice, s));
+    EL_CHECK_HIP(hipMemcpyAsync(Gu, w.T, (size_t)U * F * 4, hipMemcpyDeviceToDevice, s));
+    EL_CHECK_HIP(hipMemcpyAsync(Gi, w.T + (size_t)U * F, (size_t)I * F * 4, hipMemcpyDeviceToDevice, s));
     return 0;
 }
 

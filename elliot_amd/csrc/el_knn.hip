@@ -257,12 +257,29 @@ __global__ __launch_bounds__(64) void k_knn_score(KnnScore p) {
 
 int knn_build_cap(int N) { return el_pow2(2 * N + KNN_BUILD_THREADS); }
 
+struct KnnWs {          // the workspace of el_knn_build: KnnBuild's nrm, lcnt, rowcnt [n] and lx, lv [n, N], then the list-to-CSR arrays
+    int64_t* nrm;
+    int32_t *lcnt, *rowcnt, *lx;
+    float* lv;
+    KnnCsrWs csr;
+};
+size_t knn_carve(int64_t n, int N, void* base, KnnWs* w) {
+    ElCarve c{(char*)base};
+    w->nrm = c.take<int64_t>((size_t)n);
+    w->lcnt = c.take<int32_t>((size_t)n);
+    w->rowcnt = c.take<int32_t>((size_t)n);
+    w->lx = c.take<int32_t>((size_t)n * N);
+    w->lv = c.take<float>((size_t)n * N);
+    w->csr = el_knn_csr_carve(c, n, N);
+    return c.off;
+}
+
 }  // namespace
 
 extern "C" size_t el_knn_ws_bytes(int64_t n, int32_t n_neighbors) {
     if (n <= 0 || n_neighbors <= 0) return 0;
-    const int64_t N = n_neighbors < n ? n_neighbors : n;
-    return el_align256(n * 8) + el_align256(n * 4) * 2 + el_align256(n * N * 4) * 2 + el_knn_csr_ws_bytes(n, (int)N);
+    KnnWs w;
+    return knn_carve(n, (int)(n_neighbors < n ? n_neighbors : n), nullptr, &w);
 }
 
 extern "C" int el_knn_build(el_ctx* ctx, void* stream, const int64_t* p_indptr, const int32_t* p_indices, const int32_t* p_vals,
@@ -285,17 +302,12 @@ extern "C" int el_knn_build(el_ctx* ctx, void* stream, const int64_t* p_indptr, 
     EL_REQUIRE(bound < 4.0e18, "el_knn_build: max degree %lld x max |r|^2 %lld overflows the int64 accumulator",
                (long long)max_deg, (long long)max_abs * max_abs);
     const bool acc64 = bound > 2147483647.0;
-    EL_REQUIRE(ws != nullptr && ws_bytes >= el_knn_ws_bytes(n, n_neighbors), "el_knn_build: workspace too small (need %zu bytes)",
-               el_knn_ws_bytes(n, n_neighbors));
+    KnnWs w;
+    const size_t need = knn_carve(n, N, ws, &w);
+    EL_REQUIRE(ws != nullptr && ws_bytes >= need, "el_knn_build: workspace too small (need %zu bytes)", need);
     hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)ws;
-    int64_t* nrm = (int64_t*)w;      w += el_align256(n * 8);
-    int32_t* lcnt = (int32_t*)w;     w += el_align256(n * 4);
-    int32_t* rowcnt = (int32_t*)w;   w += el_align256(n * 4);
-    int32_t* lx = (int32_t*)w;       w += el_align256((size_t)n * N * 4);
-    float* lv = (float*)w;           w += el_align256((size_t)n * N * 4);
-    EL_CHECK_HIP(hipMemsetAsync(rowcnt, 0, (size_t)n * 4, st));
-    EL_LAUNCH("k_knn_norms", k_knn_norms, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p_indptr, p_vals, n, nrm);
+    EL_CHECK_HIP(hipMemsetAsync(w.rowcnt, 0, (size_t)n * 4, st));
+    EL_LAUNCH("k_knn_norms", k_knn_norms, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p_indptr, p_vals, n, w.nrm);
     EL_CHECK_LAUNCH();
     KnnBuild p;
     p.pp = p_indptr, p.pi = p_indices, p.pv = p_vals;
@@ -303,7 +315,7 @@ extern "C" int el_knn_build(el_ctx* ctx, void* stream, const int64_t* p_indptr, 
     p.n = n, p.N = N, p.sim = sim, p.inv_s2 = 1.0 / ((double)scale * scale);
     p.tile = KNN_TILE_BYTES / (acc64 ? 8 : 4);
     p.cap = knn_build_cap(N);
-    p.nrm = nrm, p.lx = lx, p.lv = lv, p.lcnt = lcnt, p.rowcnt = rowcnt;
+    p.nrm = w.nrm, p.lx = w.lx, p.lv = w.lv, p.lcnt = w.lcnt, p.rowcnt = w.rowcnt;
     const size_t lds = (size_t)p.cap * 8 + KNN_TILE_BYTES;
     if (acc64) {
         EL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_knn_topn<unsigned long long>),
@@ -315,7 +327,7 @@ extern "C" int el_knn_build(el_ctx* ctx, void* stream, const int64_t* p_indptr, 
         EL_LAUNCH("k_knn_topn", k_knn_topn<int>, dim3((unsigned)n), dim3(KNN_BUILD_THREADS), lds, st, p);
     }
     EL_CHECK_LAUNCH();
-    return el_knn_csr_launch(st, lx, lv, lcnt, n, N, rowcnt, w_indptr, w_indices, w_vals, w);
+    return el_knn_csr_launch(st, w.lx, w.lv, w.lcnt, n, N, w.rowcnt, w_indptr, w_indices, w_vals, w.csr);
 }
 
 extern "C" int el_knn_score_topk(el_ctx* ctx, void* stream, const int64_t* a_indptr, const int32_t* a_indices, const float* a_vals,

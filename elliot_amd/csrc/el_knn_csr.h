@@ -5,7 +5,7 @@
 //   k_knn_scan   rowcnt -> indptr, cursor
 //   k_knn_place  every list entry to its row (arbitrary order inside the row)
 //   k_knn_rank   orders each row by column
-//   el_knn_csr_launch  scan, place and rank on a workspace of el_knn_csr_ws_bytes
+//   el_knn_csr_launch  scan, place and rank on the workspace of el_knn_csr_carve
 #pragma once
 #include "el_common.h"
 
@@ -128,21 +128,18 @@ struct KnnCsrWs {
     float* tv;           // [n, N]
 };
 
-size_t el_knn_csr_ws_bytes(int64_t n, int N) { return el_align256((size_t)n * 8) + el_align256((size_t)n * N * 4) * 2; }
-
-KnnCsrWs el_knn_csr_carve(void* ws, int64_t n, int N) {
-    char* w = (char*)ws;
+// the only description of that workspace; callers nest it at the end of their own layout
+KnnCsrWs el_knn_csr_carve(ElCarve& a, int64_t n, int N) {
     KnnCsrWs c;
-    c.cursor = (int64_t*)w;   w += el_align256((size_t)n * 8);
-    c.tc = (int32_t*)w;       w += el_align256((size_t)n * N * 4);
-    c.tv = (float*)w;
+    c.cursor = a.take<int64_t>((size_t)n);
+    c.tc = a.take<int32_t>((size_t)n * N);
+    c.tv = a.take<float>((size_t)n * N);
     return c;
 }
 
-// lists + filled rowcnt -> W (w_indptr [n + 1], w_indices / w_vals [n * N]); ws: el_knn_csr_ws_bytes(n, N)
+// lists + filled rowcnt -> W (w_indptr [n + 1], w_indices / w_vals [n * N]); c: el_knn_csr_carve(.., n, N)
 int el_knn_csr_launch(hipStream_t st, const int32_t* lx, const float* lv, const int32_t* lcnt, int64_t n, int N,
-                      const int32_t* rowcnt, int64_t* w_indptr, int32_t* w_indices, float* w_vals, void* ws) {
-    const KnnCsrWs c = el_knn_csr_carve(ws, n, N);
+                      const int32_t* rowcnt, int64_t* w_indptr, int32_t* w_indices, float* w_vals, const KnnCsrWs& c) {
     EL_LAUNCH("k_knn_scan", k_knn_scan, dim3(1), dim3(1024), 0, st, rowcnt, n, w_indptr, c.cursor);
     EL_CHECK_LAUNCH();
     EL_LAUNCH("k_knn_place", k_knn_place, dim3((unsigned)((n * N + 255) / 256)), dim3(256), 0, st, lx, lv, lcnt, n, N, c.cursor, c.tc,

@@ -117,7 +117,8 @@ __global__ __launch_bounds__(256) void k_rec_metrics(const int32_t* __restrict__
 
 // sums over the valid users: the fixed-shape partial / final tree of el_metrics_tree.h, rows gated by column 7
 extern "C" size_t el_rec_metrics_ws_bytes(int64_t n_users) {
-    return n_users <= 0 ? 0 : ((size_t)n_users * MET_N * 8 + met_tree_bytes(n_users, MET_N));
+    MetWs w;
+    return n_users <= 0 ? 0 : met_carve(n_users, MET_N, nullptr, &w);
 }
 
 extern "C" int el_rec_metrics(el_ctx* ctx, void* stream, const int32_t* rec_idx, int64_t ld, int64_t u_start, int64_t u_stop,
@@ -131,13 +132,13 @@ extern "C" int el_rec_metrics(el_ctx* ctx, void* stream, const int32_t* rec_idx,
     EL_REQUIRE(rec_idx && test_indptr && test_indices && discount && sums, "el_rec_metrics: null pointer");
     EL_REQUIRE(cutoff >= 1 && cutoff <= MET_MAXCUT && (int64_t)cutoff <= ld, "el_rec_metrics: cutoff %d unsupported (1..%d, <= ld)", cutoff,
                MET_MAXCUT);
-    EL_REQUIRE(ws != nullptr && ws_bytes >= el_rec_metrics_ws_bytes(n), "el_rec_metrics: workspace too small");
+    MetWs w;
+    EL_REQUIRE(ws != nullptr && ws_bytes >= met_carve(n, MET_N, ws, &w), "el_rec_metrics: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    double* rows = per_user ? per_user : (double*)ws;
-    double* part = (double*)((char*)ws + (size_t)n * MET_N * 8);
+    double* rows = per_user ? per_user : w.rows;
     EL_LAUNCH("k_rec_metrics", k_rec_metrics, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, rec_idx, ld, u_start, n, test_indptr,
               test_indices, test_ratings, threshold, (int)cutoff, discount, rows);
-    met_tree_sum<MET_N, 7>(st, rows, n, part, sums);
+    met_tree_sum<MET_N, 7>(st, rows, n, w.part, sums);
     EL_CHECK_LAUNCH();
     return 0;
 }

@@ -285,29 +285,23 @@ struct BeyWs {
     size_t tmp_bytes, total;
 };
 
-int bey_carve(int64_t I, char* base, BeyWs* w) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base ? base + off : nullptr;
-        off += el_align256(bytes);
-        return p;
-    };
-    w->sorted = (u32*)take((size_t)I * 4);
+int bey_carve(int64_t I, void* base, BeyWs* w) {
+    ElCarve c{(char*)base};
+    w->sorted = c.take<u32>((size_t)I);
     size_t t = 0;
     u32* np = nullptr;
     if (rocprim::radix_sort_keys(nullptr, t, np, np, (unsigned)I, 0, 32, (hipStream_t)0) != hipSuccess) return 1;
     w->tmp_bytes = t;
-    w->tmp = take(t);
-    w->total = off;
+    w->tmp = c.take<char>(t);
+    w->total = c.off;
     return 0;
 }
-
-size_t bey_users_bytes(int64_t n) { return n <= 0 ? 0 : (size_t)n * BEY_N * 8 + met_tree_bytes(n, BEY_N); }
 
 }  // namespace
 
 extern "C" size_t el_beyond_ws_bytes(int64_t n_users, int64_t n_items) {
-    size_t need = bey_users_bytes(n_users);
+    MetWs m;
+    size_t need = n_users <= 0 ? 0 : met_carve(n_users, BEY_N, nullptr, &m);
     if (n_items > 0 && n_items < (1LL << 31)) {
         BeyWs w;
         if (bey_carve(n_items, nullptr, &w)) return 0;
@@ -333,15 +327,15 @@ extern "C" int el_beyond_metrics(el_ctx* ctx, void* stream, const int32_t* rec_i
                BEY_MAXCUT);
     EL_REQUIRE(n_items >= 1 && n_items < (1LL << 31) && n_head >= 0 && n_head <= n_items, "el_beyond_metrics: bad item counts");
     EL_REQUIRE(n < (1LL << 31), "el_beyond_metrics: more than 2^31 users in one block");
-    EL_REQUIRE(ws != nullptr && ws_bytes >= bey_users_bytes(n), "el_beyond_metrics: workspace too small");
+    MetWs m;
+    EL_REQUIRE(ws != nullptr && ws_bytes >= met_carve(n, BEY_N, ws, &m), "el_beyond_metrics: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     BeyArgs a;
     a.rec = rec_idx, a.ld = ld, a.u_start = u_start, a.n = n;
     a.tp = test_indptr, a.ti = test_indices, a.tr = test_ratings, a.thr = threshold, a.cutoff = (int)cutoff;
     a.qp = train_indptr, a.qi = train_indices, a.I = n_items, a.n_head = n_head;
     a.pop = pop, a.head = head, a.efd = efd, a.epc = epc, a.disc = discount, a.hist = hist;
-    a.rows = per_user ? per_user : (double*)ws;
-    double* part = (double*)((char*)ws + (size_t)n * BEY_N * 8);
+    a.rows = per_user ? per_user : m.rows;
     const dim3 grid((unsigned)((n + 3) / 4));
     if (flags & EL_BEYOND_HIST_DIRECT) {
         EL_LAUNCH("k_beyond_users", (k_beyond_users<true>), grid, dim3(256), 0, st, a);
@@ -351,7 +345,7 @@ extern "C" int el_beyond_metrics(el_ctx* ctx, void* stream, const int32_t* rec_i
         EL_LAUNCH("k_beyond_hist", k_beyond_hist, dim3((unsigned)tiles), dim3(256), 0, st, rec_idx, ld, u_start, n, test_indptr, (int)cutoff,
                   (int32_t)n_items, hist);
     }
-    met_tree_sum<BEY_N, -1>(st, a.rows, n, part, sums);
+    met_tree_sum<BEY_N, -1>(st, a.rows, n, m.part, sums);
     EL_CHECK_LAUNCH();
     return 0;
 }
@@ -362,7 +356,7 @@ extern "C" int el_beyond_hist_finish(el_ctx* ctx, void* stream, const int32_t* h
     EL_REQUIRE(hist && stats && nov, "el_beyond_hist_finish: null pointer");
     EL_REQUIRE(n_items >= 1 && n_items < (1LL << 31), "el_beyond_hist_finish: bad item count");
     BeyWs w;
-    EL_REQUIRE(bey_carve(n_items, (char*)ws, &w) == 0, "el_beyond_hist_finish: rocprim size query failed");
+    EL_REQUIRE(bey_carve(n_items, ws, &w) == 0, "el_beyond_hist_finish: rocprim size query failed");
     EL_REQUIRE(ws != nullptr && ws_bytes >= w.total, "el_beyond_hist_finish: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     EL_CHECK_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(int64_t), st));
@@ -391,10 +385,10 @@ extern "C" int el_beyond_entropy(el_ctx* ctx, void* stream, const int32_t* rec_i
     EL_REQUIRE(cutoff >= 1 && cutoff <= BEY_MAXCUT && (int64_t)cutoff <= ld, "el_beyond_entropy: cutoff %d unsupported (1..%d, <= ld)", cutoff,
                BEY_MAXCUT);
     EL_REQUIRE(n_items >= 1 && n_items < (1LL << 31), "el_beyond_entropy: bad item count");
-    EL_REQUIRE(ws != nullptr && ws_bytes >= (size_t)n * 8 + met_tree_bytes(n, 1), "el_beyond_entropy: workspace too small");
+    MetWs m;
+    EL_REQUIRE(ws != nullptr && ws_bytes >= met_carve(n, 1, ws, &m), "el_beyond_entropy: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    double* rows = (double*)ws;
-    double* part = rows + n;
+    double *rows = m.rows, *part = m.part;
     EL_LAUNCH("k_beyond_entropy", k_beyond_entropy, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, rec_idx, ld, u_start, n, test_indptr,
               (int)cutoff, (int32_t)n_items, nov, rows);
     met_tree_sum<1, -1>(st, rows, n, part, sum);

@@ -46,10 +46,18 @@ static inline int met_groups(int64_t n) {
     return (int)(g < 1 ? 1 : (g > 1024 ? 1024 : g));
 }
 
-// bytes of the partial rows behind the n per-user rows of a workspace
-static inline size_t met_tree_bytes(int64_t n, int W) { return (size_t)met_groups(n) * W * 8; }
+// the workspace of a metric call: the n per-user rows and, straight behind them (neither block is rounded), the partial rows
+struct MetWs {
+    double *rows, *part;
+};
+static inline size_t met_carve(int64_t n, int W, void* base, MetWs* w) {
+    ElCarve c{(char*)base};
+    w->rows = c.take<double>((size_t)n * W, 8);
+    w->part = c.take<double>((size_t)met_groups(n) * W, 8);
+    return c.off;
+}
 
-// sums[0 .. W) += column sums of rows[n, W]; part = met_tree_bytes(n, W) bytes of scratch
+// sums[0 .. W) += column sums of rows[n, W]; part = MetWs::part
 template <int W, int VALID>
 static inline int met_tree_sum(hipStream_t st, const double* rows, int64_t n, double* part, double* sums) {
     const int G = met_groups(n);

@@ -181,10 +181,26 @@ __global__ void k_mt_chase(const int4* __restrict__ cand, int64_t W, int64_t n, 
 
 static int64_t mt_words_for(int64_t n) { return 16 * n + 8 * MT_N; }
 
+struct MtWs {
+    u32* words;          // [W] generated words
+    int4* cand;          // [W] the sample each word would start
+    u32* backup;         // [MT_N + 1] the generator state before the call
+    int64_t* result;     // [2] consumed words, samples written
+};
+
+static size_t mt_carve(int64_t W, void* base, MtWs* w) {
+    ElCarve c{(char*)base};
+    w->words = c.take<u32>((size_t)W);
+    w->cand = c.take<int4>((size_t)W);
+    w->backup = c.take<u32>(MT_N + 1);
+    w->result = c.take<int64_t>(2);
+    return c.off;
+}
+
 extern "C" size_t el_bpr_sample_mt19937_ws_bytes(int64_t n) {
     if (n <= 0) return 0;
-    const int64_t W = mt_words_for(n);
-    return el_align256((size_t)W * 4) + el_align256((size_t)W * 16) + el_align256((MT_N + 1) * 4) + el_align256(16);
+    MtWs w;
+    return mt_carve(mt_words_for(n), nullptr, &w);
 }
 
 extern "C" int el_bpr_sample_mt19937(el_ctx* ctx, void* stream, uint32_t* mt_state, const int64_t* lists_indptr,
@@ -198,27 +214,23 @@ extern "C" int el_bpr_sample_mt19937(el_ctx* ctx, void* stream, uint32_t* mt_sta
     if (n <= 0) return 0;
     EL_REQUIRE(n <= (1LL << 26), "el_bpr_sample_mt19937: at most 2^26 samples per call");
     const int64_t W = mt_words_for(n);
-    EL_REQUIRE(ws != nullptr && ws_bytes >= el_bpr_sample_mt19937_ws_bytes(n), "el_bpr_sample_mt19937: workspace too small");
-    char* base = (char*)ws;
-    u32* words = (u32*)base;
-    int4* cand = (int4*)(base + el_align256((size_t)W * 4));
-    u32* backup = (u32*)(base + el_align256((size_t)W * 4) + el_align256((size_t)W * 16));
-    int64_t* result = (int64_t*)((char*)backup + el_align256((MT_N + 1) * 4));
+    MtWs w;
+    EL_REQUIRE(ws != nullptr && ws_bytes >= mt_carve(W, ws, &w), "el_bpr_sample_mt19937: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    EL_CHECK_HIP(hipMemcpyAsync(backup, mt_state, (MT_N + 1) * 4, hipMemcpyDeviceToDevice, s));
-    EL_LAUNCH("k_mt_generate", k_mt_generate, dim3(1), dim3(256), 0, s, mt_state, words, W, (int64_t)0, (const u32*)backup);
-    EL_LAUNCH("k_mt_candidates", k_mt_candidates, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, s, (const u32*)words, W,
-              lists_indptr, lists_items, pos_indptr, pos_indices, (u32)U, (u32)I, cand);
-    EL_LAUNCH("k_mt_chase", k_mt_chase, dim3(1), dim3(64), 0, s, (const int4*)cand, W, n, out_u, out_i, out_j, result);
+    EL_CHECK_HIP(hipMemcpyAsync(w.backup, mt_state, (MT_N + 1) * 4, hipMemcpyDeviceToDevice, s));
+    EL_LAUNCH("k_mt_generate", k_mt_generate, dim3(1), dim3(256), 0, s, mt_state, w.words, W, (int64_t)0, (const u32*)w.backup);
+    EL_LAUNCH("k_mt_candidates", k_mt_candidates, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, s, (const u32*)w.words, W,
+              lists_indptr, lists_items, pos_indptr, pos_indices, (u32)U, (u32)I, w.cand);
+    EL_LAUNCH("k_mt_chase", k_mt_chase, dim3(1), dim3(64), 0, s, (const int4*)w.cand, W, n, out_u, out_i, out_j, w.result);
     EL_CHECK_LAUNCH();
     // the number of consumed words decides the new generator state: one small synchronising read-back
     int64_t host_result[2] = {0, 0};
-    EL_CHECK_HIP(hipMemcpyAsync(host_result, result, 16, hipMemcpyDeviceToHost, s));
+    EL_CHECK_HIP(hipMemcpyAsync(host_result, w.result, 16, hipMemcpyDeviceToHost, s));
     EL_CHECK_HIP(hipStreamSynchronize(s));
     EL_REQUIRE(host_result[1] == n, "el_bpr_sample_mt19937: ran out of generated words after %lld of %lld samples "
                "(rejection rate far above the provisioned 16 words/sample)", (long long)host_result[1], (long long)n);
     EL_LAUNCH("k_mt_generate", k_mt_generate, dim3(1), dim3(256), 0, s, mt_state, (u32*)nullptr, (int64_t)0, host_result[0],
-              (const u32*)backup);
+              (const u32*)w.backup);
     EL_CHECK_LAUNCH();
     return 0;
 }

@@ -16,14 +16,6 @@
 #include "el_common.h"
 #include <rocprim/device/device_radix_sort.hpp>
 
-extern "C" int el_gemm_f32(el_ctx* ctx, void* stream, int transA, int transB, int64_t M, int64_t N, int64_t K,
-                           const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc,
-                           const float* bias, int act, void* ws, size_t ws_bytes);
-// el_bpr.hip / el_vae.hip
-__global__ void k_adam_dense(float* th, float* g, float* m, float* v, int64_t n, float lr_t, float b1, float b2, float eps);
-__global__ void k_adam_apply_dense(float* th, float* g, float* m, float* v, int64_t n, float alpha, float b1, float b2,
-                                   float eps, int zero_g);
-
 // ---- point-wise sampler (GMF) --------------------------------------------------------------------------
 struct PwPhilox {
     u32 n_lo, n_hi, k0, k1, a, w[4];
@@ -1199,15 +1191,10 @@ struct NmfStepWs {
 static int nmf_carve(el_ctx* ctx, const el_nmf_state* st, void* base, NmfStepWs* w, size_t* total) {
     const int64_t B = st->Bmax;
     const int64_t P = (int64_t)ctx->cus * 8;                      // workgroups of the head / rows of the column-sum grids at most
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        void* r = base ? (void*)((char*)base + off) : nullptr;
-        off += (bytes + 255) & ~(size_t)255;
-        return r;
-    };
+    ElCarve c{(char*)base};
     for (int k = 0; k < 2; ++k) {
-        w->kin[k] = (u32*)take((size_t)2 * B * 4), w->kout[k] = (u32*)take((size_t)2 * B * 4);
-        w->vin[k] = (int32_t*)take((size_t)2 * B * 4), w->vout[k] = (int32_t*)take((size_t)2 * B * 4);
+        w->kin[k] = c.take<u32>((size_t)2 * B), w->kout[k] = c.take<u32>((size_t)2 * B);
+        w->vin[k] = c.take<int32_t>((size_t)2 * B), w->vout[k] = c.take<int32_t>((size_t)2 * B);
     }
     size_t tb = 0;
     u32* np = nullptr;
@@ -1217,23 +1204,23 @@ static int nmf_carve(el_ctx* ctx, const el_nmf_state* st, void* base, NmfStepWs*
         return 1;
     }
     w->tmp_bytes = tb;
-    for (int k = 0; k < 2; ++k) w->tmp[k] = take(tb + 256);
-    w->llist = (int32_t*)take((size_t)(3 * (2 * B / 65 + 2) + 8) * 4);
+    for (int k = 0; k < 2; ++k) w->tmp[k] = c.take<char>(tb + 256);
+    w->llist = c.take<int32_t>((size_t)(3 * (2 * B / 65 + 2) + 8));
     {   // partial rows of the long segments' blocks: at most one per NMF_LBLK positions + one per long segment
         const int64_t Dsum = (st->use_mf ? st->F : 0) + (st->use_mlp ? st->E : 0);
-        w->lpart = (float*)take((size_t)(2 * B / NMF_LBLK + 2 * B / 65 + 4) * Dsum * 4);
+        w->lpart = c.take<float>((size_t)(2 * B / NMF_LBLK + 2 * B / 65 + 4) * Dsum);
     }
-    for (int side = 0; side < 2; ++side) w->mfp[side] = st->use_mf ? (float*)take((size_t)B * st->F * 4) : nullptr;
+    for (int side = 0; side < 2; ++side) w->mfp[side] = st->use_mf ? c.take<float>((size_t)B * st->F) : nullptr;
     const int NF = (st->use_mf ? st->F : 0) + (st->use_mlp ? st->units[st->n_layers > 0 ? st->n_layers - 1 : 0] : 0);
-    w->hpart = (float*)take((size_t)P * (NF + 1) * 4);
-    w->hloss = (double*)take((size_t)P * 8);
+    w->hpart = c.take<float>((size_t)P * (NF + 1));
+    w->hloss = c.take<double>((size_t)P);
     for (int l = 0; l < 4; ++l) {
         w->cpart[l] = nullptr;
         if (!st->use_mlp || l >= st->n_layers) continue;
         const int64_t rows = P > (B + 127) / 128 ? P : (B + 127) / 128;
-        w->cpart[l] = (float*)take((size_t)rows * st->units[l] * 4);
+        w->cpart[l] = c.take<float>((size_t)rows * st->units[l]);
     }
-    *total = off;
+    *total = c.off;
     return 0;
 }
 

@@ -26,9 +26,6 @@
 
 #include "el_topk_common.h"
 
-extern "C" int el_topk_merge(el_ctx* ctx, void* stream, const int32_t* parts_idx, const float* parts_val, int32_t G,
-                             int64_t n_users, int32_t k, int32_t* out_idx, float* out_val);
-
 #define NS_WAVES 8
 #define NS_THREADS (NS_WAVES * 64)
 
@@ -242,7 +239,6 @@ __global__ __launch_bounds__(256) void k_nmf_proj(const float* __restrict__ X, i
 }
 
 // ---- hash of the tables the PI image is derived from (Imlp, W1) -----------------------------------------------------------
-__global__ void k_items_hash(const float* __restrict__ Gi, const float* __restrict__ Bi, int64_t n_g, int64_t n_b, u64* ctl);   // el_topk_screen.hip
 // ctl[3]: the half-precision image of PI (screened route) is older than PI -- set whenever PI is rebuilt, by screened and
 // unscreened calls alike, cleared by k_nmf_pib_done after the image was rebuilt (a call that forces the rebuild -- a workspace the
 // library has not seen, other tables -- initialises it)
@@ -1228,8 +1224,6 @@ static int ns_launch_screen(const NsParams& p, const NsScreenParams& q, int64_t 
     EL_CHECK_LAUNCH();
     return 0;
 }
-
-extern "C" int el_nmf_sync_tables(el_ctx* ctx, void* stream, el_nmf_state* st);      // el_neural.hip
 
 extern "C" int el_nmf_score_topk(el_ctx* ctx, void* stream, el_nmf_state* st, int64_t u_start, int64_t u_stop,
                                  int64_t item_offset, int64_t I_local, const int64_t* excl_indptr, const int32_t* excl_indices,

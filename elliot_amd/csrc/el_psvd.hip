@@ -455,7 +455,20 @@ __global__ __launch_bounds__(256) void k_psvd_signs(const double* __restrict__ p
 }
 
 size_t gram_part_bytes(int64_t n, int R) { return el_align256((size_t)gram_slots(n) * (size_t)R * (size_t)R * sizeof(double)); }
-size_t rr_bytes(int R) { return el_align256((size_t)R * (size_t)R * sizeof(double)); }
+
+struct OrthWs {
+    double* part;          // the Gram partial sums of gram_run
+    double *G, *X, *W;     // [R, R] each
+};
+
+size_t orth_carve(int64_t n, int R, void* base, OrthWs* w) {
+    ElCarve c{(char*)base};
+    w->part = (double*)c.take<char>(gram_part_bytes(n, R));
+    w->G = c.take<double>((size_t)R * R);
+    w->X = c.take<double>((size_t)R * R);
+    w->W = c.take<double>((size_t)R * R);
+    return c.off;
+}
 
 }  // namespace
 
@@ -513,7 +526,8 @@ extern "C" int el_gram_f64(el_ctx* ctx, void* stream, const double* Y, int64_t l
 
 extern "C" size_t el_psvd_orth_ws_bytes(int64_t n, int32_t R) {
     if (n < 0 || R <= 0) return 0;
-    return gram_part_bytes(n, R) + 3 * rr_bytes(R);
+    OrthWs w;
+    return orth_carve(n, R, nullptr, &w);
 }
 
 extern "C" int el_psvd_orth(el_ctx* ctx, void* stream, double* Y, int64_t ldy, int64_t n, int32_t R, int32_t* status, void* ws,
@@ -523,14 +537,10 @@ extern "C" int el_psvd_orth(el_ctx* ctx, void* stream, double* Y, int64_t ldy, i
     EL_REQUIRE(n >= 1 && n < 0x7fffffffLL, "el_psvd_orth: bad row count %lld", (long long)n);
     EL_REQUIRE(R >= 1 && R <= EL_PSVD_MAX_R, "el_psvd_orth: R=%d unsupported (1 .. %d)", R, EL_PSVD_MAX_R);
     EL_REQUIRE(ldy >= R, "el_psvd_orth: ldy=%lld < R=%d", (long long)ldy, R);
-    const size_t need = el_psvd_orth_ws_bytes(n, R);
+    OrthWs w;
+    const size_t need = orth_carve(n, R, ws, &w);
     EL_REQUIRE(ws != nullptr && ws_bytes >= need, "el_psvd_orth: workspace too small (need %zu bytes)", need);
     hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)ws;
-    double* part = (double*)base;
-    double* G = (double*)(base + gram_part_bytes(n, R));
-    double* X = (double*)(base + gram_part_bytes(n, R) + rr_bytes(R));
-    double* W = (double*)(base + gram_part_bytes(n, R) + 2 * rr_bytes(R));
     const double rel = 8.0 * ((double)n * R + (double)R * (R + 1)) * 1.1102230246251565e-16;
     const int lds = R <= PSVD_CHOL_LDS_R;
     const size_t dyn = lds ? 2 * (size_t)R * R * sizeof(double) : 0;
@@ -540,10 +550,10 @@ extern "C" int el_psvd_orth(el_ctx* ctx, void* stream, double* Y, int64_t ldy, i
     EL_LAUNCH("k_psvd_status_init", k_psvd_status_init, dim3(1), dim3(64), 0, st, status, 1);
     EL_CHECK_LAUNCH();
     for (int pass = 0; pass < 2; ++pass) {
-        if (int rc = gram_run(Y, ldy, n, R, G, R, part, status, st)) return rc;
-        EL_LAUNCH("k_psvd_chol", k_psvd_chol, dim3(1), dim3(1024), dyn, st, G, (int)R, rel, W, X, status, lds);
+        if (int rc = gram_run(Y, ldy, n, R, w.G, R, w.part, status, st)) return rc;
+        EL_LAUNCH("k_psvd_chol", k_psvd_chol, dim3(1), dim3(1024), dyn, st, w.G, (int)R, rel, w.W, w.X, status, lds);
         EL_CHECK_LAUNCH();
-        if (int rc = project_run(Y, ldy, n, R, W, R, R, nullptr, Y, ldy, nullptr, 0, status, st)) return rc;
+        if (int rc = project_run(Y, ldy, n, R, w.W, R, R, nullptr, Y, ldy, nullptr, 0, status, st)) return rc;
     }
     return 0;
 }

@@ -22,9 +22,6 @@
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 
-int el_pick_lpt(int F, int vw, int* cpl);                                       // el_bpr.hip
-__global__ void k_adam_dense(float* th, float* g, float* m, float* v, int64_t n, float lr_t, float b1, float b2, float eps);
-
 namespace {
 
 __device__ __forceinline__ float pw_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -353,20 +350,15 @@ struct PwWs {
 int item_chunk(int64_t n);
 int user_chunk(int64_t n);
 
-int carve(int64_t n, int64_t U, int64_t I, int F, char* base, PwWs* w) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base ? base + off : nullptr;
-        off += el_align256(bytes);
-        return p;
-    };
+int carve(int64_t n, int64_t U, int64_t I, int F, void* base, PwWs* w) {
+    ElCarve c{(char*)base};
     u32** slots[4] = {&w->keyU_in, &w->valU_in, &w->keyU, &w->valU};      // users [0, n), items [n, 2n) of one array each
     u32** islots[4] = {&w->keyI_in, &w->valI_in, &w->keyI, &w->valI};
     for (int k = 0; k < 4; ++k) {
-        *slots[k] = (u32*)take((size_t)n * 8);
+        *slots[k] = c.take<u32>((size_t)n * 2);
         *islots[k] = base ? *slots[k] + n : nullptr;
     }
-    w->coef = (float*)take((size_t)n * 4);
+    w->coef = c.take<float>((size_t)n);
     size_t t1 = 0, t2 = 0, t3 = 0;
     u32* np = nullptr;
     if (rocprim::radix_sort_pairs(nullptr, t1, np, np, np, np, (unsigned)(2 * n), 0, el_bits_for(U + I), (hipStream_t)0) != hipSuccess) return 1;
@@ -375,13 +367,13 @@ int carve(int64_t n, int64_t U, int64_t I, int F, char* base, PwWs* w) {
     if (t2 > t1) t1 = t2;
     if (t3 > t1) t1 = t3;
     w->tmp_bytes = t1;
-    w->tmp = take(w->tmp_bytes);
+    w->tmp = c.take<char>(w->tmp_bytes);
     const int cu = user_chunk(n), ci = item_chunk(n);
     const int64_t groups = (n + (cu < ci ? cu : ci) - 1) / (cu < ci ? cu : ci) + 1;
-    w->part = (float*)take((size_t)2 * groups * (size_t)(F > 0 ? F : 1) * 4);
-    w->part_b = (float*)take((size_t)2 * groups * 4);
-    w->split_long = (int32_t*)take((size_t)(2 * groups + 4) * 4);
-    w->total = off;
+    w->part = c.take<float>((size_t)2 * groups * (size_t)(F > 0 ? F : 1));
+    w->part_b = c.take<float>((size_t)2 * groups);
+    w->split_long = c.take<int32_t>((size_t)(2 * groups + 4));
+    w->total = c.off;
     return 0;
 }
 
@@ -394,11 +386,6 @@ int item_chunk(int64_t n) {
 int user_chunk(int64_t n) {
     const int64_t c = n / 65536;
     return (int)(c < 4 ? 4 : (c > 16 ? 16 : c));
-}
-
-unsigned stream_grid(el_ctx* ctx, int64_t n) {
-    const int64_t blocks = (n + 255) / 256, cap = (int64_t)ctx->cus * 8;
-    return (unsigned)(blocks < 1 ? 1 : (blocks < cap ? blocks : cap));
 }
 
 int check_state(const el_pwmf_state* st, const char* who, bool train, int opt) {
@@ -465,9 +452,9 @@ int launch_seg(PwSeg p, const PwWs& w, const char* nm, hipStream_t s) {
 
 int apply(el_ctx* ctx, hipStream_t s, int opt, const char* nm, float* th, float* g, float* m, float* v, int64_t n, float lr_t) {
     if (opt == EL_PW_ADAM)
-        EL_LAUNCH(nm, k_adam_dense, dim3(stream_grid(ctx, n / 4 + 1)), dim3(256), 0, s, th, g, m, v, n, lr_t, 0.9f, 0.999f, 1e-7f);
+        EL_LAUNCH(nm, k_adam_dense, dim3(el_stream_grid(ctx, n / 4 + 1)), dim3(256), 0, s, th, g, m, v, n, lr_t, 0.9f, 0.999f, 1e-7f);
     else
-        EL_LAUNCH(nm, k_adagrad_dense, dim3(stream_grid(ctx, n)), dim3(256), 0, s, th, g, m, n, lr_t, 1e-7f);
+        EL_LAUNCH(nm, k_adagrad_dense, dim3(el_stream_grid(ctx, n)), dim3(256), 0, s, th, g, m, n, lr_t, 1e-7f);
     EL_CHECK_LAUNCH();
     return 0;
 }
@@ -502,7 +489,7 @@ static int pw_grads(el_ctx* ctx, hipStream_t s, const el_pwmf_state* stp, const 
     EL_REQUIRE(stp->U + stp->I < (1LL << 32), "%s: U + I must fit a 32-bit sort key", who);
     const el_pwmf_state st = *stp;
     PwWs w;
-    EL_REQUIRE(carve(n, st.U, st.I, st.F, (char*)ws, &w) == 0, "%s: rocprim size query failed", who);
+    EL_REQUIRE(carve(n, st.U, st.I, st.F, ws, &w) == 0, "%s: rocprim size query failed", who);
     EL_REQUIRE(ws != nullptr && ws_bytes >= w.total, "%s: workspace too small (%zu < %zu)", who, ws_bytes, w.total);
     const bool vec = rows_vec4(st);
 
@@ -618,10 +605,6 @@ extern "C" int el_topk_rerank(el_ctx* ctx, void* stream, int32_t* idx, float* va
 // for BPRMF_batch: the samples of up to PW_LOOP_CHUNK draws come from ONE sampler launch (the sampler does not read the model),
 // the batches are consecutive slices of it.  Same Philox stream and kernels as the per-batch calls.
 // ---------------------------------------------------------------------------------------------------------------------
-extern "C" int el_pointwise_sample_meta(el_ctx* ctx, void* stream, const int64_t* pos_indptr, const int32_t* pos_indices,
-                                        const void* meta, int64_t U, int64_t I, uint64_t seed, uint64_t first_sample, int64_t n,
-                                        int32_t* out_u, int32_t* out_i, float* out_label);
-
 static const int64_t PW_LOOP_CHUNK = 4 << 20;
 
 static int64_t pw_loop_cap(int64_t events, int64_t B) {

@@ -323,16 +323,41 @@ void rp3_slices(int64_t I, int* S, int* width) {
     *S = (int)((I + wd - 1) / wd);
 }
 
-size_t rp3_rows_ws(int64_t I, int N, int64_t n_rows) {
+struct Rp3RowsWs {      // the slice lists of el_rp3_rows: Rp3Rows' sk, sx [rows, S, N] and sc [rows, S, 4]
+    u64* sk;
+    int32_t *sx, *sc;
+};
+size_t rp3_rows_carve(int64_t I, int N, int64_t n_rows, void* base, Rp3RowsWs* w) {
     int S, width;
     rp3_slices(I, &S, &width);
     const size_t slots = (size_t)n_rows * S;
-    return el_align256(slots * N * 8) + el_align256(slots * N * 4) + el_align256(slots * 16);
+    ElCarve c{(char*)base};
+    w->sk = c.take<u64>(slots * N);
+    w->sx = c.take<int32_t>(slots * N);
+    w->sc = c.take<int32_t>(slots * 4);
+    return c.off;
 }
 
-size_t rp3_cut_ws(int64_t I, int N) {
-    return el_align256((size_t)I * 4) * 3 + el_align256((size_t)(I + 1) * 8) + el_align256((size_t)I * N * 4) * 3 +
-           el_knn_csr_ws_bytes(I, N);
+struct Rp3CutWs {
+    int32_t *colcnt, *ccnt, *rowcnt;     // [I]
+    int64_t* colptr;                     // [I + 1]
+    float *ln, *cv;                      // [I, N] the lists' values, normalised; the per-column lists' values
+    int32_t* cx;                         // [I, N] the per-column lists' rows
+    KnnCsrWs b;                          // the buckets of the counting sort; el_knn_csr_launch reuses them
+};
+
+size_t rp3_cut_carve(int64_t I, int N, void* base, Rp3CutWs* w) {
+    const size_t L = (size_t)I * N;
+    ElCarve c{(char*)base};
+    w->colcnt = c.take<int32_t>((size_t)I);
+    w->ccnt = c.take<int32_t>((size_t)I);
+    w->rowcnt = c.take<int32_t>((size_t)I);
+    w->colptr = c.take<int64_t>((size_t)(I + 1));
+    w->ln = c.take<float>(L);
+    w->cx = c.take<int32_t>(L);
+    w->cv = c.take<float>(L);
+    w->b = el_knn_csr_carve(c, I, N);
+    return c.off;
 }
 
 }  // namespace
@@ -352,7 +377,9 @@ extern "C" int el_csr_row_l1(el_ctx* ctx, void* stream, const int64_t* indptr, c
 extern "C" size_t el_rp3_ws_bytes(int64_t I, int32_t n_neighbors, int64_t n_rows) {
     if (I <= 0 || n_neighbors <= 0 || n_rows < 0) return 0;
     const int N = (int)(n_neighbors < I ? n_neighbors : I);
-    return n_rows > 0 ? rp3_rows_ws(I, N, n_rows < I ? n_rows : I) : rp3_cut_ws(I, N);
+    Rp3RowsWs r;
+    Rp3CutWs w;
+    return n_rows > 0 ? rp3_rows_carve(I, N, n_rows < I ? n_rows : I, nullptr, &r) : rp3_cut_carve(I, N, nullptr, &w);
 }
 
 extern "C" int el_rp3_rows(el_ctx* ctx, void* stream, const int64_t* piu_indptr, const int32_t* piu_indices, const float* piu_vals,
@@ -376,17 +403,14 @@ extern "C" int el_rp3_rows(el_ctx* ctx, void* stream, const int64_t* piu_indptr,
     Rp3Rows p;
     rp3_slices(I, &p.S, &p.width);
     EL_REQUIRE(p.S <= 65535, "el_rp3_rows: %lld items need %d column slices (at most 65535)", (long long)I, p.S);
-    EL_REQUIRE(ws != nullptr && ws_bytes >= rp3_rows_ws(I, N, rows), "el_rp3_rows: workspace too small (need %zu bytes)",
-               rp3_rows_ws(I, N, rows));
+    Rp3RowsWs w;
+    const size_t need = rp3_rows_carve(I, N, rows, ws, &w);
+    EL_REQUIRE(ws != nullptr && ws_bytes >= need, "el_rp3_rows: workspace too small (need %zu bytes)", need);
     p.pp = piu_indptr, p.pi = piu_indices, p.pv = piu_vals;
     p.qp = pui_indptr, p.qi = pui_indices, p.qv = pui_vals;
     p.deg = degree, p.I = I, p.i_start = i_start, p.N = N;
+    p.sk = w.sk, p.sx = w.sx, p.sc = w.sc;
     p.cap = el_select_cap(N);
-    const size_t slots = (size_t)rows * p.S;
-    char* w = (char*)ws;
-    p.sk = (u64*)w;       w += el_align256(slots * N * 8);
-    p.sx = (int32_t*)w;   w += el_align256(slots * N * 4);
-    p.sc = (int32_t*)w;
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)p.cap * 12 + (size_t)p.width * 4;
     EL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rp3_slice), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -408,42 +432,35 @@ extern "C" int el_rp3_cut(el_ctx* ctx, void* stream, const int32_t* list_idx, co
     const int N = (int)(n_neighbors < I ? n_neighbors : I);
     EL_REQUIRE(N <= RP3_MAX_NEIGHBORS, "el_rp3_cut: n_neighbors %d > %d unsupported (neighborhood -1 needs at most %d items)", N,
                RP3_MAX_NEIGHBORS, RP3_MAX_NEIGHBORS);
-    EL_REQUIRE(ws != nullptr && ws_bytes >= rp3_cut_ws(I, N), "el_rp3_cut: workspace too small (need %zu bytes)", rp3_cut_ws(I, N));
+    Rp3CutWs w;
+    const size_t need = rp3_cut_carve(I, N, ws, &w);
+    EL_REQUIRE(ws != nullptr && ws_bytes >= need, "el_rp3_cut: workspace too small (need %zu bytes)", need);
     hipStream_t st = (hipStream_t)stream;
     const size_t L = (size_t)I * N;
-    char* w = (char*)ws;
-    int32_t* colcnt = (int32_t*)w;   w += el_align256((size_t)I * 4);
-    int32_t* ccnt = (int32_t*)w;     w += el_align256((size_t)I * 4);
-    int32_t* rowcnt = (int32_t*)w;   w += el_align256((size_t)I * 4);
-    int64_t* colptr = (int64_t*)w;   w += el_align256((size_t)(I + 1) * 8);
-    float* ln = (float*)w;           w += el_align256(L * 4);
-    int32_t* cx = (int32_t*)w;       w += el_align256(L * 4);
-    float* cv = (float*)w;           w += el_align256(L * 4);
-    const KnnCsrWs b = el_knn_csr_carve(w, I, N);              // the buckets of the counting sort; el_knn_csr_launch reuses them
     const int cap = el_select_cap(N);
     const unsigned eblocks = (unsigned)((L + 255) / 256);
     const float* lv = list_val;
     if (normalize) {
         const int ncap = el_pow2(N < 64 ? 64 : N);
         EL_LAUNCH("k_rp3_list_l1", k_rp3_list_l1, dim3((unsigned)I), dim3(64), (size_t)ncap * 8 + 16, st, list_idx, list_val, list_cnt,
-                  N, ncap, ln);
+                  N, ncap, w.ln);
         EL_CHECK_LAUNCH();
-        lv = ln;
+        lv = w.ln;
     }
-    EL_CHECK_HIP(hipMemsetAsync(colcnt, 0, (size_t)I * 4, st));
-    EL_CHECK_HIP(hipMemsetAsync(rowcnt, 0, (size_t)I * 4, st));
-    EL_LAUNCH("k_knn_count", k_knn_count, dim3(eblocks), dim3(256), 0, st, list_idx, list_cnt, I, N, colcnt);
+    EL_CHECK_HIP(hipMemsetAsync(w.colcnt, 0, (size_t)I * 4, st));
+    EL_CHECK_HIP(hipMemsetAsync(w.rowcnt, 0, (size_t)I * 4, st));
+    EL_LAUNCH("k_knn_count", k_knn_count, dim3(eblocks), dim3(256), 0, st, list_idx, list_cnt, I, N, w.colcnt);
     EL_CHECK_LAUNCH();
     // counting sort of the row lists by column: bucket j = (row, value) of every entry in column j
-    EL_LAUNCH("k_knn_scan", k_knn_scan, dim3(1), dim3(1024), 0, st, (const int32_t*)colcnt, I, colptr, b.cursor);
+    EL_LAUNCH("k_knn_scan", k_knn_scan, dim3(1), dim3(1024), 0, st, (const int32_t*)w.colcnt, I, w.colptr, w.b.cursor);
     EL_CHECK_LAUNCH();
-    EL_LAUNCH("k_knn_place", k_knn_place, dim3(eblocks), dim3(256), 0, st, list_idx, lv, list_cnt, I, N, b.cursor, b.tc, b.tv);
+    EL_LAUNCH("k_knn_place", k_knn_place, dim3(eblocks), dim3(256), 0, st, list_idx, lv, list_cnt, I, N, w.b.cursor, w.b.tc, w.b.tv);
     EL_CHECK_LAUNCH();
     EL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rp3_coltop), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)((size_t)cap * 8 + 16)));
-    EL_LAUNCH("k_rp3_coltop", k_rp3_coltop, dim3((unsigned)I), dim3(64), (size_t)cap * 8 + 16, st, (const int64_t*)colptr,
-              (const int32_t*)b.tc, (const float*)b.tv, N, cap, cx, cv, ccnt, rowcnt);
+    EL_LAUNCH("k_rp3_coltop", k_rp3_coltop, dim3((unsigned)I), dim3(64), (size_t)cap * 8 + 16, st, (const int64_t*)w.colptr,
+              (const int32_t*)w.b.tc, (const float*)w.b.tv, N, cap, w.cx, w.cv, w.ccnt, w.rowcnt);
     EL_CHECK_LAUNCH();
     // the per-column lists to W's rows, columns ascending (the buckets are free again)
-    return el_knn_csr_launch(st, cx, cv, ccnt, I, N, rowcnt, w_indptr, w_indices, w_vals, w);
+    return el_knn_csr_launch(st, w.cx, w.cv, w.ccnt, I, N, w.rowcnt, w_indptr, w_indices, w_vals, w.b);
 }

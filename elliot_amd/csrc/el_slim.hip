@@ -317,13 +317,29 @@ size_t slim_lds_placement(int64_t U, int64_t I, int N) {
     return need <= SLIM_LDS_BYTES ? need : 0;
 }
 
-size_t slim_fit_ws(int64_t U, int64_t I, int N, int64_t n) {
-    size_t b = el_align256((size_t)I * 4) + el_align256((size_t)n * I * 4);          // norm; per-target norm (reference)
-    if (!slim_lds_placement(U, I, N)) b += el_align256((size_t)n * U * 4) + el_align256((size_t)n * I * 4);
-    return b;
+struct SlimFitWs {      // norm [I], the per-target norm [n, I] (reference); global placement: residuals [n, U], coefficients [n, I] (else NULL)
+    float *norm, *norm_t, *gr, *gw;
+};
+size_t slim_fit_carve(int64_t U, int64_t I, int N, int64_t n, void* base, SlimFitWs* w) {
+    ElCarve c{(char*)base};
+    w->norm = c.take<float>((size_t)I);
+    w->norm_t = c.take<float>((size_t)n * I);
+    const bool global = !slim_lds_placement(U, I, N);
+    w->gr = global ? c.take<float>((size_t)n * U) : nullptr;
+    w->gw = global ? c.take<float>((size_t)n * I) : nullptr;
+    return c.off;
 }
 
-size_t slim_w_ws(int64_t I, int N) { return el_align256((size_t)I * 4) + el_knn_csr_ws_bytes(I, N); }
+struct SlimWWs {        // the row counts [I], then the list-to-CSR arrays
+    int32_t* rowcnt;
+    KnnCsrWs csr;
+};
+size_t slim_w_carve(int64_t I, int N, void* base, SlimWWs* w) {
+    ElCarve c{(char*)base};
+    w->rowcnt = c.take<int32_t>((size_t)I);
+    w->csr = el_knn_csr_carve(c, I, N);
+    return c.off;
+}
 
 }  // namespace
 
@@ -341,7 +357,9 @@ extern "C" int el_slim_order(el_ctx* ctx, void* stream, uint32_t seed_state, int
 extern "C" size_t el_slim_ws_bytes(int64_t U, int64_t I, int64_t n_cols, int32_t n_neighbors) {
     if (U <= 0 || I <= 0 || n_neighbors <= 0 || n_cols < 0) return 0;
     const int N = (int)(n_neighbors < I ? n_neighbors : I);
-    return n_cols > 0 ? slim_fit_ws(U, I, N, n_cols < I ? n_cols : I) : slim_w_ws(I, N);
+    SlimFitWs f;
+    SlimWWs w;
+    return n_cols > 0 ? slim_fit_carve(U, I, N, n_cols < I ? n_cols : I, nullptr, &f) : slim_w_carve(I, N, nullptr, &w);
 }
 
 extern "C" int el_slim_fit(el_ctx* ctx, void* stream, const int64_t* csc_indptr, const int32_t* csc_indices, const float* csc_vals,
@@ -366,32 +384,26 @@ extern "C" int el_slim_fit(el_ctx* ctx, void* stream, const int64_t* csc_indptr,
                (long long)j_stop);
     const int64_t n = j_stop - j_start;
     if (n == 0) return 0;
-    EL_REQUIRE(ws != nullptr && ws_bytes >= slim_fit_ws(U, I, N, n), "el_slim_fit: workspace too small (need %zu bytes)",
-               slim_fit_ws(U, I, N, n));
+    SlimFitWs w;
+    const size_t need = slim_fit_carve(U, I, N, n, ws, &w);
+    EL_REQUIRE(ws != nullptr && ws_bytes >= need, "el_slim_fit: workspace too small (need %zu bytes)", need);
     hipStream_t st = (hipStream_t)stream;
     const bool ref = exclusion == EL_SLIM_REFERENCE;
     const size_t lds_fit = slim_lds_placement(U, I, N);
-    char* wsp = (char*)ws;
-    float* norm = (float*)wsp;     wsp += el_align256((size_t)I * 4);
-    float* norm_t = (float*)wsp;   wsp += el_align256((size_t)n * I * 4);
     SlimFit p;
     p.cp = csc_indptr, p.ci = csc_indices, p.cv = csc_vals, p.order = order;
-    p.gr = p.gw = nullptr;
-    if (!lds_fit) {
-        p.gr = (float*)wsp;        wsp += el_align256((size_t)n * U * 4);
-        p.gw = (float*)wsp;
-    }
+    p.gr = w.gr, p.gw = w.gw;
     p.U = U, p.I = I, p.j_start = j_start;
     p.l1 = l1, p.l2 = l2, p.tol = tol, p.max_iter = max_iter, p.reference = ref ? 1 : 0;
     p.N = N, p.cap = el_select_cap(N), p.w_bytes = (int)slim_w_bytes(I);
     p.lx = list_idx, p.lv = list_val, p.lcnt = list_cnt, p.n_iter = n_iter, p.coef = coef_or_null;
     if (ref) {
         EL_LAUNCH("k_slim_norm_ref", k_slim_norm_ref, dim3((unsigned)((I + 63) / 64), (unsigned)n), dim3(64), 0, st, csc_indptr,
-                  csc_indices, csc_vals, I, j_start, norm_t);
-        p.norm = norm_t;
+                  csc_indices, csc_vals, I, j_start, w.norm_t);
+        p.norm = w.norm_t;
     } else {
-        EL_LAUNCH("k_slim_norm", k_slim_norm, dim3((unsigned)((I + 255) / 256)), dim3(256), 0, st, csc_indptr, csc_vals, I, norm);
-        p.norm = norm;
+        EL_LAUNCH("k_slim_norm", k_slim_norm, dim3((unsigned)((I + 255) / 256)), dim3(256), 0, st, csc_indptr, csc_vals, I, w.norm);
+        p.norm = w.norm;
     }
     EL_CHECK_LAUNCH();
     const size_t lds = lds_fit ? lds_fit : slim_cut_lds(N);
@@ -410,13 +422,13 @@ extern "C" int el_slim_w(el_ctx* ctx, void* stream, const int32_t* list_idx, con
     EL_REQUIRE(w_indptr && w_indices && w_vals, "el_slim_w: null output pointer");
     EL_REQUIRE(I >= 1 && I < 0x7fffffffLL, "el_slim_w: bad item count %lld", (long long)I);
     EL_REQUIRE(N >= 1 && N <= I && N <= SLIM_MAX_NEIGHBORS, "el_slim_w: list width %d outside [1, min(I, %d)]", N, SLIM_MAX_NEIGHBORS);
-    EL_REQUIRE(ws != nullptr && ws_bytes >= slim_w_ws(I, N), "el_slim_w: workspace too small (need %zu bytes)", slim_w_ws(I, N));
+    SlimWWs w;
+    const size_t need = slim_w_carve(I, N, ws, &w);
+    EL_REQUIRE(ws != nullptr && ws_bytes >= need, "el_slim_w: workspace too small (need %zu bytes)", need);
     hipStream_t st = (hipStream_t)stream;
-    int32_t* rowcnt = (int32_t*)ws;
-    EL_CHECK_HIP(hipMemsetAsync(rowcnt, 0, (size_t)I * 4, st));
+    EL_CHECK_HIP(hipMemsetAsync(w.rowcnt, 0, (size_t)I * 4, st));
     EL_LAUNCH("k_knn_count", k_knn_count, dim3((unsigned)(((size_t)I * N + 255) / 256)), dim3(256), 0, st, list_idx, list_cnt, I, N,
-              rowcnt);
+              w.rowcnt);
     EL_CHECK_LAUNCH();
-    return el_knn_csr_launch(st, list_idx, list_val, list_cnt, I, N, rowcnt, w_indptr, w_indices, w_vals,
-                             (char*)ws + el_align256((size_t)I * 4));
+    return el_knn_csr_launch(st, list_idx, list_val, list_cnt, I, N, w.rowcnt, w_indptr, w_indices, w_vals, w.csr);
 }

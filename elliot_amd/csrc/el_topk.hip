@@ -554,11 +554,6 @@ __global__ __launch_bounds__(64) void k_topk_wave_f64(TopkParams64 p, int cap) {
 // =====================================================================================
 static bool mfma_eligible(int F, int k, const void* cand) { return cand == nullptr && F >= 1 && F <= 256 && k >= 1 && k <= 40; }
 
-// el_topk_screen.hip
-bool el_topk_screen_eligible(int F, int k, const void* cand);
-size_t el_topk_screen_ws_bytes(int64_t n_users, int64_t I_local, int F, int k, int64_t excl_nnz);
-int el_topk_screen_run(const TopkParams& p, void* ws, size_t ws_bytes, hipStream_t st, bool items_unchanged);
-
 extern "C" size_t el_score_topk_ws_bytes(int64_t n_users, int64_t I_local, int32_t F, int32_t k, int64_t excl_nnz, int algo) {
     algo &= 0xff;
     if ((algo == EL_TOPK_AUTO || algo == EL_TOPK_SCREEN) && el_topk_screen_eligible(F, k, nullptr) && n_users > 0)
@@ -673,17 +668,19 @@ static int64_t list_cap_for(int64_t n_users) {
     return c < LIST_DENSE ? LIST_DENSE : c;       // (the dense tier borrows the split scratch for its partial lists)
 }
 
-size_t el_topk_list_scratch_bytes(int64_t n_users, int64_t I_local, int k) {
-    return 2 * el_align256((size_t)LIST_SPLIT * (size_t)list_cap_for(n_users) * (size_t)k * 4) + el_align256((size_t)LIST_DENSE * (size_t)I_local * 4);
+TopkListWs el_topk_list_carve(ElCarve& c, int64_t n_users, int64_t I_local, int k) {
+    const size_t part = (size_t)LIST_SPLIT * (size_t)list_cap_for(n_users) * (size_t)k;
+    TopkListWs w;
+    w.part_idx = c.take<int32_t>(part);
+    w.part_val = c.take<float>(part);
+    w.preds = c.take<float>((size_t)LIST_DENSE * (size_t)I_local);
+    return w;
 }
 
-int el_topk_run_list(const TopkParams& p0, void* scratch, size_t scratch_bytes, hipStream_t st) {
+int el_topk_run_list(const TopkParams& p0, const TopkListWs& scratch, hipStream_t st) {
     const int64_t n_users = p0.u_stop - p0.u_start;
     const int64_t cap = list_cap_for(n_users);
-    EL_REQUIRE(scratch && scratch_bytes >= el_topk_list_scratch_bytes(n_users, p0.I_local, p0.k), "el_topk_run_list: scratch too small");
-    int32_t* part_idx = (int32_t*)scratch;
-    float* part_val = (float*)((char*)scratch + el_align256((size_t)LIST_SPLIT * (size_t)cap * (size_t)p0.k * 4));
-    float* preds = (float*)((char*)scratch + 2 * el_align256((size_t)LIST_SPLIT * (size_t)cap * (size_t)p0.k * 4));
+    EL_REQUIRE(scratch.part_idx && scratch.part_val && scratch.preds, "el_topk_run_list: scratch too small");
     if (p0.I_local > 0) {                            // tier 1: entries [0, LIST_DENSE)
         TopkParams d = p0;
         d.ulist_skip = 0;
@@ -691,10 +688,10 @@ int el_topk_run_list(const TopkParams& p0, void* scratch, size_t scratch_bytes, 
         d.nsplit = 0;
         if (p0.F <= 256)
             EL_LAUNCH("k_list_scores", k_list_scores, dim3((unsigned)((p0.I_local + 255) / 256)), dim3(256), (size_t)LIST_DENSE * p0.F * 4, st,
-                      d, preds);
+                      d, scratch.preds);
         else
-            EL_LAUNCH("k_list_scores", k_list_scores_wide, dim3((unsigned)((p0.I_local + 255) / 256), LIST_DENSE), dim3(256), 0, st, d, preds);
-        d.preds = preds;
+            EL_LAUNCH("k_list_scores", k_list_scores_wide, dim3((unsigned)((p0.I_local + 255) / 256), LIST_DENSE), dim3(256), 0, st, d, scratch.preds);
+        d.preds = scratch.preds;
         d.ld = p0.I_local;
         // one wave per (entry, item slice) -> partial lists in the split scratch (free until tier 2 runs) -> merge
         int DS = (int)((p0.I_local + 2047) / 2048);
@@ -702,16 +699,16 @@ int el_topk_run_list(const TopkParams& p0, void* scratch, size_t scratch_bytes, 
         d.nsplit = DS > 1 ? DS : 0;
         if (DS > 1) {
             d.part_stride = LIST_DENSE;
-            d.out_idx = part_idx;
-            d.out_val = part_val;
+            d.out_idx = scratch.part_idx;
+            d.out_val = scratch.part_val;
         }
         const int wcap = el_select_cap(p0.k);
         EL_LAUNCH("k_topk_wave", k_topk_wave<true>, dim3(LIST_DENSE, DS > 1 ? DS : 1), dim3(64), (size_t)wcap * 8 + 16, st, d, wcap);
         if (DS > 1) {
             int mcap = el_pow2(DS * p0.k);
             if (mcap < 64) mcap = 64;
-            EL_LAUNCH("k_topk_merge", k_topk_merge, dim3(LIST_DENSE), dim3(64), (size_t)mcap * 8, st, (const int32_t*)part_idx,
-                      (const float*)part_val, DS, (int64_t)LIST_DENSE, p0.k, mcap, p0.out_idx, p0.out_val, p0.ulist, p0.ulist_n, 0);
+            EL_LAUNCH("k_topk_merge", k_topk_merge, dim3(LIST_DENSE), dim3(64), (size_t)mcap * 8, st, (const int32_t*)scratch.part_idx,
+                      (const float*)scratch.part_val, DS, (int64_t)LIST_DENSE, p0.k, mcap, p0.out_idx, p0.out_val, p0.ulist, p0.ulist_n, 0);
         }
         EL_CHECK_LAUNCH();
     }
@@ -728,16 +725,16 @@ int el_topk_run_list(const TopkParams& p0, void* scratch, size_t scratch_bytes, 
             q.nsplit = WS > 1 ? WS : 0;
             if (WS > 1) {
                 q.part_stride = cap;
-                q.out_idx = part_idx;
-                q.out_val = part_val;
+                q.out_idx = scratch.part_idx;
+                q.out_val = scratch.part_val;
             }
             const int64_t rows = (n_users - skip1) < cap ? (n_users - skip1) : cap;
             EL_LAUNCH("k_topk_wave", k_topk_wave<false>, dim3((unsigned)rows, WS > 1 ? WS : 1), dim3(64), (size_t)wcap * 8 + 16, st, q, wcap);
             if (WS > 1) {
                 int mcap = el_pow2(WS * p0.k);
                 if (mcap < 64) mcap = 64;
-                EL_LAUNCH("k_topk_merge", k_topk_merge, dim3((unsigned)rows), dim3(64), (size_t)mcap * 8, st, (const int32_t*)part_idx,
-                          (const float*)part_val, WS, cap, p0.k, mcap, p0.out_idx, p0.out_val, p0.ulist, p0.ulist_n, skip1);
+                EL_LAUNCH("k_topk_merge", k_topk_merge, dim3((unsigned)rows), dim3(64), (size_t)mcap * 8, st, (const int32_t*)scratch.part_idx,
+                          (const float*)scratch.part_val, WS, cap, p0.k, mcap, p0.out_idx, p0.out_val, p0.ulist, p0.ulist_n, skip1);
             }
             if (n_users > skip1 + cap) {                             // beyond the split scratch: unsplit
                 TopkParams r = p0;
@@ -760,15 +757,15 @@ int el_topk_run_list(const TopkParams& p0, void* scratch, size_t scratch_bytes, 
     p.nsplit = (int)(S > 1 ? S : 0);
     if (S > 1) {
         p.part_stride = cap;
-        p.out_idx = part_idx;
-        p.out_val = part_val;
+        p.out_idx = scratch.part_idx;
+        p.out_val = scratch.part_val;
     }
     if (int rc = el_topk_launch_mfma(p, st)) return rc;
     if (S > 1) {
         int mcap = el_pow2((int)S * p0.k);
         if (mcap < 64) mcap = 64;
-        EL_LAUNCH("k_topk_merge", k_topk_merge, dim3((unsigned)cap), dim3(64), (size_t)mcap * 8, st, (const int32_t*)part_idx,
-                  (const float*)part_val, (int)S, cap, p0.k, mcap, p0.out_idx, p0.out_val, p0.ulist, p0.ulist_n, skip1);
+        EL_LAUNCH("k_topk_merge", k_topk_merge, dim3((unsigned)cap), dim3(64), (size_t)mcap * 8, st, (const int32_t*)scratch.part_idx,
+                  (const float*)scratch.part_val, (int)S, cap, p0.k, mcap, p0.out_idx, p0.out_val, p0.ulist, p0.ulist_n, skip1);
         EL_CHECK_LAUNCH();
     }
     if (n_users > skip1 + cap) {                     // more flagged users than the split scratch holds: plain kernel for the rest

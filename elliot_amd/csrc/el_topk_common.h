@@ -34,9 +34,18 @@ struct TopkParams {
 // defined in el_topk.hip: fp32 MFMA kernel (must be eligible: F <= 256, k <= 40, no candidate list); honours p.ulist
 int el_topk_launch_mfma(const TopkParams& p, hipStream_t st);
 // defined in el_topk.hip: exact top-k of the users in p.ulist (device list, *p.ulist_n entries), parallel over users AND
-// item slices so that a handful of users does not serialise on one workgroup.  scratch: el_topk_list_scratch_bytes().
-size_t el_topk_list_scratch_bytes(int64_t n_users, int64_t I_local, int k);
-int el_topk_run_list(const TopkParams& p, void* scratch, size_t scratch_bytes, hipStream_t st);
+// item slices so that a handful of users does not serialise on one workgroup.  Its scratch is nested in the caller's workspace.
+struct TopkListWs {
+    int32_t* part_idx;     // [LIST_SPLIT, list cap, k] partial lists of the item slices
+    float* part_val;
+    float* preds;          // [LIST_DENSE, I_local] scores of the dense tier
+};
+TopkListWs el_topk_list_carve(ElCarve& c, int64_t n_users, int64_t I_local, int k);
+int el_topk_run_list(const TopkParams& p, const TopkListWs& scratch, hipStream_t st);
+// defined in el_topk_screen.hip: the bf16-screened route of el_score_topk
+bool el_topk_screen_eligible(int F, int k, const void* cand);
+size_t el_topk_screen_ws_bytes(int64_t n_users, int64_t I_local, int F, int k, int64_t excl_nnz);
+int el_topk_screen_run(const TopkParams& p, void* ws, size_t ws_bytes, hipStream_t st, bool items_unchanged);
 
 // ---- one-wave bitonic sort (descending) of n = 2^m u64 keys held in LDS --------------
 __device__ __forceinline__ void el_wave_bitonic_desc(u64* a, int n, int lane) {

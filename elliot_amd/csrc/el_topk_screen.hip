@@ -939,11 +939,39 @@ static ScreenPolicy screen_policy(int k, int64_t I_local) {
     return q;
 }
 
+struct ScreenWs {
+    unsigned short* gib;       // ScreenParams::Gib and ::stats, writable
+    float* stats;
+    TopkListWs fb;             // scratch of the exact fallback (el_topk_run_list)
+};
+
+// The workspace of a screened call.  The item side comes first: its place does not depend on n_users, so the image survives
+// from block to block (EL_TOPK_ITEMS_UNCHANGED).  The record lists come last: sp->lists is where they start, the caller
+// shares whatever its workspace holds behind that between lists and lsc.
+static size_t screen_carve(int64_t n_users, int64_t I_local, int F, int k, int64_t excl_nnz, void* base, ScreenParams* sp, ScreenWs* w) {
+    const size_t nu = (size_t)n_users;
+    ElCarve c{(char*)base};
+    sp->Gib = w->gib = c.take<unsigned short>((size_t)I_local * screen_fp(F));
+    sp->inorm = c.take<float2>((size_t)I_local);
+    sp->stats = w->stats = c.take<float>(4);
+    sp->smax = c.take<float>(nu * SCR_TI);
+    sp->thr = c.take<float>(nu);
+    sp->cnt = c.take<int32_t>(nu);
+    sp->ovf = c.take<int32_t>(nu);
+    sp->ulist = c.take<int32_t>(nu);
+    sp->Tg = c.take<float>(nu);
+    sp->Eu = c.take<float>(nu);
+    sp->nuv = c.take<float>(nu);
+    sp->duv = c.take<float>(nu);
+    w->fb = el_topk_list_carve(c, n_users, I_local, k);
+    sp->lists = (u64*)c.take<char>((nu * screen_policy(k, I_local).surv + (size_t)excl_nnz) * 12);     // surv * U + nnz records of 8 + 4 bytes
+    return c.off;
+}
+
 size_t el_topk_screen_ws_bytes(int64_t n_users, int64_t I_local, int F, int k, int64_t excl_nnz) {
-    const int FP = screen_fp(F);
-    if (excl_nnz < 0) excl_nnz = 0;
-    return el_align256((size_t)I_local * FP * 2) + el_align256(16) + el_align256((size_t)n_users * SCR_TI * 4) + 8 * el_align256((size_t)n_users * 4) + el_align256((size_t)I_local * 8) +
-           el_align256(el_topk_list_scratch_bytes(n_users, I_local, k)) + el_align256(((size_t)n_users * screen_policy(k, I_local).surv + (size_t)excl_nnz) * 12);
+    ScreenParams sp;
+    ScreenWs w;
+    return screen_carve(n_users, I_local, F, k, excl_nnz < 0 ? 0 : excl_nnz, nullptr, &sp, &w);
 }
 
 template <int FP, int MODE, int NW, bool PROF>
@@ -1020,35 +1048,13 @@ int el_topk_screen_run(const TopkParams& p, void* ws, size_t ws_bytes, hipStream
     const int64_t n_users = p.u_stop - p.u_start;
     if (n_users <= 0) return 0;
     const int FP = screen_fp(p.F);
-    const size_t fixed = el_topk_screen_ws_bytes(n_users, p.I_local, p.F, p.k, 0);
-    EL_REQUIRE(ws != nullptr && ws_bytes >= fixed, "el_score_topk: screened top-k needs a workspace of el_score_topk_ws_bytes() bytes");
-    char* base = (char*)ws;
     ScreenParams sp;
+    ScreenWs w;
+    const size_t fixed = screen_carve(n_users, p.I_local, p.F, p.k, 0, ws, &sp, &w);
+    EL_REQUIRE(ws != nullptr && ws_bytes >= fixed, "el_score_topk: screened top-k needs a workspace of el_score_topk_ws_bytes() bytes");
     sp.t = p;
-    unsigned short* gib = (unsigned short*)base;                  // item side first: its place does not depend on n_users, so the
-    base += el_align256((size_t)p.I_local * FP * 2);              // image survives from block to block (EL_TOPK_ITEMS_UNCHANGED)
-    sp.inorm = (float2*)base;
-    base += el_align256((size_t)p.I_local * 8);
-    float* stats = (float*)base;
-    base += el_align256(16);
-    sp.smax = (float*)base;
-    base += el_align256((size_t)n_users * SCR_TI * 4);
-    sp.thr = (float*)base;
-    base += el_align256((size_t)n_users * 4);
-    sp.cnt = (int32_t*)base;
-    base += el_align256((size_t)n_users * 4);
-    sp.ovf = (int32_t*)base;
-    base += el_align256((size_t)n_users * 4);
-    sp.ulist = (int32_t*)base;
-    base += el_align256((size_t)n_users * 4);
-    sp.Tg = (float*)base;
-    base += el_align256((size_t)n_users * 4);
-    sp.Eu = (float*)base;
-    base += el_align256((size_t)n_users * 4);
-    sp.nuv = (float*)base;
-    base += el_align256((size_t)n_users * 4);
-    sp.duv = (float*)base;
-    base += el_align256((size_t)n_users * 4);
+    unsigned short* gib = w.gib;
+    float* stats = w.stats;
     const ScreenPolicy pol = screen_policy(p.k, p.I_local);
     sp.surv = pol.surv;
     sp.stride = pol.stride;
@@ -1057,14 +1063,8 @@ int el_topk_screen_run(const TopkParams& p, void* ws, size_t ws_bytes, hipStream
     sp.band = pol.band;
     sp.band_min = pol.band_min;
     sp.ulist_n = (int32_t*)(stats + 2);
-    void* fb_scratch = base;
-    const size_t fb_bytes = el_topk_list_scratch_bytes(n_users, p.I_local, p.k);
-    base += el_align256(fb_bytes);
-    sp.list_cap = (int64_t)(((char*)ws + ws_bytes - base) / 12) & ~(int64_t)31;   // whatever the caller provisioned for surv*U + nnz
-    sp.lists = (u64*)base;
-    sp.lsc = (float*)(base + (size_t)sp.list_cap * 8);
-    sp.Gib = gib;
-    sp.stats = stats;
+    sp.list_cap = (int64_t)(((char*)ws + ws_bytes - (char*)sp.lists) / 12) & ~(int64_t)31;   // whatever the caller provisioned for surv*U + nnz
+    sp.lsc = (float*)((char*)sp.lists + (size_t)sp.list_cap * 8);
     sp.prof = nullptr;
     sp.prof2 = nullptr;
     // The item side (bf16 image, max norm, max |bias|) depends on Gi / Bi only.  A caller that scores block after block of
@@ -1127,7 +1127,7 @@ int el_topk_screen_run(const TopkParams& p, void* ws, size_t ws_bytes, hipStream
     pw.ulist = sp.ulist;
     pw.ulist_n = sp.ulist_n;
     ctx->scr_cnt = sp.cnt, ctx->scr_flagged = sp.ulist_n, ctx->scr_users = n_users;
-    return el_topk_run_list(pw, fb_scratch, fb_bytes, st);
+    return el_topk_run_list(pw, w.fb, st);
 }
 
 // Diagnostics of the last screened el_score_topk call on this ctx (its workspace must still be alive): records pass 2 appended over

@@ -15,10 +15,6 @@
 // The L2 kernel_regularizers declared by the reference are never added to its loss: no-op here too.
 #include "el_common.h"
 
-extern "C" int el_gemm_f32(el_ctx* ctx, void* stream, int transA, int transB, int64_t M, int64_t N, int64_t K,
-                           const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc,
-                           const float* bias, int act, void* ws, size_t ws_bytes);
-
 // ---- first layer: CSR rows x W1 ------------------------------------------------------------------------
 // keep-probability mask of nonzero (user, item): Philox keyed by (seed, step); 1/(1-rate) scaling as Keras Dropout
 __device__ __forceinline__ float vae_drop_scale(float rate, u64 seed, u32 step, u32 user, u32 item) {

@@ -35,6 +35,17 @@ def _ptr(t, dtype=None, name="tensor"):
     return C.c_void_p(t.data_ptr())
 
 
+def workspace(holder, attr, need, device):
+    """Every workspace a library call is handed comes from here: the uint8 device tensor cached as holder.<attr>, replaced by a
+    larger one when it holds fewer than `need` bytes (never a zero-length buffer).  attr = None: a fresh tensor, kept nowhere."""
+    ws = getattr(holder, attr, None) if attr else None
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(int(need), 1), dtype=torch.uint8, device=device)
+        if attr:
+            setattr(holder, attr, ws)
+    return ws
+
+
 class Context:
     """One el_ctx per device (include/elliot_hip.h: el_ctx_create)."""
 
@@ -184,11 +195,7 @@ def score_topk(ctx, Gu, Gi, Bi, u_start, u_stop, k, excl=None, cand=None, item_o
     if cand is None and algo_id in (EL_TOPK_AUTO, EL_TOPK_SCREEN):
         need = int(ctx.lib.el_score_topk_ws_bytes(int(n), int(I_local), int(F), int(k), int(excl.nnz) if excl is not None else 0, algo_id))
         if need:
-            cached = getattr(ctx, "_topk_ws", None)
-            if cached is None or cached.numel() < need:
-                cached = torch.empty(need, dtype=torch.uint8, device=ctx.device)
-                ctx._topk_ws = cached
-            ws = C.c_void_p(cached.data_ptr())
+            ws = _ptr(workspace(ctx, "_topk_ws", need, ctx.device))
     check(ctx.lib.el_score_topk(ctx.handle, ctx.stream(), _ptr(Gu, torch.float32, "Gu"),
                                 _ptr(Gi, torch.float32, "Gi"), _ptr(Bi, torch.float32, "Bi"),
                                 int(u_start), int(u_stop), int(item_offset), int(I_local), int(F),
@@ -250,10 +257,6 @@ def device_values(values, device):
     return torch.from_numpy(v if v.shape[0] else np.zeros(1, np.float32)).to(device)
 
 
-def _workspace(ctx, need):
-    return torch.empty(max(int(need), 1), dtype=torch.uint8, device=ctx.device)
-
-
 def _w_alloc(ctx, n, N):
     """(w_indptr, w_indices, w_vals) for a W of n rows with at most n * N entries (never a zero-length buffer)."""
     return (torch.empty(n + 1, dtype=torch.int64, device=ctx.device), torch.empty(max(n * N, 1), dtype=torch.int32, device=ctx.device),
@@ -303,7 +306,7 @@ def knn_build(ctx, R, side, n_neighbors, sim):
     max_deg = int(np.diff(P.indptr).max()) if n else 0
     max_abs = int(np.abs(pv).max()) if pv.size else 0
     need = int(ctx.lib.el_knn_ws_bytes(int(n), int(n_neighbors)))
-    ws = _workspace(ctx, need)
+    ws = workspace(ctx, None, need, ctx.device)
     w_indptr, w_indices, w_vals = _w_alloc(ctx, n, min(int(n_neighbors), n))
     check(ctx.lib.el_knn_build(ctx.handle, ctx.stream(), _ptr(Pc.indptr), _ptr(Pc.indices), _ptr(pvt), _ptr(Qc.indptr),
                                _ptr(Qc.indices), _ptr(qvt), int(n), int(n_other), int(n_neighbors), KNN_SIMILARITIES[sim],
@@ -400,7 +403,7 @@ def rp3_rows(ctx, Piu, piu_vals, Pui, pui_vals, degree, n_neighbors, i_start=0, 
     per_row = max(int(ctx.lib.el_rp3_ws_bytes(I, n_neighbors, 1)), 1)
     block = max(min(RP3_ROWS_WS_BYTES // per_row, n), 1)
     need = int(ctx.lib.el_rp3_ws_bytes(I, n_neighbors, block))
-    ws = _workspace(ctx, need)
+    ws = workspace(ctx, None, need, ctx.device)
     for r0 in range(0, n, block):
         r1 = min(r0 + block, n)
         check(ctx.lib.el_rp3_rows(ctx.handle, ctx.stream(), _ptr(Piu.indptr, torch.int64), _ptr(Piu.indices, torch.int32),
@@ -420,7 +423,7 @@ def rp3_cut(ctx, idx, val, cnt, n_neighbors, normalize):
     if idx.shape != (I, N) or val.shape != (I, N):
         raise ValueError(f"row lists must be [{I}, {N}], got {tuple(idx.shape)}")
     need = int(ctx.lib.el_rp3_ws_bytes(I, n_neighbors, 0))
-    ws = _workspace(ctx, need)
+    ws = workspace(ctx, None, need, ctx.device)
     w_indptr, w_indices, w_vals = _w_alloc(ctx, I, N)
     check(ctx.lib.el_rp3_cut(ctx.handle, ctx.stream(), _ptr(idx, torch.int32), _ptr(val, torch.float32), _ptr(cnt, torch.int32), I,
                              n_neighbors, 1 if normalize else 0, _ptr(w_indptr), _ptr(w_indices), _ptr(w_vals),
@@ -496,7 +499,7 @@ def slim_fit(ctx, csc, csc_vals, alpha, l1_ratio, order, n_neighbors, j_start=0,
     block = max(min(SLIM_FIT_WS_BYTES // per_col, n), 1)
     need = int(ctx.lib.el_slim_ws_bytes(U, I, block, n_neighbors))
     given = need if ws_bytes is None else int(ws_bytes)
-    ws = _workspace(ctx, given)
+    ws = workspace(ctx, None, given, ctx.device)
     for c0 in range(0, n, block):
         c1 = min(c0 + block, n)
         check(ctx.lib.el_slim_fit(ctx.handle, ctx.stream(), _ptr(csc.indptr, torch.int64), _ptr(csc.indices, torch.int32),
@@ -516,7 +519,7 @@ def slim_w(ctx, idx, val, cnt):
     if idx.shape != (I, N) or val.shape != (I, N):
         raise ValueError(f"column lists must be [{I}, {N}], got {tuple(idx.shape)} / {tuple(val.shape)}")
     need = int(ctx.lib.el_slim_ws_bytes(I, I, 0, N))
-    ws = _workspace(ctx, need)
+    ws = workspace(ctx, None, need, ctx.device)
     w_indptr, w_indices, w_vals = _w_alloc(ctx, I, N)
     check(ctx.lib.el_slim_w(ctx.handle, ctx.stream(), _ptr(idx, torch.int32), _ptr(val, torch.float32), _ptr(cnt, torch.int32), I, N,
                             _ptr(w_indptr), _ptr(w_indices), _ptr(w_vals), C.c_void_p(ws.data_ptr()), need), "el_slim_w")
@@ -562,20 +565,13 @@ class AlsCSR:
         self.empty = np.diff(np.asarray(indptr, dtype=np.int64)) == 0
 
 
-def _als_ws(ctx, holder, attr, need):
-    ws = getattr(holder, attr, None)
-    if need and (ws is None or ws.numel() < need):
-        ws = torch.empty(need, dtype=torch.uint8, device=ctx.device)
-        setattr(holder, attr, ws)
-    return (C.c_void_p(ws.data_ptr()) if need else None), need
-
-
 def als_gram(ctx, Y, out=None, holder=None):
     """G = Y^T Y (fp64 [F, F], el_als_gram): fixed slots, symmetric bit for bit."""
     n, F = Y.shape
     if out is None:
         out = torch.empty((F, F), dtype=torch.float64, device=ctx.device)
-    ws, need = _als_ws(ctx, holder if holder is not None else ctx, "_als_gram_ws", int(ctx.lib.el_als_gram_ws_bytes(int(n), int(F))))
+    need = int(ctx.lib.el_als_gram_ws_bytes(int(n), int(F)))
+    ws = _ptr(workspace(holder if holder is not None else ctx, "_als_gram_ws", need, ctx.device)) if need else None
     check(ctx.lib.el_als_gram(ctx.handle, ctx.stream(), _ptr(Y, torch.float64, "Y"), int(n), int(F), _ptr(out, torch.float64, "G"),
                               ws, need), "el_als_gram")
     return out
@@ -590,7 +586,8 @@ def als_solve(ctx, pattern, Y, G, w_A, w_b, lam, X, skip_empty=False, holder=Non
     if pattern.csr.n_rows != n_rows or pattern.csr.n_cols != Y.shape[0]:
         raise ValueError("pattern shape does not match X / Y")
     holder = holder if holder is not None else ctx
-    ws, need = _als_ws(ctx, holder, "_als_solve_ws", int(ctx.lib.el_als_solve_ws_bytes(int(pattern.n_pieces), int(F))))
+    need = int(ctx.lib.el_als_solve_ws_bytes(int(pattern.n_pieces), int(F)))
+    ws = _ptr(workspace(holder, "_als_solve_ws", need, ctx.device)) if need else None
     status = getattr(holder, "_als_status", None)
     if status is None:
         status = holder._als_status = torch.empty(2, dtype=torch.int32, device=ctx.device)
@@ -717,7 +714,7 @@ def inv_f64(ctx, A, ipiv=None, ws=None):
     status = torch.empty(1, dtype=torch.int32, device=ctx.device)
     need = int(ctx.lib.el_inv_f64_ws_bytes(n))
     if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=ctx.device)
+        ws = workspace(ctx, None, need, ctx.device)
     check(ctx.lib.el_inv_f64(ctx.handle, ctx.stream(), _ptr(A, torch.float64, "A"), int(A.stride(0)), n, _ptr(ipiv, torch.int32), _ptr(status, torch.int32),
                              C.c_void_p(ws.data_ptr()), need), "el_inv_f64")
     bad = int(status.item())
@@ -748,7 +745,7 @@ def ease_weights(ctx, P, out=None):
     if out is None:
         out = torch.empty((I, I), dtype=torch.float32, device=ctx.device)
     need = int(ctx.lib.el_ease_weights_ws_bytes(I))
-    ws = torch.empty(need, dtype=torch.uint8, device=ctx.device)
+    ws = workspace(ctx, None, need, ctx.device)
     check(ctx.lib.el_ease_weights(ctx.handle, ctx.stream(), _ptr(P, torch.float64, "P"), int(P.stride(0)), I,
                                   _ptr(out, torch.float32, "B"), int(out.stride(0)), C.c_void_p(ws.data_ptr()), need), "el_ease_weights")
     return out
@@ -880,7 +877,8 @@ def spmm_csr_f64(ctx, A, X, out=None, holder=None, verify=True):
     if out is None:
         out = torch.empty((A.n_rows, R), dtype=torch.float64, device=ctx.device)
     holder = holder if holder is not None else ctx
-    ws, need = _als_ws(ctx, holder, "_spmm64_ws", int(ctx.lib.el_spmm_csr_f64_ws_bytes(int(A.n_pieces), R)))
+    need = int(ctx.lib.el_spmm_csr_f64_ws_bytes(int(A.n_pieces), R))
+    ws = _ptr(workspace(holder, "_spmm64_ws", need, ctx.device)) if need else None
     status = getattr(holder, "_spmm64_status", None)
     if status is None:
         status = holder._spmm64_status = torch.empty(2, dtype=torch.int32, device=ctx.device)
@@ -904,7 +902,8 @@ def gram_f64(ctx, Y, out=None, holder=None):
     n, R = int(Y.shape[0]), int(Y.shape[1])
     if out is None:
         out = torch.empty((R, R), dtype=torch.float64, device=ctx.device)
-    ws, need = _als_ws(ctx, holder if holder is not None else ctx, "_gram64_ws", int(ctx.lib.el_gram_f64_ws_bytes(n, R)))
+    need = int(ctx.lib.el_gram_f64_ws_bytes(n, R))
+    ws = _ptr(workspace(holder if holder is not None else ctx, "_gram64_ws", need, ctx.device)) if need else None
     check(ctx.lib.el_gram_f64(ctx.handle, ctx.stream(), _rows_ptr(Y, torch.float64, "Y"), int(Y.stride(0)), n, R,
                               _ptr(out, torch.float64, "G"), int(out.stride(0)), ws, need), "el_gram_f64")
     return out
@@ -915,7 +914,8 @@ def psvd_orth(ctx, Y, holder=None, status=None):
     (int32[1]: the smallest refused column, 0x7fffffff = none); reading it is the caller's synchronisation."""
     n, R = int(Y.shape[0]), int(Y.shape[1])
     holder = holder if holder is not None else ctx
-    ws, need = _als_ws(ctx, holder, "_orth_ws", int(ctx.lib.el_psvd_orth_ws_bytes(n, R)))
+    need = int(ctx.lib.el_psvd_orth_ws_bytes(n, R))
+    ws = _ptr(workspace(holder, "_orth_ws", need, ctx.device)) if need else None
     if status is None:
         status = torch.empty(1, dtype=torch.int32, device=ctx.device)
     check(ctx.lib.el_psvd_orth(ctx.handle, ctx.stream(), _rows_ptr(Y, torch.float64, "Y"), int(Y.stride(0)), n, R,
@@ -945,7 +945,8 @@ def psvd_signs(ctx, T, holder=None):
     """svd_flip's signs of the columns of fp64 T [n, k] (el_psvd_signs): a device tensor double[k] of +-1."""
     n, k = int(T.shape[0]), int(T.shape[1])
     signs = torch.empty(k, dtype=torch.float64, device=ctx.device)
-    ws, need = _als_ws(ctx, holder if holder is not None else ctx, "_signs_ws", int(ctx.lib.el_psvd_signs_ws_bytes(n, k)))
+    need = int(ctx.lib.el_psvd_signs_ws_bytes(n, k))
+    ws = _ptr(workspace(holder if holder is not None else ctx, "_signs_ws", need, ctx.device)) if need else None
     check(ctx.lib.el_psvd_signs(ctx.handle, ctx.stream(), _rows_ptr(T, torch.float64, "T"), int(T.stride(0)), n, k,
                                 _ptr(signs, torch.float64), ws, need), "el_psvd_signs")
     return signs
@@ -1165,11 +1166,7 @@ def rec_metrics(ctx, rec_idx, test, threshold, cutoff, u_start=0, sums=None, per
     if sums is None:
         sums = torch.zeros(8, dtype=torch.float64, device=ctx.device)
     rows = torch.empty((n, 8), dtype=torch.float64, device=ctx.device) if per_user else None
-    need = int(ctx.lib.el_rec_metrics_ws_bytes(int(n)))
-    ws = getattr(ctx, "_metrics_ws", None)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=ctx.device)
-        ctx._metrics_ws = ws
+    ws = workspace(ctx, "_metrics_ws", max(int(ctx.lib.el_rec_metrics_ws_bytes(int(n))), 8), ctx.device)
     disc = discount_table(cutoff, ctx.device)
     check(ctx.lib.el_rec_metrics(ctx.handle, ctx.stream(), _ptr(rec_idx, torch.int32), int(ld), int(u_start), int(u_start + n),
                                  _ptr(test.indptr, torch.int64), _ptr(test.indices, torch.int32),
@@ -1200,15 +1197,6 @@ class DeviceItemTables:
         self.epc = torch.from_numpy(np.ascontiguousarray(tables.epc, dtype=np.float64)).to(device)
 
 
-def _beyond_ws(ctx, n_users, n_items):
-    need = int(ctx.lib.el_beyond_ws_bytes(int(n_users), int(n_items)))
-    ws = getattr(ctx, "_beyond_ws", None)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=ctx.device)
-        ctx._beyond_ws = ws
-    return ws
-
-
 def beyond_metrics(ctx, rec_idx, test, train, tables, threshold, cutoff, u_start=0, hist=None, sums=None, per_user=False, direct=False):
     """First pass of the beyond-accuracy metrics over the users of rec_idx's rows (absolute ids u_start ...): their terms ADDED to
     `sums` (float64[BEYOND_SUMS]) and their lists to the item histogram `hist` (int32[num_items]); train = the DeviceCSR of the
@@ -1220,7 +1208,7 @@ def beyond_metrics(ctx, rec_idx, test, train, tables, threshold, cutoff, u_start
     if hist is None:
         hist = torch.zeros(I, dtype=torch.int32, device=ctx.device)
     rows = torch.empty((n, BEYOND_SUMS), dtype=torch.float64, device=ctx.device) if per_user else None
-    ws = _beyond_ws(ctx, n, I)
+    ws = workspace(ctx, "_beyond_ws", max(int(ctx.lib.el_beyond_ws_bytes(int(n), int(I))), 8), ctx.device)
     disc = discount_table(cutoff, ctx.device)
     check(ctx.lib.el_beyond_metrics(ctx.handle, ctx.stream(), _ptr(rec_idx, torch.int32), int(ld), int(u_start), int(u_start + n),
                                     _ptr(test.indptr, torch.int64), _ptr(test.indices, torch.int32),
@@ -1239,7 +1227,7 @@ def beyond_hist_finish(ctx, hist):
     I = int(hist.shape[0])
     stats = torch.empty(4, dtype=torch.int64, device=ctx.device)
     nov = torch.empty(I, dtype=torch.float64, device=ctx.device)
-    ws = _beyond_ws(ctx, 0, I)
+    ws = workspace(ctx, "_beyond_ws", max(int(ctx.lib.el_beyond_ws_bytes(0, int(I))), 8), ctx.device)
     check(ctx.lib.el_beyond_hist_finish(ctx.handle, ctx.stream(), _ptr(hist, torch.int32), I, _ptr(stats, torch.int64),
                                         _ptr(nov, torch.float64), C.c_void_p(ws.data_ptr()), int(ws.numel())), "el_beyond_hist_finish")
     return stats, nov
@@ -1250,7 +1238,7 @@ def beyond_entropy(ctx, rec_idx, test, nov, cutoff, u_start=0, total=None):
     n, ld = rec_idx.shape
     if total is None:
         total = torch.zeros(1, dtype=torch.float64, device=ctx.device)
-    ws = _beyond_ws(ctx, n, int(nov.shape[0]))
+    ws = workspace(ctx, "_beyond_ws", max(int(ctx.lib.el_beyond_ws_bytes(int(n), int(nov.shape[0]))), 8), ctx.device)
     check(ctx.lib.el_beyond_entropy(ctx.handle, ctx.stream(), _ptr(rec_idx, torch.int32), int(ld), int(u_start), int(u_start + n),
                                     _ptr(test.indptr, torch.int64), int(cutoff), int(nov.shape[0]), _ptr(nov, torch.float64),
                                     _ptr(total, torch.float64), C.c_void_p(ws.data_ptr()), int(ws.numel())), "el_beyond_entropy")
@@ -1348,19 +1336,16 @@ class MtReplaySampler:
         self.lists.indptr = torch.from_numpy(lp).to(ctx.device)
         self.lists.indices = torch.from_numpy(li if li.size else np.zeros(1, np.int32)).to(ctx.device)
         self.state = torch.from_numpy(mt19937_init_state(seed).view(np.int32).copy()).to(ctx.device)
-        self._ws = None
 
     def sample(self, n):
         ctx = self.ctx
-        need = int(ctx.lib.el_bpr_sample_mt19937_ws_bytes(int(n)))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=ctx.device)
+        ws = workspace(self, "_ws", int(ctx.lib.el_bpr_sample_mt19937_ws_bytes(int(n))), ctx.device)
         out = tuple(torch.empty(n, dtype=torch.int32, device=ctx.device) for _ in range(3))
         check(ctx.lib.el_bpr_sample_mt19937(ctx.handle, ctx.stream(), C.c_void_p(self.state.data_ptr()),
                                             _ptr(self.lists.indptr, torch.int64), _ptr(self.lists.indices, torch.int32),
                                             *_csr_ptrs(self.pos), int(self.pos.n_rows), int(self.pos.n_cols), int(n),
                                             _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
-                                            C.c_void_p(self._ws.data_ptr()), self._ws.numel()), "el_bpr_sample_mt19937")
+                                            _ptr(ws), ws.numel()), "el_bpr_sample_mt19937")
         return out
 
 
@@ -1793,10 +1778,8 @@ class BprmfDeviceState:
                 self.ensure_rows(B)
             self._ensure_old(B)
         if algo == _lib.EL_BPR_SORTED or (algo == _lib.EL_BPR_AUTO and B >= 2048) or self.compact:
-            need = int(self.ctx.lib.el_bprmf_ws_bytes(int(B), int(self.U), int(self.I), int(self.F)))
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=self.ctx.device)
-            ws, ws_bytes = C.c_void_p(self._ws.data_ptr()), self._ws.numel()
+            t = self.sort_workspace(B, "_ws")
+            ws, ws_bytes = _ptr(t), t.numel()
         check(self.ctx.lib.el_bprmf_train_step(self.ctx.handle, self.ctx.stream(), C.byref(self._c),
                                                _ptr(u, torch.int32, "u"), _ptr(i, torch.int32, "i"),
                                                _ptr(j, torch.int32, "j"), int(B), float(lr), float(l_w), float(l_b),
@@ -1809,17 +1792,15 @@ class BprmfDeviceState:
         """First half of train_step: loss + the summed row gradients of the batch (what OptimizerV2 receives after its segment
         sum, BPRMF_batch_model.py:77) into gGu (or the compact rows) / gGi / gBi, no optimiser.  apply() consumes them."""
         B = u.numel()
-        need = int(self.ctx.lib.el_bprmf_ws_bytes(int(B), int(self.U), int(self.I), int(self.F)))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.ctx.device)
+        ws = self.sort_workspace(B, "_ws")
         self.ensure_rows(B)
         if self.deferred or self.item_fused:
             # the two-call form runs the every-row passes (apply); the rows are brought up to date and the features stand aside
             self._two_pass(True)
         check(self.ctx.lib.el_bprmf_grads(self.ctx.handle, self.ctx.stream(), C.byref(self._c), _ptr(u, torch.int32, "u"),
                                           _ptr(i, torch.int32, "i"), _ptr(j, torch.int32, "j"), int(B), float(l_w), float(l_b),
-                                          int(self.step + 1), _ptr(self.loss, torch.float64), C.c_void_p(self._ws.data_ptr()),
-                                          self._ws.numel()), "el_bprmf_grads")
+                                          int(self.step + 1), _ptr(self.loss, torch.float64), _ptr(ws), ws.numel()),
+              "el_bprmf_grads")
 
     def apply(self, lr):
         """Second half: the optimiser (TF-dense Adam / dense SGD) on the accumulated gradients; accumulators come back clean."""
@@ -1833,9 +1814,10 @@ class BprmfDeviceState:
 
     # -- the step in two halves for a software pipeline: ordering a batch (prep + radix sort) reads only its triplets, so the
     #    batch of step t+1 can be drawn and ordered on a side stream while step t's segment kernels and optimiser pass run
-    def sort_workspace(self, B):
-        """A workspace tensor for presort() / train_step_presorted() (el_bprmf_ws_bytes): one per batch in flight."""
-        return torch.empty(int(self.ctx.lib.el_bprmf_ws_bytes(int(B), int(self.U), int(self.I), int(self.F))), dtype=torch.uint8, device=self.ctx.device)
+    def sort_workspace(self, B, attr=None):
+        """A workspace tensor for presort() / train_step_presorted() (el_bprmf_ws_bytes): one per batch in flight -- or, with
+        attr, the one this state keeps for its own steps."""
+        return workspace(self, attr, int(self.ctx.lib.el_bprmf_ws_bytes(int(B), int(self.U), int(self.I), int(self.F))), self.ctx.device)
 
     def presort(self, u, i, j, ws):
         """First half of the sorted gradient path: (row, triplet) pairs of the batch, ordered, into `ws` (current stream)."""
@@ -1875,8 +1857,7 @@ class BprmfDeviceState:
             self.ensure_rows(B)
         self._ensure_old(B)
         need = int(self.ctx.lib.el_bprmf_ws_bytes(int(B), int(self.U), int(self.I), int(self.F))) if (B >= 2048 or self.compact) else 0
-        if need and (self._ws is None or self._ws.numel() < need):
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.ctx.device)
+        ws = workspace(self, "_ws", need, self.ctx.device) if need else None
         lneed = int(self.ctx.lib.el_bprmf_train_loop_ws_bytes(int(events), int(B)))
         buf = getattr(self, "_loop_ws", None)
         if buf is None or buf.numel() != lneed:                          # (a stable address keeps the captured graph valid)
@@ -1885,7 +1866,7 @@ class BprmfDeviceState:
             self.ctx.handle, self.ctx.stream(), C.byref(self._c), *_csr_ptrs(pos), int(seed) & 0xFFFFFFFFFFFFFFFF,
             int(first_sample), int(events), int(B), float(lr), float(l_w), float(l_b), self.opt, int(self.step + 1),
             lr_t.ctypes.data_as(C.c_void_p), _ptr(self.loss, torch.float64), algo,
-            C.c_void_p(self._ws.data_ptr()) if need else None, self._ws.numel() if need else 0,
+            _ptr(ws), ws.numel() if ws is not None else 0,
             C.c_void_p(buf.data_ptr()), lneed, C.c_void_p(sampler_meta(self.ctx, pos).data_ptr())), "el_bprmf_train_loop")
         self._advance(steps)                                    # (consecutive steps: not a jump of the counter)
         self._after_steps(steps)
@@ -2015,7 +1996,7 @@ class LightGcnDeviceState:
         if graph.N != self.U + self.I or graph.n0 != self.U:
             raise ValueError("the graph does not describe these tables")
         need = int(ctx.lib.el_lightgcn_ws_bytes(self.U, self.I, self.F, self.n_layers))
-        self._ws = torch.empty(max(need, 16), dtype=torch.uint8, device=ctx.device)
+        self._ws = workspace(self, None, max(need, 16), ctx.device)
 
     @property
     def Gu(self):
@@ -2655,9 +2636,9 @@ class NmfDeviceState:
         #                                                                                   on every call, one workspace for the evaluation)
         if need == 0:
             raise _lib.ElliotHipError("el_nmf_score_topk does not take this network shape / k (NmfDeviceState.fused_supported)")
-        ws = getattr(self, "_score_ws", None)
-        if ws is None or ws.numel() < need:
-            ws = self._score_ws = torch.empty(need, dtype=torch.uint8, device=self.ctx.device)
+        held = getattr(self, "_score_ws", None)
+        ws = workspace(self, "_score_ws", need, self.ctx.device)
+        if ws is not held:
             items_unchanged = False
         out_idx = torch.empty((n, k), dtype=torch.int32, device=self.ctx.device)
         out_val = torch.empty((n, k), dtype=torch.float32, device=self.ctx.device)
@@ -2801,22 +2782,19 @@ class PwmfDeviceState:
             setattr(self, "v" + n, z(t) if adam else None)
         self.loss = torch.zeros(1, dtype=torch.float64, device=dev)
         self.step = 0
-        self._ws = None
         p = lambda t: None if t is None else t.data_ptr()
         self._c = _lib.PwmfState(U=self.U, I=self.I, F=self.F, kind=PW_KINDS[kind], alpha=self.alpha, l_w=self.l_w,
                                  **{pre + n: p(getattr(self, pre + n)) for pre in ("", "g", "m", "v") for n in names})
 
-    def _workspace(self, n):
+    def _step_ws(self, n):
         need = int(self.ctx.lib.el_pwmf_ws_bytes(int(n), int(self.U), int(self.I), int(self.F)))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.ctx.device)
-        return C.c_void_p(self._ws.data_ptr()), need
+        return _ptr(workspace(self, "_ws", need, self.ctx.device)), need
 
     def train_step(self, u, i, label, lr, side="both"):
         self.step += 1
         self._margin = _PW_MARGIN
         n = u.numel()
-        ws, need = self._workspace(n)
+        ws, need = self._step_ws(n)
         lr_t = adam_lr_t(lr, self.step) if self.optimizer == "adam" else float(lr)
         check(self.ctx.lib.el_pwmf_train_step(self.ctx.handle, self.ctx.stream(), C.byref(self._c), _ptr(u, torch.int32),
                                               _ptr(i, torch.int32), _ptr(label, torch.float32), int(n),
@@ -2833,11 +2811,9 @@ class PwmfDeviceState:
             raise ValueError("train_loop: the positives' CSR must describe this state's users x items")
         adam = self.optimizer == "adam"
         lr_t = np.array([adam_lr_t(lr, self.step + 1 + k) if adam else lr for k in range(steps)], dtype=np.float32)
-        ws, need = self._workspace(min(int(B), int(events)) if events < B else int(B))
+        ws, need = self._step_ws(min(int(B), int(events)) if events < B else int(B))
         lneed = int(self.ctx.lib.el_pwmf_train_loop_ws_bytes(int(events), int(B)))
-        buf = getattr(self, "_loop_ws", None)
-        if buf is None or buf.numel() < lneed:
-            buf = self._loop_ws = torch.empty(lneed, dtype=torch.uint8, device=self.ctx.device)
+        buf = workspace(self, "_loop_ws", lneed, self.ctx.device)
         self._margin = _PW_MARGIN
         check(self.ctx.lib.el_pwmf_train_loop(
             self.ctx.handle, self.ctx.stream(), C.byref(self._c), *_csr_ptrs(pos), C.c_void_p(sampler_meta(self.ctx, pos).data_ptr()),
@@ -2851,7 +2827,7 @@ class PwmfDeviceState:
         """Forward + loss + gradient sums only (multi-GPU: a batch-mean loss runs over n_global samples); the accumulators of
         `side` are complete on return -- item_grads() lists the replicated ones a data-parallel caller all-reduces."""
         n = u.numel()
-        ws, need = self._workspace(n)
+        ws, need = self._step_ws(n)
         check(self.ctx.lib.el_pwmf_grads(self.ctx.handle, self.ctx.stream(), C.byref(self._c), _ptr(u, torch.int32),
                                          _ptr(i, torch.int32), _ptr(label, torch.float32), int(n),
                                          int(n if n_global is None else n_global), PW_SIDES[side], _ptr(self.loss, torch.float64),
@@ -2952,25 +2928,22 @@ class CmlDeviceState(BprmfDeviceState):
 
     def __init__(self, ctx, Gu, Gi, Bi):
         super().__init__(ctx, Gu, Gi, Bi, optimizer="adam_tf_dense", compact_user_grads=False)
-        self._cml_ws = None
         self._items2 = None
 
     def train_step(self, u, i, j, lr, l_w, l_b, margin):
         self.step += 1
         B = u.numel()
-        need = self._cml_workspace(B, B)
+        ws, need = self._cml_ws_for(B, B)
         check(self.ctx.lib.el_cml_train_step(self.ctx.handle, self.ctx.stream(), C.byref(self._c), _ptr(u, torch.int32),
                                              _ptr(i, torch.int32), _ptr(j, torch.int32), int(B), float(l_w), float(l_b),
                                              float(margin), int(self.step), float(adam_lr_t(lr, self.step)),
-                                             _ptr(self.loss, torch.float64), C.c_void_p(self._cml_ws.data_ptr()), need),
+                                             _ptr(self.loss, torch.float64), ws, need),
               "el_cml_train_step")
         self._items2 = None
 
-    def _cml_workspace(self, B, B_all):
+    def _cml_ws_for(self, B, B_all):
         need = int(self.ctx.lib.el_cml_ws_bytes(int(B), int(B_all), int(self.U), int(self.I), int(self.F)))
-        if self._cml_ws is None or self._cml_ws.numel() < need:
-            self._cml_ws = torch.empty(need, dtype=torch.uint8, device=self.ctx.device)
-        return need
+        return _ptr(workspace(self, "_cml_ws", need, self.ctx.device)), need
 
     def forward_de(self, u, i, j, l_w, l_b):
         """Phase 1 of the multi-GPU step: the rank's D_a, E_a (device float [B] each) + its share of the regulariser."""
@@ -2985,12 +2958,12 @@ class CmlDeviceState(BprmfDeviceState):
     def grads_de(self, u, i, j, l_w, l_b, margin, D, E, D_all, E_all):
         """Phase 2: the rank's triplets against the gathered D / E of the global batch; gradients stay in the accumulators."""
         B, B_all = u.numel(), D_all.numel()
-        need = self._cml_workspace(B, B_all)
+        ws, need = self._cml_ws_for(B, B_all)
         check(self.ctx.lib.el_cml_grads(self.ctx.handle, self.ctx.stream(), C.byref(self._c), _ptr(u, torch.int32),
                                         _ptr(i, torch.int32), _ptr(j, torch.int32), int(B), float(l_w), float(l_b), float(margin),
                                         _ptr(D, torch.float32), _ptr(E, torch.float32), _ptr(D_all, torch.float32),
                                         _ptr(E_all, torch.float32), int(B_all), _ptr(self.loss, torch.float64),
-                                        C.c_void_p(self._cml_ws.data_ptr()), need), "el_cml_grads")
+                                        ws, need), "el_cml_grads")
         self._items2 = None
 
     # -- optimiser alone (multi-GPU step): the split form overlaps the item-gradient all-reduce with the user rows' update

@@ -287,29 +287,24 @@ class HipBackend:
         import ctypes as C
         st, ctx = self.state, self.ctx
         B = u.numel()
-        need = int(ctx.lib.el_bprmf_ws_bytes(int(B), int(st.U), int(st.I), int(st.F)))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=ctx.device)
+        ws = ops.workspace(self, "_ws", int(ctx.lib.el_bprmf_ws_bytes(int(B), int(st.U), int(st.I), int(st.F))), ctx.device)
         if self._dU is None or self._dU.shape[0] != B:
             self._dU = torch.empty((B, st.F), dtype=torch.float32, device=ctx.device)
         ops.check(ctx.lib.el_bprmf_shard_grads(ctx.handle, ctx.stream(), C.byref(st._c), ops._ptr(u, torch.int32),
                                                ops._ptr(i, torch.int32), ops._ptr(j, torch.int32), int(B), float(l_w),
                                                float(l_b), int(st.step + 1), ops._ptr(self._dU, torch.float32),
-                                               ops._ptr(st.loss, torch.float64), C.c_void_p(self._ws.data_ptr()),
-                                               self._ws.numel()), "el_bprmf_shard_grads")
+                                               ops._ptr(st.loss, torch.float64), ops._ptr(ws), ws.numel()),
+                  "el_bprmf_shard_grads")
         return self._dU
 
     def reduce_user_rows(self, ids, rows):
-        import ctypes as C
         st, ctx = self.state, self.ctx
         n = ids.numel()
-        need = int(ctx.lib.el_rows_segment_sum_ws_bytes(int(n), int(st.U)))
-        if self._ws2 is None or self._ws2.numel() < need:
-            self._ws2 = torch.empty(need, dtype=torch.uint8, device=ctx.device)
+        ws = ops.workspace(self, "_ws2", int(ctx.lib.el_rows_segment_sum_ws_bytes(int(n), int(st.U))), ctx.device)
         ops.check(ctx.lib.el_rows_segment_sum(ctx.handle, ctx.stream(), ops._ptr(ids, torch.int32),
                                               ops._ptr(rows, torch.float32), int(n), int(st.F), int(st.U),
-                                              ops._ptr(st.gGu, torch.float32), C.c_void_p(self._ws2.data_ptr()),
-                                              self._ws2.numel()), "el_rows_segment_sum")
+                                              ops._ptr(st.gGu, torch.float32), ops._ptr(ws), ws.numel()),
+                  "el_rows_segment_sum")
 
     def apply(self, lr):
         import ctypes as C
@@ -371,13 +366,11 @@ class HipDenseBackend:
         C = self._C
         st, ctx = self.state, self.ctx
         B = u.numel()
-        need = int(ctx.lib.el_bprmf_ws_bytes(int(B), int(st.U), int(st.I), int(st.F)))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=ctx.device)
+        ws = ops.workspace(self, "_ws", int(ctx.lib.el_bprmf_ws_bytes(int(B), int(st.U), int(st.I), int(st.F))), ctx.device)
         ops.check(ctx.lib.el_bprmf_grads(ctx.handle, ctx.stream(), C.byref(st._c), ops._ptr(u, torch.int32),
                                          ops._ptr(i, torch.int32), ops._ptr(j, torch.int32), int(B), float(l_w), float(l_b),
-                                         int(st.step + 1), ops._ptr(st.loss, torch.float64), C.c_void_p(self._ws.data_ptr()),
-                                         self._ws.numel()), "el_bprmf_grads")
+                                         int(st.step + 1), ops._ptr(st.loss, torch.float64), ops._ptr(ws), ws.numel()),
+                  "el_bprmf_grads")
         return st.gGu
 
     def apply_own(self, lr):
@@ -447,32 +440,29 @@ class HipUserShardBackend:
                                           fused_user_step=False)
         self._ws = None
 
-    def _workspace(self, B):
+    def _sort_ws(self, B):
         st, ctx = self.state, self.ctx
-        need = int(ctx.lib.el_bprmf_ws_bytes(int(B), int(st.U), int(st.I), int(st.F)))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=ctx.device)
+        return ops.workspace(self, "_ws", int(ctx.lib.el_bprmf_ws_bytes(int(B), int(st.U), int(st.I), int(st.F))), ctx.device)
 
     def presort(self, u_local, i, j):
         """Order a batch for grads(..., presorted=True): reads only the triplets, so it can run under the previous step's
         collective.  One workspace: the previous batch's segment kernels are done (stream order) before this overwrites it."""
-        import ctypes as C
         st, ctx = self.state, self.ctx
-        self._workspace(u_local.numel())
+        ws = self._sort_ws(u_local.numel())
         ops.check(ctx.lib.el_bprmf_presort(ctx.handle, ctx.stream(), ops._ptr(u_local, torch.int32), ops._ptr(i, torch.int32),
                                            ops._ptr(j, torch.int32), int(u_local.numel()), int(st.U), int(st.I),
-                                           C.c_void_p(self._ws.data_ptr()), self._ws.numel()), "el_bprmf_presort")
+                                           ops._ptr(ws), ws.numel()), "el_bprmf_presort")
 
     def grads(self, u_local, i, j, l_w, l_b, presorted=False):
         import ctypes as C
         st, ctx = self.state, self.ctx
         B = u_local.numel()
-        self._workspace(B)
+        ws = self._sort_ws(B)
         st.ensure_rows(B)                                       # (compact user-gradient rows: one slot per sorted position)
         fn = ctx.lib.el_bprmf_grads_presorted if presorted else ctx.lib.el_bprmf_grads
         ops.check(fn(ctx.handle, ctx.stream(), C.byref(st._c), ops._ptr(u_local, torch.int32), ops._ptr(i, torch.int32),
                      ops._ptr(j, torch.int32), int(B), float(l_w), float(l_b), int(st.step + 1), ops._ptr(st.loss, torch.float64),
-                     C.c_void_p(self._ws.data_ptr()), self._ws.numel()), "el_bprmf_grads")
+                     ops._ptr(ws), ws.numel()), "el_bprmf_grads")
 
     def item_grads(self):
         return [self.state.item_grad_flat]                    # gGi rows + gBi in one buffer: one collective per step
@@ -489,16 +479,13 @@ class HipUserShardBackend:
         """gGi / gBi <- the sum, per item, of the gathered (id, row) records of every rank -- the rows in the gathered order, which is
         the same on every rank (el_rows_segment_sum: stable sort by id, one lane group walks a segment): identical replicas.  Every row
         a rank's own batch touched is among the records, so every stale local row is overwritten with the global sum."""
-        import ctypes as C
         st, ctx = self.state, self.ctx
         n = int(ids_all.numel())
-        need = int(ctx.lib.el_rows_segment_sum_ws_bytes(n, int(st.I)))
-        if getattr(self, "_ws_rows", None) is None or self._ws_rows.numel() < need:
-            self._ws_rows = torch.empty(need, dtype=torch.uint8, device=ctx.device)
+        ws = ops.workspace(self, "_ws_rows", int(ctx.lib.el_rows_segment_sum_ws_bytes(n, int(st.I))), ctx.device)
         for rows, F, out in ((rows_all, st.F, st.gGi), (bias_all, 1, st.gBi)):
             ops.check(ctx.lib.el_rows_segment_sum(ctx.handle, ctx.stream(), ops._ptr(ids_all, torch.int32), ops._ptr(rows, torch.float32), n,
-                                                  int(F), int(st.I), ops._ptr(out, torch.float32), C.c_void_p(self._ws_rows.data_ptr()),
-                                                  self._ws_rows.numel()), "el_rows_segment_sum")
+                                                  int(F), int(st.I), ops._ptr(out, torch.float32), ops._ptr(ws), ws.numel()),
+                      "el_rows_segment_sum")
 
     def _apply(self, c_state, lr):
         import ctypes as C
