@@ -231,11 +231,12 @@ extern "C" int el_spmm_csr_f32(el_ctx* ctx, void* stream, const el_graph_csr* g,
                                float* Y1) {
     if (int rc = el_bind(ctx)) return rc;
     if (int rc = spmm_check("el_spmm_csr_f32", g, F)) return rc;
-    EL_REQUIRE(X0 && Y0 && (g->n0 == g->N || (X1 && Y1)), "el_spmm_csr_f32: null table");
+    // a table without rows (n0 == 0: the first, n0 == N: the second) may be null: no row index ever resolves into it
+    EL_REQUIRE((g->n0 == 0 || (X0 && Y0)) && (g->n0 == g->N || (X1 && Y1)), "el_spmm_csr_f32: null table");
     EL_REQUIRE((((uintptr_t)X0 | (uintptr_t)X1 | (uintptr_t)Y0 | (uintptr_t)Y1 | (uintptr_t)g->part) & 15) == 0, "el_spmm_csr_f32: tables must be 16-byte aligned");
     SpmmParams p;
     spmm_fill(p, g, F);
-    p.X0 = X0, p.X1 = X1 ? X1 : X0, p.Y0 = Y0, p.Y1 = Y1 ? Y1 : Y0;
+    p.X0 = X0 ? X0 : X1, p.X1 = X1 ? X1 : X0, p.Y0 = Y0 ? Y0 : Y1, p.Y1 = Y1 ? Y1 : Y0;     // (N >= 1: one of each pair has rows)
     return spmm_launch((hipStream_t)stream, p);
 }
 

@@ -13,7 +13,7 @@ from .... import ops
 from ....dataset.samplers import custom_sampler
 from ...base_recommender_model import BaseRecommenderModel, init_charger, param
 from ...recommender_utils_mixin import RecMixin
-from .LightGCN_model import LightGCNModel
+from .LightGCN_model import LightGCNModel, require_multiple_of_4
 
 
 class LightGCN(RecMixin, BaseRecommenderModel):
@@ -32,6 +32,7 @@ class LightGCN(RecMixin, BaseRecommenderModel):
             param("n_fold", "n_fold", 1),
         ]
         self.autoset_params()
+        require_multiple_of_4("latent_dim (factors)", self._factors)   # (a deviation from the reference, refused before the device is touched)
         self._ctx = ops.get_context(max(int(getattr(self._config, "gpu", 0) or 0), 0))
         replay = getattr(self._params, "sampler", "philox") == "replay"
         self._sampler = custom_sampler.Sampler(self._data.i_train_dict if replay else self._data.sp_i_train, ctx=self._ctx, replay=replay)

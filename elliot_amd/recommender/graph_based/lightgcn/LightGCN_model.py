@@ -5,6 +5,9 @@ head with the doubled L2 term (:136-167) + Keras Adam; scoring through `recommen
 The tables start at ZERO, as the reference's `_create_weights` (:63-65) creates them -- where every gradient of the head vanishes and
 the model never moves; `init_weights=(Gu, Gi)` injects tables (tests, warm starts).  `n_fold` (:47, :96-109) only cuts TensorFlow's
 sparse product into row blocks: accepted and ignored.
+
+Deviation from the reference: `embed_k` (the plugin's `latent_dim`, shortcut `factors`) must be a multiple of 4 -- the propagation kernels move rows as
+16-byte vectors -- and the constructor refuses any other width with a ValueError; the reference accepts any width.
 """
 import pickle
 
@@ -15,9 +18,30 @@ from .... import ops
 from ...latent_factor_models.BPRMF_batch.BPRMF_batch_model import DeferredLoss
 
 
+ADAM_MOMENTS = ("mGu", "vGu", "mGi", "vGi")
+
+
+def require_multiple_of_4(name, value):
+    """The graph kernels' row width: refused here, by parameter name, before anything reaches the device."""
+    if int(value) < 4 or int(value) % 4:
+        raise ValueError(f"{name}={value}: the graph propagation kernels need a multiple of 4 (rows move as 16-byte vectors)")
+
+
+def restore_adam(b, d, complete):
+    """The Adam state of the tables (a BprmfDeviceState) from a saved dict.  A dict without the moments (an older file) restarts
+    Adam as a whole -- step 0 on zero moments -- so that a restored step count never meets moments it does not belong to."""
+    b.step = int(d.get("_step", 0)) if complete else 0
+    for n in ADAM_MOMENTS:
+        if complete:
+            getattr(b, n).copy_(torch.from_numpy(d[n]))
+        else:
+            getattr(b, n).zero_()
+
+
 class LightGCNModel:
     def __init__(self, num_users, num_items, learning_rate, embed_k, l_w, n_layers, n_fold, adjacency, laplacian, random_seed,
                  name="LightGCN", ctx=None, init_weights=None, **kwargs):
+        require_multiple_of_4("embed_k (latent_dim, factors)", embed_k)
         self.ctx = ctx or ops.get_context(0)
         self.num_users, self.num_items, self.embed_k = int(num_users), int(num_items), int(embed_k)
         self.learning_rate, self.l_w, self.n_layers, self.n_fold = learning_rate, l_w, int(n_layers), n_fold
@@ -61,7 +85,7 @@ class LightGCNModel:
         b = self.state.bpr
         b.sync()
         d = {"Gu": b.Gu.cpu().numpy(), "Gi": b.Gi.cpu().numpy(), "_step": b.step}
-        for n in ("mGu", "vGu", "mGi", "vGi"):
+        for n in ADAM_MOMENTS:
             d[n] = getattr(b, n).cpu().numpy()
         return d
 
@@ -70,10 +94,7 @@ class LightGCNModel:
         self._weights_version += 1
         b.Gu.copy_(torch.from_numpy(d["Gu"]))
         b.Gi.copy_(torch.from_numpy(d["Gi"]))
-        b.step = int(d.get("_step", 0))
-        for n in ("mGu", "vGu", "mGi", "vGi"):
-            if n in d:
-                getattr(b, n).copy_(torch.from_numpy(d[n]))
+        restore_adam(b, d, all(n in d for n in ADAM_MOMENTS))
 
     def save_weights(self, path):
         with open(path, "wb") as f:

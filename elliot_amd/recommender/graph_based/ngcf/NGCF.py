@@ -13,6 +13,7 @@ from ....dataset.samplers import custom_sampler
 from ...base_recommender_model import BaseRecommenderModel, init_charger, param
 from ...recommender_utils_mixin import RecMixin
 from ..lightgcn.LightGCN import LightGCN
+from ..lightgcn.LightGCN_model import require_multiple_of_4
 from .NGCF_model import NGCFModel
 
 
@@ -44,6 +45,9 @@ class NGCF(RecMixin, BaseRecommenderModel):
         ]
         self.autoset_params()
         self._n_layers = len(self._weight_size)
+        require_multiple_of_4("latent_dim (factors)", self._factors)   # (a deviation from the reference, refused before the device is touched)
+        for w in self._weight_size:
+            require_multiple_of_4("weight_size entry", w)
         self._ctx = ops.get_context(max(int(getattr(self._config, "gpu", 0) or 0), 0))
         replay = getattr(self._params, "sampler", "philox") == "replay"
         self._sampler = custom_sampler.Sampler(self._data.i_train_dict if replay else self._data.sp_i_train, ctx=self._ctx, replay=replay)

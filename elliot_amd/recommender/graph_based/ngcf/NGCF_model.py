@@ -7,6 +7,10 @@ creates them (:88-91) -- a state in which the layer-0 columns never receive a gr
 injects them; the GraphLayers follow GlorotUniform ([kin, kout] and [1, kout] limits, :95-104; TensorFlow's seeded stream itself is not
 reproducible).  node_dropout (:56-60, :153-158): one fixed sparsification of the Laplacian at construction, keep probability
 node_dropout[0], kept entries scaled by 1 / keep.  `n_fold` only cuts TensorFlow's sparse product into row blocks: ignored.
+
+Deviation from the reference: `embed_k` (the plugin's `latent_dim`, shortcut `factors`) and every entry of `weight_size` must be multiples of 4 -- the
+propagation kernels move rows as 16-byte vectors -- and the constructor refuses any other width with a ValueError; the reference accepts
+any width.
 """
 import pickle
 
@@ -15,11 +19,15 @@ import torch
 
 from .... import ops
 from ...latent_factor_models.BPRMF_batch.BPRMF_batch_model import DeferredLoss
+from ..lightgcn.LightGCN_model import ADAM_MOMENTS, require_multiple_of_4, restore_adam
 
 
 class NGCFModel:
     def __init__(self, num_users, num_items, learning_rate, embed_k, l_w, weight_size, n_layers, node_dropout, message_dropout, n_fold,
                  adjacency, laplacian, random_seed, name="NGFC", ctx=None, init_weights=None, **kwargs):
+        require_multiple_of_4("embed_k (latent_dim, factors)", embed_k)
+        for w in weight_size:
+            require_multiple_of_4("weight_size entry", w)
         self.ctx = ctx or ops.get_context(0)
         self.num_users, self.num_items, self.embed_k = int(num_users), int(num_items), int(embed_k)
         self.learning_rate, self.l_w = learning_rate, l_w
@@ -80,18 +88,30 @@ class NGCFModel:
     def get_model_state(self):
         st, b = self.state, self.state.bpr
         b.sync()
-        return {"Gu": b.Gu.cpu().numpy(), "Gi": b.Gi.cpu().numpy(), "_step": b.step,
-                "layers": [{k: v.cpu().numpy() for k, v in l.items()} for l in st.layers]}
+        d = {"Gu": b.Gu.cpu().numpy(), "Gi": b.Gi.cpu().numpy(), "_step": b.step,
+             "layers": [{k: v.cpu().numpy() for k, v in l.items()} for l in st.layers],
+             "layer_slots": [{k: (m.cpu().numpy(), v.cpu().numpy()) for k, (m, v) in sl.items()} for sl in st.slots]}
+        for n in ADAM_MOMENTS:
+            d[n] = getattr(b, n).cpu().numpy()
+        return d
 
     def set_model_state(self, d):
         st, b = self.state, self.state.bpr
         self._weights_version += 1
         b.Gu.copy_(torch.from_numpy(d["Gu"]))
         b.Gi.copy_(torch.from_numpy(d["Gi"]))
-        b.step = int(d.get("_step", 0))
         for l, src in zip(st.layers, d.get("layers", [])):
             for k, v in src.items():
                 l[k].copy_(torch.from_numpy(v))
+        # the tables' moments, the GraphLayers' (m, v) slots and the step count (which also seeds the message-dropout mask) go together
+        complete = all(n in d for n in ADAM_MOMENTS) and "layer_slots" in d
+        restore_adam(b, d, complete)
+        for sl, src in zip(st.slots, d["layer_slots"] if complete else [{}] * len(st.slots)):
+            for k, (m, v) in sl.items():
+                if complete:
+                    m.copy_(torch.from_numpy(src[k][0])), v.copy_(torch.from_numpy(src[k][1]))
+                else:
+                    m.zero_(), v.zero_()
 
     def save_weights(self, path):
         with open(path, "wb") as f:

@@ -1200,6 +1200,7 @@ typedef struct el_graph_csr {
 } el_graph_csr;
 
 /* Y = L X for the stacked table X = [X0 (n0 rows); X1 (N - n0 rows)] of width F (a multiple of 4, 16-byte aligned tables).
+ * A half without rows (X0 / Y0 when n0 == 0, X1 / Y1 when n0 == N) may be NULL.
  * Replaces: tf.sparse.sparse_dense_matmul(A_fold_hat[f], ego_embeddings) over all folds (LightGCN_model.py:78-82, NGCF_model.py:118-121). */
 int el_spmm_csr_f32(el_ctx* ctx, void* stream, const el_graph_csr* g, const float* X0, const float* X1, int32_t F, float* Y0, float* Y1);
 

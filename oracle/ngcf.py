@@ -18,6 +18,7 @@ stream: only rate 0 is restated (the device draws its own counter-based mask).""
 import numpy as np
 
 from . import bprmf_batch as ob
+from . import tf_clauses
 
 f32 = np.float32
 
@@ -63,8 +64,8 @@ class NGCFOracle:
             for k, p in l.items():
                 m, v = sl[k]
                 g = f32(2.0 * self.l_w) * p
-                m += (g - m) * f32(1 - 0.9)                                             # [TF] Keras dense apply
-                v += (g * g - v) * f32(1 - 0.999)
+                m += (g - m) * tf_clauses.one_minus(0.9)                                # [TF] Keras dense apply; 1 - beta formed in fp32
+                v += (g * g - v) * tf_clauses.one_minus(0.999)                          # (clause adam_one_minus_beta_in_fp32)
                 p -= (m * lr_t) / (np.sqrt(v) + f32(1e-7))
         return loss
 
