@@ -22,6 +22,8 @@ EL_BPR_ATOMIC = 1
 EL_BPR_SORTED = 2
 EL_KNN_COSINE = 0
 EL_KNN_DOT = 1
+EL_PROFILE_ADD = 0
+EL_PROFILE_LAST = 1
 EL_SLIM_COLUMN = 0
 EL_SLIM_REFERENCE = 1
 EL_ALS_SKIP_EMPTY = 1
@@ -275,6 +277,12 @@ PROTOTYPES = {
                                C.c_int, C.c_int32, C.c_int64, C.c_int32, _i64p, _i32p, _f32p, C.c_void_p, C.c_size_t]),
     "el_knn_score_topk": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _f32p, _i64p, _i32p, _f32p, C.c_int64, C.c_int64,
                                     C.c_int64, _i64p, _i32p, _i64p, _i32p, C.c_int32, _i32p, _f32p]),
+    "el_profile_ws_bytes": (C.c_size_t, [C.c_int64]),
+    "el_profile_build": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _i64p, _i32p, _f64p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+                                   C.c_int, _i64p, _i32p, _f32p, C.c_int64, C.c_void_p, C.c_size_t]),
+    "el_knn_f32_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "el_knn_build_f32": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _f32p, _i64p, _i32p, _f32p, C.c_int64, C.c_int64, C.c_int32,
+                                   C.c_int, _i64p, _i32p, _f32p, C.c_void_p, C.c_size_t]),
     "el_csr_row_l1": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _f32p, C.c_int64, _f32p]),
     "el_rp3_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int64]),
     "el_rp3_rows": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _f32p, _i64p, _i32p, _f32p, _f64p, C.c_int64, C.c_int64,

@@ -17,11 +17,10 @@
 #include "el_common.h"
 
 #include "el_knn_csr.h"
+#include "el_knn_select.h"
 #include "el_topk_common.h"
 
-#define KNN_BUILD_THREADS 256
 #define KNN_TILE_BYTES 65536                      // LDS accumulator tile of both kernels
-#define KNN_MAX_NEIGHBORS 2048                    // running top-N lives in LDS next to the tile
 #define KNN_MAX_K 4032                            // running top-k of the scoring wave (cap = el_select_cap(k) <= 4096)
 
 namespace {
@@ -60,37 +59,6 @@ __device__ __forceinline__ float knn_value(int64_t cnt, double nc, int64_t nx_in
     if (sim == EL_KNN_DOT) return (float)cd;
     const double nx = __dmul_rn((double)nx_int, inv_s2);
     return (float)__ddiv_rn(cd, __dsqrt_rn(__dmul_rn(nc, nx)));
-}
-
-// block-wide bitonic sort (descending) of n = 2^m keys in LDS
-__device__ void knn_block_bitonic_desc(u64* a, int n) {
-    for (int size = 2; size <= n; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = threadIdx.x; t < (n >> 1); t += blockDim.x) {
-                int i = 2 * t - (t & (stride - 1));
-                int j = i + stride;
-                bool desc = ((i & size) == 0);
-                u64 x = a[i], y = a[j];
-                if (desc ? (x < y) : (x > y)) {
-                    a[i] = y;
-                    a[j] = x;
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// keep the best N of the cnt keys in keys[0 .. cap); every thread passes the same cnt
-__device__ void knn_block_compact(u64* keys, int cnt, int cap, int N, int* s_cnt, u64* s_tau) {
-    for (int t = cnt + (int)threadIdx.x; t < cap; t += blockDim.x) keys[t] = 0ull;
-    __syncthreads();
-    knn_block_bitonic_desc(keys, cap);
-    if (threadIdx.x == 0) {
-        *s_cnt = cnt < N ? cnt : N;
-        *s_tau = cnt >= N ? keys[N - 1] : 0ull;
-    }
-    __syncthreads();
 }
 
 // One workgroup per target column c: expand every t of P row c over Q row t into an LDS tile of the x range (integer
@@ -254,8 +222,6 @@ __global__ __launch_bounds__(64) void k_knn_score(KnnScore p) {
         p.out_val[urel * p.k + t] = ov;
     }
 }
-
-int knn_build_cap(int N) { return el_pow2(2 * N + KNN_BUILD_THREADS); }
 
 struct KnnWs {          // the workspace of el_knn_build: KnnBuild's nrm, lcnt, rowcnt [n] and lx, lv [n, N], then the list-to-CSR arrays
     int64_t* nrm;

@@ -14,6 +14,7 @@ from types import SimpleNamespace
 import numpy as np
 
 from .dataset import DataSet, _split_flags, np_seed_state
+from .side_information import coordinate
 
 COLUMNS = ("userId", "itemId", "rating", "timestamp")
 
@@ -244,6 +245,8 @@ class DataSetLoader:
         self.config = config
         dc = config.data_config
         strategy = _get(dc, "strategy")
+        sides = _get(dc, "side_information")
+        self.side_information = None
         binarize = bool(getattr(config, "binarize", False))
 
         def prep(fr):
@@ -257,8 +260,12 @@ class DataSetLoader:
                 self.tuple_list = [([(train, prep(read_ratings(resolve(_get(dc, "validation_path")))))], test)]
             else:
                 self.tuple_list = [(train, test)]
+            if sides:
+                self.tuple_list, self.side_information = coordinate(self.tuple_list, sides, resolve=resolve)
         elif strategy == "dataset":
             frame = read_ratings(resolve(_get(dc, "dataset_path")))
+            if sides:                                   # dataset.py:96-98: before prefiltering and splitting
+                frame, self.side_information = coordinate(frame, sides, resolve=resolve)
             frame = prefilter(frame, getattr(config, "prefiltering", None))
             self.tuple_list = split(prep(frame), config.splitting, getattr(config, "random_seed", 42))
         else:
@@ -266,9 +273,11 @@ class DataSetLoader:
 
     def generate_dataobjects(self):
         out = []
+        side = self.side_information
         for train_val, test in self.tuple_list:
             if isinstance(train_val, list):
-                out.append([DataSet(self.config, _triples(train), _triples(test), _triples(val)) for train, val in train_val])
+                out.append([DataSet(self.config, _triples(train), _triples(test), _triples(val), side_information=side)
+                            for train, val in train_val])
             else:
-                out.append([DataSet(self.config, _triples(train_val), _triples(test))])
+                out.append([DataSet(self.config, _triples(train_val), _triples(test), side_information=side)])
         return out

@@ -24,16 +24,27 @@ import scipy.sparse as sp
 
 
 class DataSet:
-    def __init__(self, config, train, test, val=None, public_users=None, public_items=None):
+    def __init__(self, config, train, test, val=None, public_users=None, public_items=None, side_information=None):
         """train/test/val: (user, item, rating) triples of *public* ids as three aligned arrays.
 
         Private ids follow the reference: users in first-appearance order of the train rows (dataset.py:248),
         items in the iteration order of the Python set of train items (dataset.py:202) unless `public_items`
-        fixes the order (synthetic data whose ids are already dense)."""
+        fixes the order (synthetic data whose ids are already dense).
+        side_information: the loader's namespace (dataset/side_information.py); aligned with this training fold unless
+        config.align_side_with_train is False (dataset.py:194-197).  None: an empty namespace, nothing else changes."""
         self.config = config
         tu, ti, tr = (np.asarray(x) for x in train)
         if public_users is None:
             public_users = self._first_appearance(tu)
+        if side_information is None:
+            self.side_information = SimpleNamespace()
+        elif getattr(config, "align_side_with_train", True):
+            from .side_information import align_with_training
+            first = self._first_appearance(tu)
+            self.side_information = align_with_training(first.tolist(), self._items_in_dict_order(tu, ti, first).tolist(),
+                                                        side_information)
+        else:
+            self.side_information = side_information
         if public_items is None:
             # user-major order of appearance, as `{k for a in train_dict.values() for k in a}` inserts them (dataset.py:202)
             public_items = pyset_order(self._items_in_dict_order(tu, ti, public_users))
@@ -188,6 +199,19 @@ class DataSet:
         indptr = np.zeros(self.num_users + 1, dtype=np.int64)
         np.cumsum(np.bincount(pu, minlength=self.num_users), out=indptr[1:])
         return indptr, pi.astype(np.int32), r
+
+    def dict_order_csr(self):
+        """The train matrix with every row in the order of train_dict[u] (file order, a repeated pair at its first position):
+        (indptr int64 [U + 1], private item ids int32) -- the order the reference's per-user dict loops visit the items in."""
+        tu, ti, _ = self._train_triples
+        pu = self._to_private(tu, self._pub_u)
+        order = self._group_stable(pu, self.num_users)
+        pu, pi = pu[order], self._to_private(ti, self._pub_i)[order]
+        _, first = np.unique(pu * self.num_items + pi, return_index=True)
+        keep = np.sort(first)
+        indptr = np.zeros(self.num_users + 1, dtype=np.int64)
+        np.cumsum(np.bincount(pu[keep], minlength=self.num_users), out=indptr[1:])
+        return indptr, pi[keep].astype(np.int32)
 
     def get_test(self):
         return self.test_dict

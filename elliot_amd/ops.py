@@ -333,6 +333,77 @@ def knn_score_topk(ctx, A, A_vals, B, B_vals, u_start, u_stop, k, excl=None, can
 
 
 # ------------------------------------------------------------------------------------------
+# attribute-aware baselines (AttributeItemKNN / AttributeUserKNN / VSM)
+# ------------------------------------------------------------------------------------------
+PROFILE_MODES = {"add": _lib.EL_PROFILE_ADD, "last": _lib.EL_PROFILE_LAST}
+
+
+def profile_build(ctx, r_indptr, r_indices, F, f_weights, mode, by_len):
+    """User profiles over item features (compute_binary_profile / TFIDF.get_profiles + build_feature_sparse_values of the
+    reference's attribute plug-ins) as a host scipy CSR [U, nF] float32, columns ascending, zeros kept.
+    r_indptr / r_indices: the train rows in train_dict order; F: scipy CSR [I, nF], the features of every item (its values are
+    not read); f_weights: float64 per entry of F (mode "last") or None; mode "add" | "last"; by_len: divide by the row length."""
+    import scipy.sparse as sp
+    if mode not in PROFILE_MODES:
+        raise ValueError(f"profile_build: mode {mode!r} is not supported; supported: {sorted(PROFILE_MODES)}")
+    if mode == "last" and f_weights is None:
+        raise ValueError("profile_build: mode 'last' needs one weight per entry of F")
+    r_indptr = np.ascontiguousarray(r_indptr, dtype=np.int64)
+    U, (I, nF) = r_indptr.shape[0] - 1, F.shape
+    if U < 1 or I < 1 or nF < 1:
+        raise ValueError(f"profile_build: empty operand (users {U}, items {I}, features {nF})")
+    dev = ctx.device
+    Rc, Fc = DeviceCSR(r_indptr, r_indices, I, dev), DeviceCSR(F.indptr, F.indices, nF, dev)
+    fw = None
+    if mode == "last":
+        fw = np.ascontiguousarray(f_weights, dtype=np.float64)
+        if fw.shape[0] != F.nnz:
+            raise ValueError("profile_build: one weight per entry of F")
+        fw = torch.from_numpy(fw if fw.shape[0] else np.zeros(1, np.float64)).to(dev)
+    # an entry per feature touched: at most the features of the user's items, and at most nF
+    deg = np.concatenate([[0], np.cumsum(np.diff(F.indptr)[np.asarray(r_indices, dtype=np.int64)])])
+    cap = int(np.minimum(deg[r_indptr[1:]] - deg[r_indptr[:-1]], nF).sum())
+    out_indptr = torch.empty(U + 1, dtype=torch.int64, device=dev)
+    out_indices = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    out_vals = torch.empty(max(cap, 1), dtype=torch.float32, device=dev)
+    need = int(ctx.lib.el_profile_ws_bytes(U))
+    ws = workspace(ctx, None, need, dev)
+    check(ctx.lib.el_profile_build(ctx.handle, ctx.stream(), _ptr(Rc.indptr), _ptr(Rc.indices), _ptr(Fc.indptr), _ptr(Fc.indices),
+                                   _ptr(fw), U, I, nF, PROFILE_MODES[mode], 1 if by_len else 0, _ptr(out_indptr), _ptr(out_indices),
+                                   _ptr(out_vals), cap, C.c_void_p(ws.data_ptr()), need), "el_profile_build")
+    indptr = out_indptr.cpu().numpy()
+    nnz = int(indptr[-1])
+    assert nnz <= cap
+    return sp.csr_matrix((out_vals[:nnz].cpu().numpy(), out_indices[:nnz].cpu().numpy(), indptr), shape=(U, nF))
+
+
+def knn_build_f32(ctx, A, n_neighbors, sim):
+    """Similarity.initialize of attribute_user_knn_similarity.py: W of the rows of A (scipy sparse [n, n_other], float32 values,
+    explicit zeros kept), top-`n_neighbors` non-zeros per column, self-similarity kept.  fp64 sums in the stored (ascending)
+    order of A's rows.  Returns (DeviceCSR W, float32 values tensor) as knn_build."""
+    import scipy.sparse as sp
+    if sim not in KNN_SIMILARITIES:
+        raise ValueError(f"similarity {sim!r} is not supported; supported: {sorted(KNN_SIMILARITIES)}")
+    P = sp.csr_matrix(A, dtype=np.float32)
+    P.sum_duplicates()
+    P.sort_indices()
+    Q = P.T.tocsr()
+    Q.sort_indices()
+    n, n_other = P.shape
+    dev = ctx.device
+    Pc, Qc = DeviceCSR(P.indptr, P.indices, n_other, dev), DeviceCSR(Q.indptr, Q.indices, n, dev)
+    pvt, qvt = device_values(P.data, dev), device_values(Q.data, dev)
+    need = int(ctx.lib.el_knn_f32_ws_bytes(int(n), int(n_neighbors)))
+    ws = workspace(ctx, None, need, dev)
+    w_indptr, w_indices, w_vals = _w_alloc(ctx, n, min(int(n_neighbors), n))
+    check(ctx.lib.el_knn_build_f32(ctx.handle, ctx.stream(), _ptr(Pc.indptr), _ptr(Pc.indices), _ptr(pvt), _ptr(Qc.indptr),
+                                   _ptr(Qc.indices), _ptr(qvt), int(n), int(n_other), int(n_neighbors), KNN_SIMILARITIES[sim],
+                                   _ptr(w_indptr), _ptr(w_indices), _ptr(w_vals), C.c_void_p(ws.data_ptr()), need),
+          "el_knn_build_f32")
+    return _w_result(w_indptr, w_indices, w_vals)
+
+
+# ------------------------------------------------------------------------------------------
 # RP3beta (graph_based/RP3beta; beta = 0 is P3alpha)
 # ------------------------------------------------------------------------------------------
 RP3_ROWS_WS_BYTES = 1 << 28          # bound of el_rp3_rows' workspace: longer row ranges are built in pieces

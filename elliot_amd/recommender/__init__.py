@@ -19,6 +19,9 @@ from .neural.NeuMF.neural_matrix_factorization import NeuMF
 from .neural.GeneralizedMF.generalized_matrix_factorization import GMF
 from .knn.item_knn.item_knn import ItemKNN
 from .knn.user_knn.user_knn import UserKNN
+from .knn.attribute_item_knn.attribute_item_knn import AttributeItemKNN
+from .knn.attribute_user_knn.attribute_user_knn import AttributeUserKNN
+from .content_based.VSM.vector_space_model import VSM
 from .latent_factor_models.iALS.iALS import iALS
 from .latent_factor_models.WRMF.wrmf import WRMF
 from .autoencoders.EASE_R.ease_r import EASER
@@ -27,4 +30,5 @@ from .latent_factor_models.PureSVD.pure_svd import PureSVD
 
 __all__ = ["BaseRecommenderModel", "init_charger", "RecMixin", "BPRMF_batch", "BPRMF", "MultiVAE", "MultiDAE", "NeuMF", "GMF",
            "MF", "PMF", "FunkSVD", "LogisticMatrixFactorization", "LMF", "CML", "MF2020", "LightGCN", "NGCF", "ProxyRecommender",
-           "ItemKNN", "UserKNN", "iALS", "WRMF", "EASER", "RP3beta", "Slim", "PureSVD"]
+           "ItemKNN", "UserKNN", "iALS", "WRMF", "EASER", "RP3beta", "Slim", "PureSVD",
+           "AttributeItemKNN", "AttributeUserKNN", "VSM"]

@@ -1,7 +1,8 @@
 """Minimal experiment runner for the latent-factor plugins (single configuration, no hyperopt).
 
 Honours the slice of Elliot's YAML schema (elliot/namespace/namespace_model.py:28-61) that the hello-world style
-experiments use: dataset, data_config {strategy: dataset|fixed, dataset_path | train_path/test_path/validation_path}, prefiltering, binarize,
+experiments use: dataset, data_config {strategy: dataset|fixed, dataset_path | train_path/test_path/validation_path,
+side_information: [{dataloader: ItemAttributes, attribute_file}]}, align_side_with_train, prefiltering, binarize,
 splitting {test_splitting, validation_splitting: every strategy of base_splitter.py}, negative_sampling {strategy: random|fixed}, top_k, evaluation {cutoffs, simple_metrics,
 relevance_threshold}, gpu, path_output_rec_*, models {<Model>: {meta: {...}, <hyper-params>}}.
 The full driver (HPO, result handlers, statistical tests: elliot/run.py:39-148) stays Elliot's: plug the models in
@@ -69,6 +70,7 @@ def load_data_objects(exp, cfg, base_dir):
     cfg.data_config = SimpleNamespace(**dc)
     cfg.random_seed = exp.get("random_seed", 42)
     cfg.binarize = bool(exp.get("binarize", False))
+    cfg.align_side_with_train = exp.get("align_side_with_train", True)      # namespace_model.py:237-238
     if exp.get("prefiltering"):
         pf = exp["prefiltering"]
         cfg.prefiltering = [_to_ns(x) for x in (pf if isinstance(pf, list) else [pf])]      # namespace_model.py:177-182

@@ -69,6 +69,38 @@ def small_dataset(n_users=200, n_items=150, seed=0, mean_log=2.3, sigma_log=0.7,
     return indptr, indices, d
 
 
+def small_item_attributes(n_items, n_features=40, missing=(), extra=(), seed=7):
+    """Lines of a tiny ItemAttributes file for small_dataset: [(item, [feature id, ...])] in file order.  1-8 Zipf-distributed
+    features per item out of `n_features` (ids 500, 503, ...: not dense, so CPython's set order is not the sorted one), the
+    first feature repeated on every tenth line; the items in `missing` have no line, `extra` are offsets behind the last item
+    for lines about items nobody rated."""
+    rs = np.random.RandomState(seed)
+    p = 1.0 / (np.arange(n_features) + 1.0)
+    p /= p.sum()
+    lines = []
+    for item in list(range(n_items)) + [n_items + d for d in extra]:
+        feats = (500 + 3 * rs.choice(n_features, size=rs.randint(1, 9), replace=False, p=p)).tolist()
+        if item % 10 == 0:
+            feats.append(feats[0])
+        if item not in missing:
+            lines.append((item, feats))
+    return lines
+
+
+def write_attribute_sample(folder, n_users=200, n_items=150, seed=0):
+    """dataset.tsv (user, item, rating) and item_attributes.tsv of config_files/sample_attribute_knn_amd.yml."""
+    import os
+    _, indices, itd = small_dataset(n_users, n_items, seed=seed)
+    os.makedirs(folder, exist_ok=True)
+    with open(os.path.join(folder, "dataset.tsv"), "w") as fh:
+        for u, d in itd.items():
+            for i, r in d.items():
+                fh.write(f"{u}\t{i}\t{int(r)}\n")
+    with open(os.path.join(folder, "item_attributes.tsv"), "w") as fh:
+        for item, feats in small_item_attributes(int(indices.max()) + 1, missing=(3, 17, 58, 99, 120), extra=(5, 9, 20)):
+            fh.write("\t".join(str(x) for x in [item] + feats) + "\n")
+
+
 def zipf_csr_device(n_users, n_items, device, mean_log=3.9, sigma_log=1.0, dmin=5, dmax=2000, zipf_a=1.0, seed=1234):
     """Same construction as zipf_csr, generated on the GPU with torch (data plumbing only: 1e6 x 1e5 with
     ~8e7 interactions takes < 2 s there vs ~1 min in NumPy).  Returns torch tensors (int64 indptr, int32 indices)."""

@@ -492,6 +492,52 @@ int el_knn_score_topk(el_ctx* ctx, void* stream,
                       const int64_t* cand_indptr, const int32_t* cand_indices,
                       int32_t k, int32_t* out_idx, float* out_val);
 
+/* ---- attribute-aware baselines: AttributeItemKNN / AttributeUserKNN / VSM ------------------------------------------- */
+
+#define EL_PROFILE_ADD 0
+#define EL_PROFILE_LAST 1
+
+/* Replaces the user-profile dict loops of the reference (attribute_user_knn.py:125-131 compute_binary_profile, both
+ * tfidf_utils.py TFIDF.get_profiles, vector_space_model.py:122-129) and build_feature_sparse_values (:142-151):
+ *   R (users -> items) in STORED order = the order of train_dict[u]; items -> features as a CSR whose columns are distinct
+ *   inside an item (any order) with fp64 weights f_vals (EL_PROFILE_LAST; may be null for EL_PROFILE_ADD).
+ *   One fp64 cell per (user, feature), the user's items taken one after the other; len = the length of R row u:
+ *   EL_PROFILE_ADD   cell = cell + w from +0 for every item that carries the feature, w = 1 / len (by_len) or 1: the repeated
+ *                    addition of the same double, not count / len
+ *   EL_PROFILE_LAST  cell = the weight of the feature in the LAST item that carries it (get_profiles' comprehension reads an
+ *                    empty dict, so nothing is summed), then cell / len (by_len) or the cell itself
+ *   every operation a correctly rounded fp64 add / divide; the result is rounded once to float.
+ * Output: CSR over users, an entry for every feature touched (a zero value is kept), columns ascending: out_indptr
+ * int64[n_users + 1], out_indices / out_vals with room for out_cap entries -- sum over users of min(n_features, sum of the
+ * feature counts of the user's items) always suffices; the nnz is out_indptr[n_users], and when it exceeds out_cap the rows
+ * that would not fit are left unwritten.  The same bytes on every run.  ws = el_profile_ws_bytes(n_users) bytes.          */
+size_t el_profile_ws_bytes(int64_t n_users);
+int el_profile_build(el_ctx* ctx, void* stream,
+                     const int64_t* r_indptr, const int32_t* r_indices,
+                     const int64_t* f_indptr, const int32_t* f_indices, const double* f_vals,
+                     int64_t n_users, int64_t n_items, int64_t n_features, int mode, int by_len,
+                     int64_t* out_indptr, int32_t* out_indices, float* out_vals, int64_t out_cap,
+                     void* ws, size_t ws_bytes);
+
+/* el_knn_build for FLOAT-valued rows (Similarity.initialize of attribute_user_knn_similarity.py:34-82: cosine_similarity(A) or
+ * A @ A.T of the profile matrix, cut to the N largest non-zeros of every column, self-similarity kept):
+ *   P (targets -> t) and Q (t -> x, columns ascending) are the two orientations of A with float values.
+ *   dot[c,x] = sum_t P[c,t] Q[t,x] in fp64: acc = acc + p q from +0, one correctly rounded add per entry t of P row c IN ITS
+ *   STORED ORDER (the product of two floats is exact in fp64); n_c = sum_t P[c,t]^2 likewise.  No float atomics: the order is
+ *   fixed, so the same input gives the same bytes on every run, and scipy's fp64 A64 @ A64.T (csr_matmat adds in the same
+ *   order) gives the same doubles.
+ *   EL_KNN_DOT    value = (float)dot
+ *   EL_KNN_COSINE value = (float)(dot / sqrt(n_c * n_x)), fp64 correctly rounded, rounded once to float (sklearn normalises
+ *                 the float32 rows first: within (2 L + 8) 2^-24 relative for rows of L entries)
+ *   column c of W keeps min(N, non-zeros) entries by (value desc, index asc); an entry needs dot != 0 and value != 0.
+ * Output and workspace as el_knn_build: ws = el_knn_f32_ws_bytes(n, n_neighbors) bytes.  N <= 2048.                        */
+size_t el_knn_f32_ws_bytes(int64_t n, int32_t n_neighbors);
+int el_knn_build_f32(el_ctx* ctx, void* stream,
+                     const int64_t* p_indptr, const int32_t* p_indices, const float* p_vals,
+                     const int64_t* q_indptr, const int32_t* q_indices, const float* q_vals,
+                     int64_t n, int64_t n_other, int32_t n_neighbors, int sim,
+                     int64_t* w_indptr, int32_t* w_indices, float* w_vals, void* ws, size_t ws_bytes);
+
 /* ---- RP3beta (graph_based/RP3beta; beta = 0 is P3alpha) ------------------------------------------------------------- */
 
 /* Replaces sklearn's normalize(X, norm='l1', axis=1) on a CSR (rp3beta.py:78 Pui, :91 Piu, :147 normalize_similarity):
