@@ -280,6 +280,7 @@ PROTOTYPES = {
     "el_profile_ws_bytes": (C.c_size_t, [C.c_int64]),
     "el_profile_build": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _i64p, _i32p, _f64p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                    C.c_int, _i64p, _i32p, _f32p, C.c_int64, C.c_void_p, C.c_size_t]),
+    "el_kahfm_init": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _i64p, _i32p, _f64p, C.c_int64, C.c_int64, C.c_int64, _f64p, _f64p]),
     "el_knn_f32_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "el_knn_build_f32": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _f32p, _i64p, _i32p, _f32p, C.c_int64, C.c_int64, C.c_int32,
                                    C.c_int, _i64p, _i32p, _f32p, C.c_void_p, C.c_size_t]),

@@ -872,7 +872,7 @@ static int launch_bprsgd(const el_bprsgd_state& st, const int32_t* u, const int3
     const int vw = vec ? 2 : 1;
     int cpl = 1;
     int lpt = el_pick_lpt(st.F, vw, &cpl);
-    EL_REQUIRE(cpl <= 4, "el_bprsgd_apply: F=%d too large for this build", st.F);
+    if (cpl > 4) return el_bprsgd_launch_wide(st, u, i, j, first, n, s);      // el_bprsgd_wide.hip: one workgroup per triplet
     int64_t threads = n * lpt;
     unsigned grid = (unsigned)((threads + 255) / 256);
 #define EL_SGD_LAUNCH(VW_, CPL_) \

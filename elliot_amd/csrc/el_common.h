@@ -131,6 +131,9 @@ int el_bprmf_apply_items_adam(el_ctx* ctx, hipStream_t s, const el_bprmf_state& 
 int el_bprmf_check_state(const el_bprmf_state* stp, const int32_t* u, const int32_t* i, const int32_t* j,
                          double* loss_out, int opt, int32_t step, bool* vec, bool* rows_mode);
 __global__ void k_adam_dense(float* th, float* g, float* m, float* v, int64_t n, float lr_t, float b1, float b2, float eps);
+// (el_bprsgd_wide.hip) el_bprsgd_apply for the rows k_bprsgd_apply cannot hold in registers
+__attribute__((visibility("hidden"))) int el_bprsgd_launch_wide(const el_bprsgd_state& st, const int32_t* u, const int32_t* i, const int32_t* j,
+                                                                int64_t first, int64_t n, hipStream_t s);
 // (el_bpr_sorted.hip)
 extern "C" __attribute__((visibility("hidden"))) int el_bprmf_train_step_sorted(el_ctx* ctx, void* stream, const el_bprmf_state* stp, const int32_t* u,
                                           const int32_t* i, const int32_t* j, int64_t B, float lr, float l_w, float l_b, int opt,

@@ -1,6 +1,7 @@
-"""Side information of the data plane: item attributes, narrowed together with the rating frames and with each training fold.
+"""Side information of the data plane: item attributes and knowledge-graph features, narrowed together with the rating frames and
+with each training fold.
 
-What Elliot's `ItemAttributes` loader, its loader coordination and `DataSet`'s alignment with the training fold produce, on this
+What Elliot's `ItemAttributes` and `ChainedKG` loaders, their coordination and `DataSet`'s alignment with the training fold produce, on this
 package's column frames.  One routine, `_settle`, serves both stages: it intersects the running (users, items) with what every
 loader covers until nothing shrinks any more.
 
@@ -11,8 +12,11 @@ and documented where they happen; everything else here is free:
   * every intersection has the running set on the LEFT and the loader's set on the right, a loader narrows its own sets with its own
     set on the left;
   * before a fold is aligned the loader's two sets are rebuilt from a list of their elements (what `copy.deepcopy` does to a set).
-`feature_map` stays the unfiltered map of the file: TF-IDF counts its documents over it.
+`feature_map` of `ItemAttributes` stays the unfiltered map of the file: TF-IDF counts its documents over it.  `ChainedKG` hands
+out its REDUCED map instead (features of the selected properties that occur often enough, items that keep one), reduced again
+every time the loader is narrowed.
 """
+from collections import Counter
 from types import SimpleNamespace
 
 import numpy as np
@@ -65,7 +69,86 @@ class ItemAttributes:
                                public_features={f: p for p, f in enumerate(features)})
 
 
-LOADERS = {"ItemAttributes": ItemAttributes}
+def read_feature_names(path):
+    """{feature id: its chain of properties} of a `id \t <p1><p2>...<pn>` file, cut as the reference cuts it: the text behind the
+    tab is split on '><', the first piece loses its first character and the last piece its last TWO ('>' and the newline -- a last
+    line without a newline loses one character of the name)."""
+    names = {}
+    with open(path) as fh:
+        for line in fh:
+            fields = line.split("\t")
+            chain = fields[1].split("><")
+            chain[0] = chain[0][1:]
+            chain[-1] = chain[-1][:-2]
+            names[int(fields[0])] = chain
+    return names
+
+
+def read_properties(path):
+    """The selected properties, one per line; lines that start with '#' are skipped."""
+    with open(path) as fh:
+        return [line.rstrip("\n") for line in fh if line[0] != "#"]
+
+
+class ChainedKG:
+    """Item features out of a knowledge graph (kahfm_style.py): a feature is a chain of properties that ends in an entity.  Of the
+    file's map the loader keeps the features whose FIRST property is selected (`additive`) or is not selected (not `additive`) --
+    all of them when no property is given -- and that occur more than `threshold` times among the current items; an item left
+    without a feature leaves the loader.  The reduction runs at load and again whenever the loader is narrowed."""
+    name = "ChainedKG"
+    KEYS = ("map", "features", "properties")
+
+    def __init__(self, users, items, map_, feature_names, properties, additive, threshold):
+        self.users, self.items, self.map_ = users, items, map_
+        self.feature_names, self.properties, self.additive, self.threshold = feature_names, properties, additive, threshold
+
+    @classmethod
+    def load(cls, users, items, spec, resolve):
+        paths = {}
+        for key in cls.KEYS:
+            paths[key] = _get(spec, key)
+            if not paths[key]:
+                raise Exception(f"side_information: the ChainedKG loader needs `{key}` (its keys: map, features, properties; "
+                                f"optional additive, threshold)")
+        self = cls(users, items, read_item_attributes(resolve(paths["map"])), read_feature_names(resolve(paths["features"])),
+                   read_properties(resolve(paths["properties"])), _get(spec, "additive", True), _get(spec, "threshold", 10))
+        self._reduce()
+        return self
+
+    def _reduce(self):
+        """reduce_attribute_map_property_selection, then the items that kept a feature (the loader's own set left)."""
+        if not self.properties:
+            acceptable = set(self.feature_names.keys())
+        else:
+            acceptable = {f for f, chain in self.feature_names.items() if (chain[0] in self.properties) == bool(self.additive)}
+        narrowed = {k: v for k, v in self.map_.items() if k in self.items}
+        count = Counter(f for fs in narrowed.values() for f in fs if f in acceptable)
+        popular = {f for f, n in count.items() if n > self.threshold}
+        reduced = {k: [f for f in v if f in popular] for k, v in narrowed.items()}
+        self.map_ = {k: v for k, v in reduced.items() if len(v) > 0}
+        self.items = self.items & set(self.map_.keys())
+
+    def for_fold(self):
+        """A loader of its own for one training fold: both sets rebuilt from lists, and a map of its own (`filter` rewrites it)."""
+        return ChainedKG(set(list(self.users)), set(list(self.items)), {k: list(v) for k, v in self.map_.items()},
+                         self.feature_names, self.properties, self.additive, self.threshold)
+
+    def get_mapped(self):
+        return self.users, self.items
+
+    def filter(self, users, items):
+        self.users, self.items = self.users & users, self.items & items       # the loader's own sets left
+        self._reduce()
+
+    def namespace(self):
+        """What models read as `data.side_information.ChainedKG`; `feature_map` is the reduced map."""
+        features = list({f for i in self.items for f in self.map_[i]})
+        return SimpleNamespace(__name__=self.name, object=self, feature_map=self.map_, features=features,
+                               nfeatures=len(features), private_features=dict(enumerate(features)),
+                               public_features={f: p for p, f in enumerate(features)})
+
+
+LOADERS = {"ItemAttributes": ItemAttributes, "ChainedKG": ChainedKG}
 
 
 def _settle(users, items, loaders):

@@ -377,6 +377,33 @@ def profile_build(ctx, r_indptr, r_indices, F, f_weights, mode, by_len):
     return sp.csr_matrix((out_vals[:nnz].cpu().numpy(), out_indices[:nnz].cpu().numpy(), indptr), shape=(U, nF))
 
 
+def kahfm_init(ctx, r_indptr, r_indices, F, f_weights, P0=None, Q0=None):
+    """The start tables of KAHFMModel.initialize (kahfm_model.py:47-72) as device tensors (P0 [U, nF], Q0 [I, nF]) float64.
+    r_indptr / r_indices: the train rows in train_dict order; F: scipy CSR [I, nF], the features of every item (its values are not
+    read); f_weights: the float64 TF-IDF weight of every entry of F.  P0[u, f]: the weight of f in the last item of row u that
+    carries it, divided by the row's length; Q0[i, f]: the weight.  P0 / Q0: tensors to fill instead of new ones."""
+    r_indptr = np.ascontiguousarray(r_indptr, dtype=np.int64)
+    U, (I, nF) = r_indptr.shape[0] - 1, F.shape
+    if U < 1 or I < 1 or nF < 1:
+        raise ValueError(f"kahfm_init: empty operand (users {U}, items {I}, features {nF})")
+    fw = np.ascontiguousarray(f_weights, dtype=np.float64)
+    if fw.shape[0] != F.nnz:
+        raise ValueError("kahfm_init: one weight per entry of F")
+    dev = ctx.device
+    Rc, Fc = DeviceCSR(r_indptr, r_indices, I, dev), DeviceCSR(F.indptr, F.indices, nF, dev)
+    fw = torch.from_numpy(fw if fw.shape[0] else np.zeros(1, np.float64)).to(dev)
+    if P0 is None:
+        P0 = torch.empty((U, nF), dtype=torch.float64, device=dev)
+    if Q0 is None:
+        Q0 = torch.empty((I, nF), dtype=torch.float64, device=dev)
+    if tuple(P0.shape) != (U, nF) or tuple(Q0.shape) != (I, nF):
+        raise ValueError(f"kahfm_init: P0 {tuple(P0.shape)} / Q0 {tuple(Q0.shape)} do not fit ({U}, {nF}) / ({I}, {nF})")
+    check(ctx.lib.el_kahfm_init(ctx.handle, ctx.stream(), _ptr(Rc.indptr), _ptr(Rc.indices), _ptr(Fc.indptr), _ptr(Fc.indices),
+                                _ptr(fw), U, I, nF, _ptr(P0, torch.float64, "P0"), _ptr(Q0, torch.float64, "Q0")), "el_kahfm_init")
+    torch.cuda.synchronize(dev)                     # the operands above are released on return
+    return P0, Q0
+
+
 def knn_build_f32(ctx, A, n_neighbors, sim):
     """Similarity.initialize of attribute_user_knn_similarity.py: W of the rows of A (scipy sparse [n, n_other], float32 values,
     explicit zeros kept), top-`n_neighbors` non-zeros per column, self-similarity kept.  fp64 sums in the stored (ascending)

@@ -22,6 +22,7 @@ from .knn.user_knn.user_knn import UserKNN
 from .knn.attribute_item_knn.attribute_item_knn import AttributeItemKNN
 from .knn.attribute_user_knn.attribute_user_knn import AttributeUserKNN
 from .content_based.VSM.vector_space_model import VSM
+from .knowledge_aware.kaHFM.kahfm import KaHFM
 from .latent_factor_models.iALS.iALS import iALS
 from .latent_factor_models.WRMF.wrmf import WRMF
 from .autoencoders.EASE_R.ease_r import EASER
@@ -31,4 +32,4 @@ from .latent_factor_models.PureSVD.pure_svd import PureSVD
 __all__ = ["BaseRecommenderModel", "init_charger", "RecMixin", "BPRMF_batch", "BPRMF", "MultiVAE", "MultiDAE", "NeuMF", "GMF",
            "MF", "PMF", "FunkSVD", "LogisticMatrixFactorization", "LMF", "CML", "MF2020", "LightGCN", "NGCF", "ProxyRecommender",
            "ItemKNN", "UserKNN", "iALS", "WRMF", "EASER", "RP3beta", "Slim", "PureSVD",
-           "AttributeItemKNN", "AttributeUserKNN", "VSM"]
+           "AttributeItemKNN", "AttributeUserKNN", "VSM", "KaHFM"]

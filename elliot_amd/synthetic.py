@@ -101,6 +101,59 @@ def write_attribute_sample(folder, n_users=200, n_items=150, seed=0):
             fh.write("\t".join(str(x) for x in [item] + feats) + "\n")
 
 
+KG_PROPERTY, KG_ENTITY = "http://kg.example/property/{0}", "http://kg.example/entity/{0}"
+
+
+def small_kg_features(n_items, n_features=60, per_item=(1, 9), n_properties=6, selected=(0, 1, 2, 3), zipf=True, missing=(),
+                      extra=(), seed=11):
+    """A tiny knowledge-graph side information (the three files of the ChainedKG loader) for small_dataset.  Returns
+    (map_lines, feature_lines, property_lines):
+      map_lines       [(item, [feature id, ...])] in file order: per_item[0] .. per_item[1] - 1 features per item out of
+                      `n_features` (ids 900, 907, ...: not dense), Zipf-distributed or uniform, the first feature repeated on every
+                      tenth line; the items in `missing` have no line, `extra` are offsets behind the last item
+      feature_lines   [(feature id, [property, ..., entity])]: feature k hangs on property k mod n_properties, every third one
+                      through a second property (a chain of two hops); three further features that no item carries
+      property_lines  the text lines of the properties file: a comment, then the `selected` properties"""
+    rs = np.random.RandomState(seed)
+    p = 1.0 / (np.arange(n_features) + 1.0) if zipf else np.ones(n_features)
+    p /= p.sum()
+    map_lines = []
+    for item in list(range(n_items)) + [n_items + d for d in extra]:
+        feats = (900 + 7 * rs.choice(n_features, size=rs.randint(*per_item), replace=False, p=p)).tolist()
+        if item % 10 == 0:
+            feats.append(feats[0])
+        if item not in missing:
+            map_lines.append((item, feats))
+    feature_lines = []
+    for k in range(n_features + 3):
+        chain = [KG_PROPERTY.format(k % n_properties)]
+        if k % 3 == 2:
+            chain.append(KG_PROPERTY.format((k // 3) % n_properties))
+        feature_lines.append((900 + 7 * k, chain + [KG_ENTITY.format(k)]))
+    property_lines = ["# the properties whose features are kept"] + [KG_PROPERTY.format(x) for x in selected]
+    return map_lines, feature_lines, property_lines
+
+
+def write_kg_files(folder, map_lines, feature_lines, property_lines):
+    """map.tsv (item \\t feature ...), features.tsv (feature \\t <property>...<entity>) and properties.conf in `folder`."""
+    import os
+    os.makedirs(folder, exist_ok=True)
+    with open(os.path.join(folder, "map.tsv"), "w") as fh:
+        for item, feats in map_lines:
+            fh.write("\t".join(str(x) for x in [item] + feats) + "\n")
+    with open(os.path.join(folder, "features.tsv"), "w") as fh:
+        for fid, chain in feature_lines:
+            fh.write(f"{fid}\t<{'><'.join(chain)}>\n")
+    with open(os.path.join(folder, "properties.conf"), "w") as fh:
+        fh.write("".join(line + "\n" for line in property_lines))
+
+
+def write_kg_sample(folder, n_users=200, n_items=150, seed=0):
+    """The knowledge-graph files of config_files/sample_kahfm_amd.yml, for the dataset.tsv of write_attribute_sample."""
+    _, indices, _ = small_dataset(n_users, n_items, seed=seed)
+    write_kg_files(folder, *small_kg_features(int(indices.max()) + 1, missing=(3, 17, 58), extra=(5, 9)))
+
+
 def zipf_csr_device(n_users, n_items, device, mean_log=3.9, sigma_log=1.0, dmin=5, dmax=2000, zipf_a=1.0, seed=1234):
     """Same construction as zipf_csr, generated on the GPU with torch (data plumbing only: 1e6 x 1e5 with
     ~8e7 interactions takes < 2 s there vs ~1 min in NumPy).  Returns torch tensors (int64 indptr, int32 indices)."""

@@ -344,7 +344,11 @@ typedef struct el_bprsgd_state {
  * in-place aliasing order (item rows see the UPDATED user row).  Triplets
  * [first, first+n) are applied concurrently: the caller guarantees they are
  * mutually conflict-free (level schedule, el_bprsgd_levels_host) for the result to
- * equal the sequential reference; otherwise the update is Hogwild.               */
+ * equal the sequential reference; otherwise the update is Hogwild.
+ * Any F >= 1.  Rows too wide for the registers of 64 lanes (F > 512, or F > 256 when F is odd or a table is not 16-byte
+ * aligned; KaHFM has one factor per feature) take one workgroup per triplet: the two dot products are summed in a fixed shape
+ * (lane partials in ascending order, a shuffle tree per wave, the four wave sums in wave order), without atomics, so the same
+ * input gives the same bytes on every run.  No element at or beyond F of a row is touched.                              */
 int el_bprsgd_apply(el_ctx* ctx, void* stream, const el_bprsgd_state* st,
                     const int32_t* u, const int32_t* i, const int32_t* j,
                     int64_t first, int64_t n);
@@ -518,6 +522,22 @@ int el_profile_build(el_ctx* ctx, void* stream,
                      int64_t n_users, int64_t n_items, int64_t n_features, int mode, int by_len,
                      int64_t* out_indptr, int32_t* out_indices, float* out_vals, int64_t out_cap,
                      void* ws, size_t ws_bytes);
+
+/* ---- KaHFM: start tables -------------------------------------------------------------------------------------------- */
+
+/* Replaces KAHFMModel.initialize (kahfm_model.py:47-72) together with TFIDF.get_profiles (kaHFM/tfidf_utils.py): the dense fp64
+ * start tables of the factorisation, one factor per feature.
+ *   R (users -> items) in STORED order = the order of train_dict[u]; items -> features as a CSR whose columns are distinct
+ *   inside an item (any order) with fp64 TF-IDF weights f_vals -- the operands of el_profile_build.
+ *   Q0 double[n_items, n_features]: Q0[i, f] = the weight of f in item i, +0.0 elsewhere.
+ *   P0 double[n_users, n_features]: P0[u, f] = the weight of f in the LAST item of row u that carries it (nothing is summed),
+ *   divided by the length of row u -- one correctly rounded fp64 divide; +0.0 elsewhere; a user with an empty row gets +0.0.
+ * Every cell of both tables is written; the same bytes on every run.                                                      */
+int el_kahfm_init(el_ctx* ctx, void* stream,
+                  const int64_t* r_indptr, const int32_t* r_indices,
+                  const int64_t* f_indptr, const int32_t* f_indices, const double* f_vals,
+                  int64_t n_users, int64_t n_items, int64_t n_features,
+                  double* P0, double* Q0);
 
 /* el_knn_build for FLOAT-valued rows (Similarity.initialize of attribute_user_knn_similarity.py:34-82: cosine_similarity(A) or
  * A @ A.T of the profile matrix, cut to the N largest non-zeros of every column, self-similarity kept):
