@@ -1,27 +1,21 @@
-// Attribute-aware baselines (AttributeItemKNN / AttributeUserKNN / VSM): what they need beside el_knn.hip.
+// Attribute-aware baselines (AttributeItemKNN / AttributeUserKNN / VSM): what they need beside el_knn.hip (whose el_knn_build_f32
+// turns the profile rows into W).
 //
 //   el_profile_build   user profiles over item features -- the reference's Python dict loops (compute_binary_profile of
 //                      attribute_user_knn.py / vector_space_model.py, TFIDF.get_profiles of both tfidf_utils.py) -- as a CSR
-//   el_knn_build_f32   el_knn_build for float-valued rows: top-N similarity of profile rows, then W as CSR
 //
 // Numerics contract (tests/helpers/attr_ref.py restates it in NumPy):
 //   profile  one fp64 cell per (user, feature); the user's items are taken in stored order (train_dict order);
 //            ADD:  cell = __dadd_rn(cell, w) from +0 per item that carries the feature, w = __ddiv_rn(1, len) (or 1);
 //            LAST: cell = weight of the feature in the last item that carries it, then __ddiv_rn(cell, len) (or as it is);
 //            an entry for every feature touched (zeros kept), columns ascending, value rounded once to float
-//   dot[c,x] = sum_t P[c,t] Q[t,x] in fp64, one __dadd_rn(acc, __dmul_rn(p, q)) per entry t of P row c IN STORED ORDER, from +0
-//            (the product of two floats is exact in fp64); n_c = sum_t P[c,t]^2 likewise
-//   dot      value = (float)dot
-//   cosine   value = (float)__ddiv_rn(dot, __dsqrt_rn(__dmul_rn(n_c, n_x)))
-//   top-N    entries with dot != 0 and value != 0 only, (value desc, index asc), self-similarity kept
-// No float atomics: every cell is written by one lane per step and the steps are ordered by the wave's own LDS order
-// (profiles) or a workgroup barrier (similarity), so the same input gives the same bytes on every run.
+// No float atomics: every cell is written by one lane per step and the steps are ordered by the wave's own LDS order, so the
+// same input gives the same bytes on every run.
 #include "el_common.h"
 
 #include "el_knn_csr.h"
-#include "el_knn_select.h"
 
-#define ATTR_TILE 8192                            // fp64 cells per LDS tile (64 KiB) of both kernels
+#define ATTR_TILE 8192                            // fp64 cells per LDS tile (64 KiB)
 
 namespace {
 
@@ -120,119 +114,6 @@ size_t profile_carve(int64_t U, void* base, ProfileWs* w) {
     return c.off;
 }
 
-struct KnnBuildF {
-    const int64_t* pp;   // targets -> other side (t), stored order = summation order
-    const int32_t* pi;
-    const float* pv;
-    const int64_t* qp;   // other side (t) -> x, columns ascending
-    const int32_t* qi;
-    const float* qv;
-    int64_t n;
-    int N, sim, tile, cap;
-    const double* nrm;   // [n] sum of squares
-    int32_t* lx;         // [n, N] neighbour lists
-    float* lv;
-    int32_t* lcnt;
-    int32_t* rowcnt;
-};
-
-__global__ __launch_bounds__(256) void k_knn_norms_f32(const int64_t* __restrict__ pp, const float* __restrict__ pv, int64_t n,
-                                                       double* __restrict__ nrm) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n) return;
-    double s = 0.0;
-    for (int64_t e = pp[c]; e < pp[c + 1]; ++e) s = __dadd_rn(s, __dmul_rn((double)pv[e], (double)pv[e]));
-    nrm[c] = s;
-}
-
-// One workgroup per target column c: the whole workgroup walks P row c one entry at a time, its lanes across Q row t
-// (columns distinct: one add per cell per step, a barrier between steps fixes the order), then turns the fp64 tile into values
-// and keeps the running top-N as k_knn_topn does; the next tile of x reuses the LDS.
-__global__ __launch_bounds__(KNN_BUILD_THREADS) void k_knn_topn_f32(KnnBuildF p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    u64* keys = reinterpret_cast<u64*>(smem);                                  // [cap]
-    double* acc = reinterpret_cast<double*>(smem + (size_t)p.cap * 8);         // [tile]
-    __shared__ int s_cnt;
-    __shared__ u64 s_tau;
-    const int tid = threadIdx.x;
-    const int64_t c = blockIdx.x;
-    const int64_t p0 = p.pp[c], p1 = p.pp[c + 1];
-    const double nc = p.nrm[c];
-    if (tid == 0) {
-        s_cnt = 0;
-        s_tau = 0ull;
-    }
-    for (int64_t x0 = 0; x0 < p.n; x0 += p.tile) {
-        const int64_t x1 = (x0 + p.tile < p.n) ? x0 + p.tile : p.n;
-        const int w = (int)(x1 - x0);
-        const bool tiled = p.tile < p.n;
-        for (int i = tid; i < w; i += KNN_BUILD_THREADS) acc[i] = 0.0;
-        __syncthreads();
-        for (int64_t e = p0; e < p1; ++e) {
-            const int32_t t = p.pi[e];
-            const double rv = (double)p.pv[e];
-            int64_t q0 = p.qp[t], q1 = p.qp[t + 1];
-            if (tiled) {
-                q0 = el_lower_bound(p.qi, q0, q1, (int32_t)x0);
-                q1 = el_lower_bound(p.qi, q0, q1, (int32_t)x1);
-            }
-            for (int64_t f = q0 + tid; f < q1; f += KNN_BUILD_THREADS) {
-                double* a = &acc[p.qi[f] - x0];
-                *a = __dadd_rn(*a, __dmul_rn(rv, (double)p.qv[f]));
-            }
-            __syncthreads();
-        }
-        for (int base = 0; base < w; base += KNN_BUILD_THREADS) {
-            const int i = base + tid;
-            const u64 tau = s_tau;
-            if (i < w) {
-                const double a = acc[i];
-                if (a != 0.0) {
-                    const float v = p.sim == EL_KNN_DOT ? (float)a : (float)__ddiv_rn(a, __dsqrt_rn(__dmul_rn(nc, p.nrm[x0 + i])));
-                    if (v != 0.0f) {
-                        const u64 key = el_make_key(v, (int32_t)(x0 + i));
-                        if (key > tau) keys[atomicAdd(&s_cnt, 1)] = key;
-                    }
-                }
-            }
-            __syncthreads();
-            const int cnt = s_cnt;
-            __syncthreads();                                  // every thread has read s_cnt before it changes
-            if (cnt > p.cap - KNN_BUILD_THREADS) knn_block_compact(keys, cnt, p.cap, p.N, &s_cnt, &s_tau);
-        }
-    }
-    __syncthreads();
-    const int cnt = s_cnt;
-    __syncthreads();
-    knn_block_compact(keys, cnt, p.cap, p.N, &s_cnt, &s_tau);
-    const int m = cnt < p.N ? cnt : p.N;
-    for (int j = tid; j < m; j += KNN_BUILD_THREADS) {
-        const u64 key = keys[j];
-        const int32_t x = el_key_item(key);
-        p.lx[c * p.N + j] = x;
-        p.lv[c * p.N + j] = el_key_score(key);
-        atomicAdd(&p.rowcnt[x], 1);
-    }
-    if (tid == 0) p.lcnt[c] = m;
-}
-
-struct KnnFWs {         // KnnBuildF's nrm, lcnt, rowcnt [n] and lx, lv [n, N], then the list-to-CSR arrays
-    double* nrm;
-    int32_t *lcnt, *rowcnt, *lx;
-    float* lv;
-    KnnCsrWs csr;
-};
-size_t knn_f32_carve(int64_t n, int N, void* base, KnnFWs* w) {
-    ElCarve c{(char*)base};
-    w->nrm = c.take<double>((size_t)n);
-    w->lcnt = c.take<int32_t>((size_t)n);
-    w->rowcnt = c.take<int32_t>((size_t)n);
-    w->lx = c.take<int32_t>((size_t)n * N);
-    w->lv = c.take<float>((size_t)n * N);
-    w->csr = el_knn_csr_carve(c, n, N);
-    return c.off;
-}
-
 int attr_tile(int64_t n) { return (int)(n < ATTR_TILE ? ((n + 63) / 64) * 64 : ATTR_TILE); }
 
 }  // namespace
@@ -277,44 +158,4 @@ extern "C" int el_profile_build(el_ctx* ctx, void* stream, const int64_t* r_indp
     EL_LAUNCH("k_profile_fill", k_profile<true>, dim3((unsigned)n_users), dim3(64), lds_fill, st, p);
     EL_CHECK_LAUNCH();
     return 0;
-}
-
-extern "C" size_t el_knn_f32_ws_bytes(int64_t n, int32_t n_neighbors) {
-    if (n <= 0 || n_neighbors <= 0) return 0;
-    KnnFWs w;
-    return knn_f32_carve(n, (int)(n_neighbors < n ? n_neighbors : n), nullptr, &w);
-}
-
-extern "C" int el_knn_build_f32(el_ctx* ctx, void* stream, const int64_t* p_indptr, const int32_t* p_indices, const float* p_vals,
-                                const int64_t* q_indptr, const int32_t* q_indices, const float* q_vals, int64_t n, int64_t n_other,
-                                int32_t n_neighbors, int sim, int64_t* w_indptr, int32_t* w_indices, float* w_vals, void* ws,
-                                size_t ws_bytes) {
-    if (int rc = el_bind(ctx)) return rc;
-    EL_REQUIRE(p_indptr && p_indices && p_vals && q_indptr && q_indices && q_vals, "el_knn_build_f32: null input pointer");
-    EL_REQUIRE(w_indptr && w_indices && w_vals, "el_knn_build_f32: null output pointer");
-    EL_REQUIRE(n >= 1 && n < 0x7fffffffLL && n_other >= 1 && n_other < 0x7fffffffLL, "el_knn_build_f32: bad sizes n=%lld n_other=%lld",
-               (long long)n, (long long)n_other);
-    EL_REQUIRE(sim == EL_KNN_COSINE || sim == EL_KNN_DOT, "el_knn_build_f32: similarity %d unsupported (EL_KNN_COSINE, EL_KNN_DOT)", sim);
-    EL_REQUIRE(n_neighbors >= 1, "el_knn_build_f32: n_neighbors must be >= 1");
-    const int N = (int)(n_neighbors < n ? n_neighbors : n);
-    EL_REQUIRE(N <= KNN_MAX_NEIGHBORS, "el_knn_build_f32: n_neighbors %d > %d unsupported", N, KNN_MAX_NEIGHBORS);
-    KnnFWs w;
-    const size_t need = knn_f32_carve(n, N, ws, &w);
-    EL_REQUIRE(ws != nullptr && ws_bytes >= need, "el_knn_build_f32: workspace too small (need %zu bytes)", need);
-    hipStream_t st = (hipStream_t)stream;
-    EL_CHECK_HIP(hipMemsetAsync(w.rowcnt, 0, (size_t)n * 4, st));
-    EL_LAUNCH("k_knn_norms_f32", k_knn_norms_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p_indptr, p_vals, n, w.nrm);
-    EL_CHECK_LAUNCH();
-    KnnBuildF p;
-    p.pp = p_indptr, p.pi = p_indices, p.pv = p_vals;
-    p.qp = q_indptr, p.qi = q_indices, p.qv = q_vals;
-    p.n = n, p.N = N, p.sim = sim;
-    p.tile = attr_tile(n);
-    p.cap = knn_build_cap(N);
-    p.nrm = w.nrm, p.lx = w.lx, p.lv = w.lv, p.lcnt = w.lcnt, p.rowcnt = w.rowcnt;
-    const size_t lds = (size_t)p.cap * 8 + (size_t)p.tile * 8;
-    EL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_knn_topn_f32), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    EL_LAUNCH("k_knn_topn_f32", k_knn_topn_f32, dim3((unsigned)n), dim3(KNN_BUILD_THREADS), lds, st, p);
-    EL_CHECK_LAUNCH();
-    return el_knn_csr_launch(st, w.lx, w.lv, w.lcnt, n, N, w.rowcnt, w_indptr, w_indices, w_vals, w.csr);
 }

@@ -349,6 +349,28 @@ __device__ __forceinline__ bool el_row_contains(const int32_t* __restrict__ idx,
     return p < hi && idx[p] == x;
 }
 
+// The integer co-occurrence expansion of one LDS tile (k_knn_topn's count kinds, k_ease_gram): for every entry e of the row
+// [p0, p1) of P and every entry f of row pi[e] of Q (columns ascending) with x0 <= qi[f] < x1, acc[qi[f] - x0] += pv[e] * qv[f].
+// The NW waves of the workgroup take the entries e side by side, their lanes across f; integer LDS atomics, so every order
+// gives the same counts.  tiled: [x0, x1) is not Q's whole column range (the whole range needs no search).  The caller zeroes
+// acc and puts a workgroup barrier before and after.
+template <int NW, typename ACC>
+__device__ __forceinline__ void el_count_expand(ACC* acc, const int32_t* pi, const int32_t* pv, int64_t p0, int64_t p1,
+                                                const int64_t* qp, const int32_t* qi, const int32_t* qv, int64_t x0, int64_t x1,
+                                                bool tiled) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int64_t e = p0 + wv; e < p1; e += NW) {
+        const int32_t t = pi[e];
+        const ACC a = (ACC)pv[e];                         // (an int32 widens to a 64-bit cell with its sign)
+        int64_t q0 = qp[t], q1 = qp[t + 1];
+        if (tiled) {
+            q0 = el_lower_bound(qi, q0, q1, (int32_t)x0);
+            q1 = el_lower_bound(qi, q0, q1, (int32_t)x1);
+        }
+        for (int64_t f = q0 + lane; f < q1; f += 64) atomicAdd(&acc[qi[f] - x0], a * (ACC)qv[f]);
+    }
+}
+
 // ---- Philox4x32-10 (counter-based RNG; Salmon et al. 2011) ------------------------
 struct el_philox4 {
     u32 x, y, z, w;

@@ -49,8 +49,7 @@ template <typename ACC>
 __global__ __launch_bounds__(EASE_GRAM_THREADS) void k_ease_gram(EaseGram p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     ACC* acc = reinterpret_cast<ACC*>(smem);                                   // [tile]
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    constexpr int nw = EASE_GRAM_THREADS / 64;
+    const int tid = threadIdx.x;
     const int64_t c = blockIdx.x;
     const int64_t p0 = p.tp[c], p1 = p.tp[c + 1];
     // ease_r.py:80-82: the stored-entry count plus l2_norm, a double, assigned into the float32 matrix
@@ -61,16 +60,7 @@ __global__ __launch_bounds__(EASE_GRAM_THREADS) void k_ease_gram(EaseGram p) {
         const int w = (int)(x1 - x0);
         for (int i = tid; i < w; i += EASE_GRAM_THREADS) acc[i] = 0;
         __syncthreads();
-        for (int64_t e = p0 + wv; e < p1; e += nw) {
-            const int32_t t = p.ti[e];
-            const ACC a = (ACC)(int64_t)p.tv[e];
-            int64_t q0 = p.rp[t], q1 = p.rp[t + 1];
-            if (tiled) {
-                q0 = el_lower_bound(p.ri, q0, q1, (int32_t)x0);
-                q1 = el_lower_bound(p.ri, q0, q1, (int32_t)x1);
-            }
-            for (int64_t f = q0 + lane; f < q1; f += 64) atomicAdd(&acc[p.ri[f] - x0], a * (ACC)(int64_t)p.rv[f]);
-        }
+        el_count_expand<EASE_GRAM_THREADS / 64>(acc, p.ti, p.tv, p0, p1, p.rp, p.ri, p.rv, x0, x1, tiled);
         __syncthreads();
         double* g = p.G + c * p.ldg + x0;
         for (int i = tid; i < w; i += EASE_GRAM_THREADS)

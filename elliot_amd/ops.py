@@ -251,10 +251,10 @@ def topk_merge(ctx, parts_idx, parts_val):
 KNN_SIMILARITIES = {"cosine": _lib.EL_KNN_COSINE, "dot": _lib.EL_KNN_DOT}
 
 
-def device_values(values, device):
-    """The values of a CSR as a float32 device tensor beside its DeviceCSR (never a zero-length buffer)."""
-    v = np.ascontiguousarray(values, dtype=np.float32)
-    return torch.from_numpy(v if v.shape[0] else np.zeros(1, np.float32)).to(device)
+def device_values(values, device, dtype=np.float32):
+    """The values of a CSR as a device tensor (float32 unless told otherwise) beside its DeviceCSR (never a zero-length buffer)."""
+    v = np.ascontiguousarray(values, dtype=dtype)
+    return torch.from_numpy(v if v.shape[0] else np.zeros(1, dtype)).to(device)
 
 
 def _w_alloc(ctx, n, N):
@@ -281,38 +281,55 @@ def knn_integer_ratings(values):
                      "this train matrix holds other values")
 
 
+def _pair_operands(ctx, M, targets, integer=None):
+    """What a co-occurrence kernel reads of a scipy sparse M: P = the targets' side (targets = "rows": M, "cols": M^T) and
+    Q = P^T, both with sorted rows.  integer: knn_integer_ratings or its like, which turns the values into exact int32 (or
+    refuses them with its caller's message); None: float32 values as they are.
+    Returns (Pc, pvt, Qc, qvt, scale, max_deg, max_abs): the two DeviceCSRs with their value tensors, then -- integer only,
+    else None -- the scale of the values, the longest row of P and the largest |value|."""
+    import scipy.sparse as sp
+    M = sp.csr_matrix(M) if integer else sp.csr_matrix(M, dtype=np.float32)
+    M.sum_duplicates()
+    M.sort_indices()
+    Mt = M.T.tocsr()
+    Mt.sort_indices()
+    P, Q = (M, Mt) if targets == "rows" else (Mt, M)
+    n, n_other = P.shape
+    scale = max_deg = max_abs = None
+    pv, qv, dtype = P.data, Q.data, np.float32
+    if integer:
+        dtype = np.int32
+        scale, pv = integer(P.data)
+        _, qv = integer(Q.data)
+        max_deg = int(np.diff(P.indptr).max()) if n else 0
+        max_abs = int(np.abs(pv).max()) if pv.size else 0
+    dev = ctx.device
+    return (DeviceCSR(P.indptr, P.indices, n_other, dev), device_values(pv, dev, dtype),
+            DeviceCSR(Q.indptr, Q.indices, n, dev), device_values(qv, dev, dtype), scale, max_deg, max_abs)
+
+
+def _knn_w(ctx, entry, ws_query, Pc, pvt, Qc, qvt, n_neighbors, sim, *extra):
+    """W of el_knn_build / el_knn_build_f32 (`entry`; `extra`: its arguments between sim and the outputs) on _pair_operands."""
+    n, n_other = Pc.n_rows, Pc.n_cols
+    need = int(getattr(ctx.lib, ws_query)(n, int(n_neighbors)))
+    ws = workspace(ctx, None, need, ctx.device)
+    w_indptr, w_indices, w_vals = _w_alloc(ctx, n, min(int(n_neighbors), n))
+    check(getattr(ctx.lib, entry)(ctx.handle, ctx.stream(), _ptr(Pc.indptr), _ptr(Pc.indices), _ptr(pvt), _ptr(Qc.indptr),
+                                  _ptr(Qc.indices), _ptr(qvt), n, n_other, int(n_neighbors), KNN_SIMILARITIES[sim], *extra,
+                                  _ptr(w_indptr), _ptr(w_indices), _ptr(w_vals), C.c_void_p(ws.data_ptr()), need), entry)
+    return _w_result(w_indptr, w_indices, w_vals)
+
+
 def knn_build(ctx, R, side, n_neighbors, sim):
     """Similarity.initialize (item_knn_similarity.py / user_knn_similarity.py:46-80): W of ItemKNN (side="item": the columns
     of R) or UserKNN (side="user": its rows), top-`n_neighbors` non-zeros per column.  R: scipy sparse [U, I] with values.
     Returns (DeviceCSR W, float32 values tensor); W is [n, n], columns ascending in every row."""
-    import scipy.sparse as sp
     if sim not in KNN_SIMILARITIES:
         raise ValueError(f"similarity {sim!r} is not supported; supported: {sorted(KNN_SIMILARITIES)}")
     if side not in ("item", "user"):
         raise ValueError("side must be 'item' or 'user'")
-    R = sp.csr_matrix(R)
-    R.sum_duplicates()
-    R.sort_indices()
-    Rt = R.T.tocsr()
-    Rt.sort_indices()
-    P, Q = (Rt, R) if side == "item" else (R, Rt)
-    n, n_other = P.shape
-    scale, pv = knn_integer_ratings(P.data)
-    _, qv = knn_integer_ratings(Q.data)
-    dev = ctx.device
-    Pc, Qc = DeviceCSR(P.indptr, P.indices, n_other, dev), DeviceCSR(Q.indptr, Q.indices, n, dev)
-    pvt = torch.from_numpy(pv if pv.size else np.zeros(1, np.int32)).to(dev)
-    qvt = torch.from_numpy(qv if qv.size else np.zeros(1, np.int32)).to(dev)
-    max_deg = int(np.diff(P.indptr).max()) if n else 0
-    max_abs = int(np.abs(pv).max()) if pv.size else 0
-    need = int(ctx.lib.el_knn_ws_bytes(int(n), int(n_neighbors)))
-    ws = workspace(ctx, None, need, ctx.device)
-    w_indptr, w_indices, w_vals = _w_alloc(ctx, n, min(int(n_neighbors), n))
-    check(ctx.lib.el_knn_build(ctx.handle, ctx.stream(), _ptr(Pc.indptr), _ptr(Pc.indices), _ptr(pvt), _ptr(Qc.indptr),
-                               _ptr(Qc.indices), _ptr(qvt), int(n), int(n_other), int(n_neighbors), KNN_SIMILARITIES[sim],
-                               int(scale), max_deg, max_abs, _ptr(w_indptr), _ptr(w_indices), _ptr(w_vals),
-                               C.c_void_p(ws.data_ptr()), need), "el_knn_build")
-    return _w_result(w_indptr, w_indices, w_vals)
+    Pc, pvt, Qc, qvt, scale, max_deg, max_abs = _pair_operands(ctx, R, "cols" if side == "item" else "rows", knn_integer_ratings)
+    return _knn_w(ctx, "el_knn_build", "el_knn_ws_bytes", Pc, pvt, Qc, qvt, n_neighbors, sim, int(scale), max_deg, max_abs)
 
 
 def knn_score_topk(ctx, A, A_vals, B, B_vals, u_start, u_stop, k, excl=None, cand=None, out_idx=None, out_val=None):
@@ -338,6 +355,24 @@ def knn_score_topk(ctx, A, A_vals, B, B_vals, u_start, u_stop, k, excl=None, can
 PROFILE_MODES = {"add": _lib.EL_PROFILE_ADD, "last": _lib.EL_PROFILE_LAST}
 
 
+def _feature_operands(ctx, who, r_indptr, r_indices, F, f_weights):
+    """What profile_build and kahfm_init (`who`) read: the train rows and the items' features as DeviceCSRs, the weights (or
+    None) as a float64 tensor.  Returns (r_indptr as host int64, Rc, Fc, fw)."""
+    r_indptr = np.ascontiguousarray(r_indptr, dtype=np.int64)
+    U, (I, nF) = r_indptr.shape[0] - 1, F.shape
+    if U < 1 or I < 1 or nF < 1:
+        raise ValueError(f"{who}: empty operand (users {U}, items {I}, features {nF})")
+    dev = ctx.device
+    Rc, Fc = DeviceCSR(r_indptr, r_indices, I, dev), DeviceCSR(F.indptr, F.indices, nF, dev)
+    fw = None
+    if f_weights is not None:
+        fw = np.ascontiguousarray(f_weights, dtype=np.float64)
+        if fw.shape[0] != F.nnz:
+            raise ValueError(f"{who}: one weight per entry of F")
+        fw = device_values(fw, dev, np.float64)
+    return r_indptr, Rc, Fc, fw
+
+
 def profile_build(ctx, r_indptr, r_indices, F, f_weights, mode, by_len):
     """User profiles over item features (compute_binary_profile / TFIDF.get_profiles + build_feature_sparse_values of the
     reference's attribute plug-ins) as a host scipy CSR [U, nF] float32, columns ascending, zeros kept.
@@ -348,18 +383,8 @@ def profile_build(ctx, r_indptr, r_indices, F, f_weights, mode, by_len):
         raise ValueError(f"profile_build: mode {mode!r} is not supported; supported: {sorted(PROFILE_MODES)}")
     if mode == "last" and f_weights is None:
         raise ValueError("profile_build: mode 'last' needs one weight per entry of F")
-    r_indptr = np.ascontiguousarray(r_indptr, dtype=np.int64)
-    U, (I, nF) = r_indptr.shape[0] - 1, F.shape
-    if U < 1 or I < 1 or nF < 1:
-        raise ValueError(f"profile_build: empty operand (users {U}, items {I}, features {nF})")
-    dev = ctx.device
-    Rc, Fc = DeviceCSR(r_indptr, r_indices, I, dev), DeviceCSR(F.indptr, F.indices, nF, dev)
-    fw = None
-    if mode == "last":
-        fw = np.ascontiguousarray(f_weights, dtype=np.float64)
-        if fw.shape[0] != F.nnz:
-            raise ValueError("profile_build: one weight per entry of F")
-        fw = torch.from_numpy(fw if fw.shape[0] else np.zeros(1, np.float64)).to(dev)
+    r_indptr, Rc, Fc, fw = _feature_operands(ctx, "profile_build", r_indptr, r_indices, F, f_weights if mode == "last" else None)
+    U, (I, nF), dev = Rc.n_rows, F.shape, ctx.device
     # an entry per feature touched: at most the features of the user's items, and at most nF
     deg = np.concatenate([[0], np.cumsum(np.diff(F.indptr)[np.asarray(r_indices, dtype=np.int64)])])
     cap = int(np.minimum(deg[r_indptr[1:]] - deg[r_indptr[:-1]], nF).sum())
@@ -382,16 +407,8 @@ def kahfm_init(ctx, r_indptr, r_indices, F, f_weights, P0=None, Q0=None):
     r_indptr / r_indices: the train rows in train_dict order; F: scipy CSR [I, nF], the features of every item (its values are not
     read); f_weights: the float64 TF-IDF weight of every entry of F.  P0[u, f]: the weight of f in the last item of row u that
     carries it, divided by the row's length; Q0[i, f]: the weight.  P0 / Q0: tensors to fill instead of new ones."""
-    r_indptr = np.ascontiguousarray(r_indptr, dtype=np.int64)
-    U, (I, nF) = r_indptr.shape[0] - 1, F.shape
-    if U < 1 or I < 1 or nF < 1:
-        raise ValueError(f"kahfm_init: empty operand (users {U}, items {I}, features {nF})")
-    fw = np.ascontiguousarray(f_weights, dtype=np.float64)
-    if fw.shape[0] != F.nnz:
-        raise ValueError("kahfm_init: one weight per entry of F")
-    dev = ctx.device
-    Rc, Fc = DeviceCSR(r_indptr, r_indices, I, dev), DeviceCSR(F.indptr, F.indices, nF, dev)
-    fw = torch.from_numpy(fw if fw.shape[0] else np.zeros(1, np.float64)).to(dev)
+    _, Rc, Fc, fw = _feature_operands(ctx, "kahfm_init", r_indptr, r_indices, F, f_weights)
+    U, (I, nF), dev = Rc.n_rows, F.shape, ctx.device
     if P0 is None:
         P0 = torch.empty((U, nF), dtype=torch.float64, device=dev)
     if Q0 is None:
@@ -408,26 +425,9 @@ def knn_build_f32(ctx, A, n_neighbors, sim):
     """Similarity.initialize of attribute_user_knn_similarity.py: W of the rows of A (scipy sparse [n, n_other], float32 values,
     explicit zeros kept), top-`n_neighbors` non-zeros per column, self-similarity kept.  fp64 sums in the stored (ascending)
     order of A's rows.  Returns (DeviceCSR W, float32 values tensor) as knn_build."""
-    import scipy.sparse as sp
     if sim not in KNN_SIMILARITIES:
         raise ValueError(f"similarity {sim!r} is not supported; supported: {sorted(KNN_SIMILARITIES)}")
-    P = sp.csr_matrix(A, dtype=np.float32)
-    P.sum_duplicates()
-    P.sort_indices()
-    Q = P.T.tocsr()
-    Q.sort_indices()
-    n, n_other = P.shape
-    dev = ctx.device
-    Pc, Qc = DeviceCSR(P.indptr, P.indices, n_other, dev), DeviceCSR(Q.indptr, Q.indices, n, dev)
-    pvt, qvt = device_values(P.data, dev), device_values(Q.data, dev)
-    need = int(ctx.lib.el_knn_f32_ws_bytes(int(n), int(n_neighbors)))
-    ws = workspace(ctx, None, need, dev)
-    w_indptr, w_indices, w_vals = _w_alloc(ctx, n, min(int(n_neighbors), n))
-    check(ctx.lib.el_knn_build_f32(ctx.handle, ctx.stream(), _ptr(Pc.indptr), _ptr(Pc.indices), _ptr(pvt), _ptr(Qc.indptr),
-                                   _ptr(Qc.indices), _ptr(qvt), int(n), int(n_other), int(n_neighbors), KNN_SIMILARITIES[sim],
-                                   _ptr(w_indptr), _ptr(w_indices), _ptr(w_vals), C.c_void_p(ws.data_ptr()), need),
-          "el_knn_build_f32")
-    return _w_result(w_indptr, w_indices, w_vals)
+    return _knn_w(ctx, "el_knn_build_f32", "el_knn_f32_ws_bytes", *_pair_operands(ctx, A, "rows")[:4], n_neighbors, sim)
 
 
 # ------------------------------------------------------------------------------------------
@@ -778,21 +778,8 @@ def ease_integer_ratings(values):
 def ease_gram(ctx, R, l2_norm, out=None):
     """ease_r.py:76-82: G = R^T R of a scipy [U, I] train matrix with the diagonal replaced by (float)(n_i + l2_norm), as an fp64
     [I, I] device tensor (el_ease_gram: exact integer counts)."""
-    import scipy.sparse as sp
-    R = sp.csr_matrix(R)
-    R.sum_duplicates()
-    R.sort_indices()
-    Rt = R.T.tocsr()
-    Rt.sort_indices()
-    U, I = R.shape
-    scale, rv = ease_integer_ratings(R.data)
-    _, tv = ease_integer_ratings(Rt.data)
-    dev = ctx.device
-    Rc, Tc = DeviceCSR(R.indptr, R.indices, I, dev), DeviceCSR(Rt.indptr, Rt.indices, U, dev)
-    rvt = torch.from_numpy(rv if rv.size else np.zeros(1, np.int32)).to(dev)
-    tvt = torch.from_numpy(tv if tv.size else np.zeros(1, np.int32)).to(dev)
-    max_deg = int(np.diff(Rt.indptr).max()) if I else 0
-    max_abs = int(np.abs(rv).max()) if rv.size else 0
+    Tc, tvt, Rc, rvt, scale, max_deg, max_abs = _pair_operands(ctx, R, "cols", ease_integer_ratings)
+    I, U, dev = Tc.n_rows, Tc.n_cols, ctx.device
     if out is None:
         out = torch.empty((I, I), dtype=torch.float64, device=dev)
     check(ctx.lib.el_ease_gram(ctx.handle, ctx.stream(), _ptr(Tc.indptr), _ptr(Tc.indices), _ptr(tvt), _ptr(Rc.indptr),

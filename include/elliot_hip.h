@@ -550,7 +550,8 @@ int el_kahfm_init(el_ctx* ctx, void* stream,
  *   EL_KNN_COSINE value = (float)(dot / sqrt(n_c * n_x)), fp64 correctly rounded, rounded once to float (sklearn normalises
  *                 the float32 rows first: within (2 L + 8) 2^-24 relative for rows of L entries)
  *   column c of W keeps min(N, non-zeros) entries by (value desc, index asc); an entry needs dot != 0 and value != 0.
- * Output and workspace as el_knn_build: ws = el_knn_f32_ws_bytes(n, n_neighbors) bytes.  N <= 2048.                        */
+ * Output and workspace as el_knn_build -- one kernel, workspace layout and host sequence serve both (el_knn.hip) --:
+ * ws = el_knn_f32_ws_bytes(n, n_neighbors) = el_knn_ws_bytes(n, n_neighbors) bytes.  N <= 2048.                          */
 size_t el_knn_f32_ws_bytes(int64_t n, int32_t n_neighbors);
 int el_knn_build_f32(el_ctx* ctx, void* stream,
                      const int64_t* p_indptr, const int32_t* p_indices, const float* p_vals,

@@ -62,6 +62,22 @@ def launches(ctx, fn):
     return {name: n for name, (n, _ms) in ctx.timing_report().items()}
 
 
+def kernel_runs_ms(ctx, fn, name, reps):
+    """The time of kernel `name` alone (events around its launch, el_timing_enable) in each of `reps` runs of fn."""
+    out = []
+    torch.cuda.synchronize()
+    ctx.timing_report()
+    for _ in range(reps):
+        ctx.timing(True)
+        try:
+            fn()
+            torch.cuda.synchronize()
+        finally:
+            ctx.timing(False)
+        out.append(ctx.timing_report()[name][1])
+    return out
+
+
 def run_leg(ctx, label, reps, score_users, cpu_inv):
     U, I, mean_log, dmin, dmax, binary, l2 = LEGS[label]
     indptr, indices = zipf_csr(U, I, mean_log=mean_log, sigma_log=1.0, dmin=dmin, dmax=dmax, seed=7)
@@ -70,7 +86,9 @@ def run_leg(ctx, label, reps, score_users, cpu_inv):
     R = sp.csr_matrix((vals, indices, indptr), shape=(U, I))
     st = ops.EaseDeviceState(ctx, R, l2)
     G = ops.ease_gram(ctx, R, l2)                                                       # warm-up
-    t_gram = median(lambda: ops.ease_gram(ctx, R, l2, out=G), reps)
+    gram_ms = [event_ms(lambda: ops.ease_gram(ctx, R, l2, out=G)) for _ in range(reps)]
+    t_gram = sorted(gram_ms)[reps // 2]
+    gram_kernel_ms = kernel_runs_ms(ctx, lambda: ops.ease_gram(ctx, R, l2, out=G), "k_ease_gram", reps)
     A = torch.empty_like(G)
     ipiv = torch.empty(I, dtype=torch.int32, device=ctx.device)
     ws = torch.empty(int(ctx.lib.el_inv_f64_ws_bytes(I)), dtype=torch.uint8, device=ctx.device)
@@ -108,7 +126,8 @@ def run_leg(ctx, label, reps, score_users, cpu_inv):
             "inverse_pct_of_fp64_peak": round(100.0 * flops / t_inv / 1e9 / FP64_PEAK_TFLOPS, 1),
             "weights_ms": round(t_w, 3), "score_users": n_score, "score_ms": round(t_score, 3),
             "score_users_per_s": round(n_score / t_score * 1e3, 1), "score_all_users": n_score == U,
-            "all_runs_ms": {"lu": [round(x, 3) for x in lu_ms], "inverse": [round(x, 3) for x in inv_ms]}}
+            "all_runs_ms": {"gram": [round(x, 3) for x in gram_ms], "k_ease_gram": [round(x, 3) for x in gram_kernel_ms],
+                            "lu": [round(x, 3) for x in lu_ms], "inverse": [round(x, 3) for x in inv_ms]}}
     if cpu_inv:
         Gh = ease_gram_host(R, l2)
         t0 = time.perf_counter()

@@ -48,6 +48,8 @@ def main():
                                    shapes(rs, N // 2, (0, 200000), (0, 1000000), (1, 256), (1, 128), (0, 5000000))],
         "el_bprmf_train_loop_ws_bytes": shapes(rs, N, (0, 30000000), (0, 2000000)),
         "el_pwmf_train_loop_ws_bytes": shapes(rs, N, (0, 30000000), (0, 2000000)),
+        "el_knn_f32_ws_bytes": shapes(rs, N, (0, 200000), (0, 900)),
+        "el_profile_ws_bytes": shapes(rs, N, (0, 9000000)),
     }
     slim = cpu["el_slim_ws_bytes"]
     slim += [(38000, 3706, c, 10) for c in (0, 1, 2, 9)] + [(37000, 3706, c, 10) for c in (1, 2)] + [(138493, 26744, 9, 10)]

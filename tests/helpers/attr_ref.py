@@ -1,4 +1,4 @@
-"""NumPy / scipy restatement of the attribute kernels' contract (elliot_amd/csrc/el_attr.hip, include/elliot_hip.h).
+"""NumPy / scipy restatement of the attribute kernels' contract (elliot_amd/csrc/el_attr.hip, el_knn.hip, include/elliot_hip.h).
 
   profile   one fp64 cell per (user, feature), the user's items in stored (train_dict) order:
             ADD   cell = cell + w from 0 per item that carries the feature, w = 1 / len (by_len) or 1

@@ -1,4 +1,4 @@
-"""GPU: el_profile_build and el_knn_build_f32 (elliot_amd/csrc/el_attr.hip) against the reference's own matrices
+"""GPU: el_profile_build (elliot_amd/csrc/el_attr.hip) and el_knn_build_f32 (el_knn.hip) against the reference's own matrices
 (tests/golden/attr_ref.npz) and the restatement of their contract (tests/helpers/attr_ref.py), bit for bit.
 
 Shapes: ATTR_TILE = 8192 fp64 cells per LDS tile, so 8192 + 37 features / targets cross one tile boundary; everything else is

@@ -45,11 +45,36 @@ def test_gram_exact_symmetric_repeatable(ctx, half):
     assert np.array_equal(G1, ease_ref.gram(R, 13.7))
 
 
-def test_gram_more_than_one_lds_tile(ctx):
-    """I > 16 384: every row of G is counted in two passes over the columns."""
+def count_bound(R):
+    """The largest magnitude a Gram count can reach: the longest column times the largest rating squared."""
+    return float(np.diff(sp.csc_matrix(R).indptr).max()) * float(np.abs(R.data).max()) ** 2
+
+
+def test_gram_wide_counts_use_the_int64_counters(ctx):
+    """max degree x max |r|^2 beyond int32 (and below 2^53, so the fp64 products of the check are exact): 64-bit LDS counters."""
+    rs = np.random.RandomState(5)
+    R = sp.random(300, 120, density=0.3, random_state=rs, format="csr", dtype=np.float32)
+    R.data[:] = rs.randint(1, 20001, size=R.nnz)
+    R.data[:5] = 20000
+    assert 2 ** 31 - 1 < count_bound(R) < 2 ** 53
+    G1 = ops.ease_gram(ctx, R, 13.7).cpu().numpy()
+    G2 = ops.ease_gram(ctx, R, 13.7).cpu().numpy()
+    assert np.array_equal(G1, exact_gram_rows(R, np.arange(R.shape[1]), 13.7))
+    assert np.array_equal(G1, G1.T)
+    assert G1.tobytes() == G2.tobytes()
+
+
+@pytest.mark.parametrize("wide", [False, True])
+def test_gram_more_than_one_lds_tile(ctx, wide):
+    """I > 16 384: every row of G is counted in two passes over the columns.  wide: ratings of 40 000 to 60 000, so the 64-bit
+    counters take the two passes and most sampled cells exceed int32."""
     R = ratings(2500, 16384 + 917, 0.002, 5)
-    G = ops.ease_gram(ctx, R, 1000.0)
     rows = np.array([0, 1, 4097, 16383, 16384, 16385, R.shape[1] - 1])
+    if wide:
+        R.data[:] = np.random.RandomState(6).randint(40000, 60001, size=R.nnz)
+        assert 2 ** 31 - 1 < count_bound(R) < 2 ** 53
+        assert (exact_gram_rows(R, rows, 1000.0) > 2 ** 31).sum() > 500
+    G = ops.ease_gram(ctx, R, 1000.0)
     got = G[torch.from_numpy(rows).to(ctx.device)].cpu().numpy()
     assert np.array_equal(got, exact_gram_rows(R, rows, 1000.0))
     again = ops.ease_gram(ctx, R, 1000.0)[torch.from_numpy(rows).to(ctx.device)].cpu().numpy()

@@ -192,6 +192,33 @@ def test_wide_counts_use_the_int64_accumulator(ctx):
         assert_w_equal(host_w(W, Wv), knn_ref.build_w(R, "item", 15, sim))
 
 
+def test_int64_counts_across_the_tile_boundary(ctx):
+    """10 240 users with ratings of 40 000 to 60 000: the 64-bit counts take two LDS tiles (8 192 cells each), every sampled dot
+    list keeps neighbours from both tiles and values beyond int32.  45 columns of W bit-exact against the restatement."""
+    from elliot_amd import ops
+    rs = np.random.RandomState(5)
+    tile, n, I, N = 8192, 8192 + 2048, 96, 20
+    fixed = np.array([0, 1, tile - 1, tile, n - 1])
+    cols = np.sort(np.concatenate([fixed, rs.choice(np.setdiff1d(np.arange(n), fixed), size=40, replace=False)]))
+    deg = rs.randint(1, 4, size=n)
+    indptr = np.concatenate([[0], np.cumsum(deg)]).astype(np.int64)
+    indices = np.concatenate([np.sort(rs.choice(I, size=d, replace=False)) for d in deg]).astype(np.int32)
+    R = sp.csr_matrix((rs.randint(40000, 60001, size=indices.shape[0]).astype(np.float32), indices, indptr), shape=(n, I))
+    assert float(deg.max()) * float(R.data.max()) ** 2 > 2 ** 31 - 1             # el_knn_build picks the 64-bit cells
+    M = knn_ref.targets_matrix(R, "user")
+    for sim in ("dot", "cosine"):
+        W, Wv = ops.knn_build(ctx, R, "user", N, sim)
+        Wc = host_w(W, Wv).tocsc()
+        Wc.sort_indices()
+        for c, (x, v) in zip(cols, knn_ref.column_lists(M, cols, N, sim)):
+            if sim == "dot":
+                assert len(x) == N and x.min() < tile <= x.max() and v.max() > 2.0 ** 31, c
+            o = np.argsort(x)
+            lo, hi = Wc.indptr[c], Wc.indptr[c + 1]
+            assert np.array_equal(Wc.indices[lo:hi], x[o]), (sim, c)
+            assert same_bits(Wc.data[lo:hi], v[o]), (sim, c)
+
+
 def test_half_step_ratings(ctx):
     from elliot_amd import ops
     rs = np.random.RandomState(2)
