@@ -371,6 +371,30 @@ __device__ __forceinline__ void el_count_expand(ACC* acc, const int32_t* pi, con
     }
 }
 
+// el_count_expand's sibling with two counters per cell (k_slope_build): over the same pairs (e, f), cnt[qi[f] - x0] += 1 and
+// dif[qi[f] - x0] += pv[e] - qv[f].  A 64-bit cell is unsigned and takes the difference in two's complement.  Integer LDS
+// atomics again: every order gives the same counts.  The caller zeroes both arrays and puts a workgroup barrier before and after.
+template <int NW, typename ACC>
+__device__ __forceinline__ void el_count_diff_expand(int* cnt, ACC* dif, const int32_t* pi, const int32_t* pv, int64_t p0,
+                                                     int64_t p1, const int64_t* qp, const int32_t* qi, const int32_t* qv,
+                                                     int64_t x0, int64_t x1, bool tiled) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int64_t e = p0 + wv; e < p1; e += NW) {
+        const int32_t t = pi[e];
+        const int64_t a = (int64_t)pv[e];
+        int64_t q0 = qp[t], q1 = qp[t + 1];
+        if (tiled) {
+            q0 = el_lower_bound(qi, q0, q1, (int32_t)x0);
+            q1 = el_lower_bound(qi, q0, q1, (int32_t)x1);
+        }
+        for (int64_t f = q0 + lane; f < q1; f += 64) {
+            const int64_t x = qi[f] - x0;
+            atomicAdd(&cnt[x], 1);
+            atomicAdd(&dif[x], (ACC)(a - (int64_t)qv[f]));
+        }
+    }
+}
+
 // ---- Philox4x32-10 (counter-based RNG; Salmon et al. 2011) ------------------------
 struct el_philox4 {
     u32 x, y, z, w;

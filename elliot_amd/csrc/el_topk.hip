@@ -427,6 +427,9 @@ struct TopkParams64 {
     int k;
     int32_t* out_idx;
     double* out_val;
+    // dense-preds variant
+    const double* preds;
+    int64_t ld;
 };
 
 __device__ __forceinline__ bool el_pair_less(u64 pa, u32 sa, u64 pb, u32 sb) {
@@ -455,6 +458,7 @@ __device__ __forceinline__ void el_wave_bitonic_desc_pair(u64* a, u32* s, int n,
     }
 }
 
+template <bool DENSE>
 __global__ __launch_bounds__(64) void k_topk_wave_f64(TopkParams64 p, int cap) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     u64* prim = reinterpret_cast<u64*>(smem);        // [cap]
@@ -462,7 +466,7 @@ __global__ __launch_bounds__(64) void k_topk_wave_f64(TopkParams64 p, int cap) {
     const int lane = threadIdx.x;
     const int64_t user = p.u_start + blockIdx.x;
     const int F = p.F;
-    const double* pu = p.P + user * (int64_t)F;
+    const double* pu = DENSE ? nullptr : p.P + user * (int64_t)F;
     int64_t e0 = 0, e1 = 0, c0 = 0, c1 = 0;
     if (p.excl_indptr) {
         e0 = p.excl_indptr[user];
@@ -506,10 +510,14 @@ __global__ __launch_bounds__(64) void k_topk_wave_f64(TopkParams64 p, int cap) {
         }
         double s = 0.0;
         if (valid) {
-            const double* qi = p.Q + il * (int64_t)F;
-            double acc = 0.0;
-            for (int f = 0; f < F; ++f) acc = __builtin_fma(qi[f], pu[f], acc);
-            s = (p.b ? acc + p.b[il] : acc) + 0.0;
+            if (DENSE) {
+                s = p.preds[(int64_t)blockIdx.x * p.ld + il] + 0.0;
+            } else {
+                const double* qi = p.Q + il * (int64_t)F;
+                double acc = 0.0;
+                for (int f = 0; f < F; ++f) acc = __builtin_fma(qi[f], pu[f], acc);
+                s = (p.b ? acc + p.b[il] : acc) + 0.0;
+            }
         }
         bool hit = valid && (s >= tau);
         if (hit && use_excl) hit = !el_row_contains(p.excl_indices, e0, e1, gitem);
@@ -886,7 +894,39 @@ extern "C" int el_score_topk_f64(el_ctx* ctx, void* stream, const double* P, con
     p.out_idx = out_idx;
     p.out_val = out_val;
     int cap = el_select_cap(k);
-    EL_LAUNCH("k_topk_wave_f64", k_topk_wave_f64, dim3((unsigned)(u_stop - u_start)), dim3(64), (size_t)cap * 12,
+    EL_LAUNCH("k_topk_wave_f64", k_topk_wave_f64<false>, dim3((unsigned)(u_stop - u_start)), dim3(64), (size_t)cap * 12,
+                       (hipStream_t)stream, p, cap);
+    EL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int el_dense_topk_f64(el_ctx* ctx, void* stream, const double* preds, int64_t ld, int64_t u_start, int64_t u_stop,
+                                 int64_t I, const int64_t* excl_indptr, const int32_t* excl_indices, const int64_t* cand_indptr,
+                                 const int32_t* cand_indices, int32_t k, int32_t* out_idx, double* out_val) {
+    if (int rc = el_bind(ctx)) return rc;
+    if (int rc = check_topk_args("el_dense_topk_f64", u_start, u_stop, I, 1, k, out_idx, out_val)) return rc;
+    EL_REQUIRE(preds && ld >= I, "el_dense_topk_f64: bad preds/ld");
+    EL_REQUIRE((cand_indptr == nullptr) == (cand_indices == nullptr), "el_dense_topk_f64: cand CSR needs both arrays");
+    EL_REQUIRE(excl_indptr == nullptr || excl_indices != nullptr, "el_dense_topk_f64: excl_indptr without excl_indices");
+    if (u_stop == u_start) return 0;
+    TopkParams64 p;
+    memset(&p, 0, sizeof(p));
+    p.u_start = u_start;
+    p.u_stop = u_stop;
+    p.item_offset = 0;
+    p.I_local = I;
+    p.F = 1;
+    p.excl_indptr = excl_indptr;
+    p.excl_indices = excl_indices;
+    p.cand_indptr = cand_indptr;
+    p.cand_indices = cand_indices;
+    p.k = k;
+    p.out_idx = out_idx;
+    p.out_val = out_val;
+    p.preds = preds;
+    p.ld = ld;
+    int cap = el_select_cap(k);
+    EL_LAUNCH("k_topk_wave_f64", k_topk_wave_f64<true>, dim3((unsigned)(u_stop - u_start)), dim3(64), (size_t)cap * 12,
                        (hipStream_t)stream, p, cap);
     EL_CHECK_LAUNCH();
     return 0;

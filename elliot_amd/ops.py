@@ -921,6 +921,185 @@ class EaseDeviceState:
 
 
 # ------------------------------------------------------------------------------------------
+# SlopeOne (exact deviation build, scoring table, ordered fp64 scoring)
+# ------------------------------------------------------------------------------------------
+SLOPE_SCORE_BLOCK_BYTES = 1 << 28    # bound of one [Ub, I] float64 score block
+SLOPE_TILE = 8192                    # LDS cells per pass of k_slope_build over the catalogue (el_slope.hip)
+
+
+def slope_integer_ratings(values):
+    """(scale, int32 values) as knn_integer_ratings; SlopeOne refuses anything else with its own message."""
+    try:
+        return knn_integer_ratings(values)
+    except ValueError:
+        raise ValueError("SlopeOne needs integer or half-step ratings (the deviation sums are exact integers); "
+                         "this train matrix holds other values") from None
+
+
+def slope_build(ctx, R, freq=None, dev=None, table=True):
+    """SlopeOneModel.initialize (slope_one_model.py:19-37) of a scipy [U, I] train matrix: (freq int32 [I, I], dev float64
+    [I, I], T float64 [I, I] or None) on the device (el_slope_build).  freq and dev start from zero, where the reference starts
+    them from np.empty and relies on fresh pages being zero.  A CSR R is brought to sorted rows in place, as by ease_gram."""
+    Tc, tvt, Rc, rvt, scale, max_deg, max_abs = _pair_operands(ctx, R, "cols", slope_integer_ratings)
+    I, U, d = Tc.n_rows, Tc.n_cols, ctx.device
+    if freq is None:
+        freq = torch.empty((I, I), dtype=torch.int32, device=d)
+    if dev is None:
+        dev = torch.empty((I, I), dtype=torch.float64, device=d)
+    T = torch.empty((I, I), dtype=torch.float64, device=d) if table else None
+    check(ctx.lib.el_slope_build(ctx.handle, ctx.stream(), _ptr(Tc.indptr), _ptr(Tc.indices), _ptr(tvt), _ptr(Rc.indptr),
+                                 _ptr(Rc.indices), _ptr(rvt), int(I), int(U), int(scale), max_deg, max_abs,
+                                 _ptr(freq, torch.int32, "freq"), int(freq.stride(0)), _ptr(dev, torch.float64, "dev"),
+                                 int(dev.stride(0)), _ptr(T, torch.float64, "T"), int(I)), "el_slope_build")
+    return freq, dev, T
+
+
+def slope_table(ctx, freq, dev, out=None):
+    """The scoring table of a (freq int32, dev float64) pair: T[j, i] = dev[i, j] where freq[i, j] > 0, NaN elsewhere
+    (el_slope_table)."""
+    I = int(freq.shape[0])
+    if out is None:
+        out = torch.empty((I, I), dtype=torch.float64, device=ctx.device)
+    check(ctx.lib.el_slope_table(ctx.handle, ctx.stream(), _ptr(freq, torch.int32, "freq"), int(freq.stride(0)),
+                                 _ptr(dev, torch.float64, "dev"), int(dev.stride(0)), I, _ptr(out, torch.float64, "T"),
+                                 int(out.stride(0))), "el_slope_table")
+    return out
+
+
+def slope_scores(ctx, rows, user_mean, T, u_start, u_stop, out=None):
+    """SlopeOneModel.predict (slope_one_model.py:42-47) for users [u_start, u_stop) and every item: float64 [n, I]
+    (el_slope_scores).  rows: the train matrix as a DeviceCSR in dict order; user_mean: float64 [U] on the device."""
+    n, I = int(u_stop) - int(u_start), int(T.shape[1])
+    if out is None:
+        out = torch.empty((n, I), dtype=torch.float64, device=ctx.device)
+    if out.shape[0] < n or out.shape[1] != I:
+        raise ValueError("slope_scores: the output block is smaller than [n, I]")
+    check(ctx.lib.el_slope_scores(ctx.handle, ctx.stream(), _ptr(rows.indptr, torch.int64), _ptr(rows.indices, torch.int32),
+                                  _ptr(user_mean, torch.float64, "user_mean"), int(u_start), int(u_stop),
+                                  _ptr(T, torch.float64, "T"), int(T.stride(0)), I, _ptr(out, torch.float64, "P"),
+                                  int(out.stride(0))), "el_slope_scores")
+    return out
+
+
+def dense_topk_f64(ctx, preds, u_start, u_stop, k, excl=None, cand=None, out_idx=None, out_val=None, pad=False):
+    """dense_topk over a float64 [n_users, I] block: (idx int32 [n, k], val float64 [n, k]) by (value desc, index asc)
+    (el_dense_topk_f64).  pad: entries at -inf become (-1, -inf) (el_topk_pad_f64)."""
+    n, I = int(u_stop) - int(u_start), int(preds.shape[1])
+    if preds.shape[0] < n:
+        raise ValueError("preds rows must cover u_stop - u_start")
+    if out_idx is None:
+        out_idx = torch.empty((n, k), dtype=torch.int32, device=ctx.device)
+    if out_val is None:
+        out_val = torch.empty((n, k), dtype=torch.float64, device=ctx.device)
+    ep, ei = _csr_ptrs(excl)
+    cp, ci = _csr_ptrs(cand)
+    check(ctx.lib.el_dense_topk_f64(ctx.handle, ctx.stream(), _ptr(preds, torch.float64, "preds"), int(preds.stride(0)),
+                                    int(u_start), int(u_stop), I, ep, ei, cp, ci, int(k), _ptr(out_idx, torch.int32),
+                                    _ptr(out_val, torch.float64)), "el_dense_topk_f64")
+    if pad:
+        check(ctx.lib.el_topk_pad_f64(ctx.handle, ctx.stream(), _ptr(out_idx, torch.int32), _ptr(out_val, torch.float64),
+                                      int(n * k)), "el_topk_pad_f64")
+    return out_idx, out_val
+
+
+def slope_user_mean(indptr, ratings):
+    """np.mean of every user's train ratings (slope_one_model.py:40) on the host: the exact sum (integer or half-step ratings)
+    and one fp64 division; nan for a user without ratings, as np.mean of nothing."""
+    indptr = np.asarray(indptr, dtype=np.int64)
+    ratings = np.asarray(ratings, dtype=np.float64)
+    n = np.diff(indptr)
+    users = np.repeat(np.arange(n.shape[0]), n)
+    s2 = np.bincount(users, weights=ratings * 2.0, minlength=n.shape[0])       # integers: exact in any order
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (s2 * 0.5) / n
+
+
+def slope_block_rows(I, U):
+    return min(max(SLOPE_SCORE_BLOCK_BYTES // (8 * max(int(I), 1)), 1), max(int(U), 1))
+
+
+def slope_memory_need(I, U):
+    """Device bytes SlopeDeviceState needs: freq (4 I^2), dev and T (8 I^2 each) and one float64 score block."""
+    I, U = int(I), int(U)
+    return 4 * I * I + 8 * I * I + 8 * I * I + slope_block_rows(I, U) * 8 * I
+
+
+class SlopeDeviceState:
+    """The train matrix in dict order (DeviceCSR), user_mean, freq (int32), dev and the scoring table T (float64 [I, I]) of
+    SlopeOne in HBM.
+
+    build() forms freq, dev and T (el_slope_build); set_model() takes a restored (freq, dev, user_mean) and forms T from it
+    (el_slope_table); recommend() scores blocks of at most SLOPE_SCORE_BLOCK_BYTES with el_slope_scores and selects with
+    el_dense_topk_f64; lists short of k are padded with (-1, -inf).  The device memory is checked before anything is allocated.
+
+    R: scipy [U, I] train matrix with the ratings; rows: (indptr, indices) of the same matrix in the order of the reference's
+    train dict (DataSet.dict_order_csr) -- the order the prediction's sum runs in."""
+
+    def __init__(self, ctx, R, rows):
+        import scipy.sparse as sp
+        self.ctx = ctx
+        R = sp.csr_matrix(R, dtype=np.float64)
+        self.U, self.I = int(R.shape[0]), int(R.shape[1])
+        self.need = slope_memory_need(self.I, self.U)
+        free, _total = torch.cuda.mem_get_info(ctx.device)
+        if self.need > free:
+            raise ValueError(f"SlopeOne: {self.I} items need {self.need} bytes of device memory (freq {4 * self.I * self.I}, dev "
+                             f"and the scoring table 2 x {8 * self.I * self.I}, one score block); {free} bytes are free")
+        slope_integer_ratings(R.data)
+        indptr, indices = rows
+        indptr = np.asarray(indptr, dtype=np.int64)
+        if indptr.shape[0] != self.U + 1 or int(indptr[-1]) != R.nnz:
+            raise ValueError("SlopeOne: the dict-order rows do not describe the train matrix")
+        self._host = R
+        self.rows = DeviceCSR(indptr, indices, self.I, ctx.device)
+        users = np.repeat(np.arange(self.U), np.diff(indptr))
+        ratings = np.asarray(R[users, np.asarray(indices, dtype=np.int64)], dtype=np.float64).ravel() if R.nnz else np.zeros(0)
+        self.user_mean_host = slope_user_mean(indptr, ratings)
+        self.user_mean = torch.from_numpy(self.user_mean_host).to(ctx.device)
+        self.freq = self.dev = self.T = None
+        self.block_rows = slope_block_rows(self.I, self.U)
+        self._P = None
+
+    def build(self):
+        self.freq, self.dev, self.T = slope_build(self.ctx, self._host)
+        return self.freq, self.dev
+
+    def set_model(self, freq, dev, user_mean):
+        freq, dev = np.asarray(freq), np.ascontiguousarray(dev, dtype=np.float64)
+        mean = np.ascontiguousarray(np.asarray(user_mean, dtype=np.float64))
+        if freq.shape != (self.I, self.I) or dev.shape != (self.I, self.I) or mean.shape != (self.U,):
+            raise ValueError(f"SlopeOne state has shapes {freq.shape}, {dev.shape}, {mean.shape}; the model expects "
+                             f"{(self.I, self.I)} twice and {(self.U,)}")
+        self.freq = torch.from_numpy(np.ascontiguousarray(freq, dtype=np.int32)).to(self.ctx.device)
+        self.dev = torch.from_numpy(dev).to(self.ctx.device)
+        self.user_mean_host = mean
+        self.user_mean = torch.from_numpy(mean).to(self.ctx.device)
+        self.T = slope_table(self.ctx, self.freq, self.dev)
+
+    def recommend(self, mask, k, start, stop):
+        """Top-k of users [start, stop) under the tagged mask ("excl" | "cand", DeviceCSR): (idx int32, val float64) [n, k] on
+        the device."""
+        if self.T is None:
+            raise _lib.ElliotHipError("SlopeOne: recommend() before build() or set_model()")
+        kind, csr = mask if mask is not None else (None, None)
+        excl, cand = (csr if kind == "excl" else None), (csr if kind == "cand" else None)
+        n = int(stop) - int(start)
+        out_idx = torch.empty((n, k), dtype=torch.int32, device=self.ctx.device)
+        out_val = torch.empty((n, k), dtype=torch.float64, device=self.ctx.device)
+        if self._P is None:
+            self._P = torch.empty((self.block_rows, self.I), dtype=torch.float64, device=self.ctx.device)
+        for s in range(int(start), int(stop), self.block_rows):
+            e = min(s + self.block_rows, int(stop))
+            slope_scores(self.ctx, self.rows, self.user_mean, self.T, s, e, out=self._P)
+            r = s - int(start)
+            dense_topk_f64(self.ctx, self._P, s, e, k, excl=excl, cand=cand, out_idx=out_idx[r:r + e - s],
+                           out_val=out_val[r:r + e - s])
+        check(self.ctx.lib.el_topk_pad_f64(self.ctx.handle, self.ctx.stream(), _ptr(out_idx, torch.int32),
+                                           _ptr(out_val, torch.float64), int(n * k)), "el_topk_pad_f64")
+        return out_idx, out_val
+
+
+# ------------------------------------------------------------------------------------------
 # PureSVD (randomized truncated SVD: CSR x dense fp64, Gram, Cholesky-QR2, projection)
 # ------------------------------------------------------------------------------------------
 PSVD_PIECE_LEN = 2048         # rows longer than this are summed in pieces (el_spmm_csr_f64's long-row plan)

@@ -28,8 +28,9 @@ from .latent_factor_models.WRMF.wrmf import WRMF
 from .autoencoders.EASE_R.ease_r import EASER
 from .latent_factor_models.Slim.slim import Slim
 from .latent_factor_models.PureSVD.pure_svd import PureSVD
+from .algebric.slope_one.slope_one import SlopeOne
 
 __all__ = ["BaseRecommenderModel", "init_charger", "RecMixin", "BPRMF_batch", "BPRMF", "MultiVAE", "MultiDAE", "NeuMF", "GMF",
            "MF", "PMF", "FunkSVD", "LogisticMatrixFactorization", "LMF", "CML", "MF2020", "LightGCN", "NGCF", "ProxyRecommender",
            "ItemKNN", "UserKNN", "iALS", "WRMF", "EASER", "RP3beta", "Slim", "PureSVD",
-           "AttributeItemKNN", "AttributeUserKNN", "VSM", "KaHFM"]
+           "AttributeItemKNN", "AttributeUserKNN", "VSM", "KaHFM", "SlopeOne"]

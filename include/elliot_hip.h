@@ -717,6 +717,48 @@ int el_csr_dense_scores(el_ctx* ctx, void* stream, const int64_t* indptr, const 
  * value is -inf into (-1, -inf), the padding of the KNN and ALS lists.  idx int32[n], val float[n].                        */
 int el_topk_pad(el_ctx* ctx, void* stream, int32_t* idx, const float* val, int64_t n);
 
+/* ---- SlopeOne: exact deviation build, scoring table, ordered fp64 scoring ----------------------------------------- */
+
+/* Replaces SlopeOneModel.initialize (slope_one_model.py:19-37) from INTEGER values (ratings times scale, 1: integers, 2: half
+ * steps); the operands are el_ease_gram's: T = R^T (item -> users) and R (user -> items, rows ascending), max_deg = longest
+ * row of T, max_abs = max |value|.
+ *   freq[c, x] = users who rated both c and x (diagonal included), int32 [I, I] (ldf);
+ *   S[c, x]    = sum over those users of (r_uc - r_ux), counted exactly in LDS (int32 when 2 * max_deg * max_abs fits, int64
+ *                otherwise; beyond the exact fp64 range the call is an error);
+ *   dev[c, x]  = (S[c, x] / scale) / freq[c, x] for c < x, one correctly rounded fp64 division, +0 where freq is 0;
+ *                dev[x, c] = -dev[c, x] exactly (so -0.0 below wherever +0.0 stands above); dev[c, c] = +0.  fp64 [I, I] (ldd).
+ *   T (may be NULL): the scoring table of el_slope_table, written by the same epilogue.  fp64 [I, I] (ldt).
+ * freq and dev start from zero (the reference starts them from np.empty and relies on fresh pages being zero).  Every cell
+ * is written; the same input gives the same bytes on every run.                                                              */
+int el_slope_build(el_ctx* ctx, void* stream,
+                   const int64_t* t_indptr, const int32_t* t_indices, const int32_t* t_vals,
+                   const int64_t* r_indptr, const int32_t* r_indices, const int32_t* r_vals,
+                   int64_t I, int64_t U, int32_t scale, int64_t max_deg, int32_t max_abs,
+                   int32_t* freq, int64_t ldf, double* dev, int64_t ldd, double* T, int64_t ldt);
+
+/* The scoring table of a (freq, dev) pair, e.g. a restored checkpoint: T[j, i] = dev[i, j] where freq[i, j] > 0, a quiet NaN
+ * (0x7ff8000000000000) elsewhere.  Equal to the T of el_slope_build bit for bit.                                             */
+int el_slope_table(el_ctx* ctx, void* stream, const int32_t* freq, int64_t ldf, const double* dev, int64_t ldd, int64_t I,
+                   double* T, int64_t ldt);
+
+/* Replaces SlopeOneModel.predict (slope_one_model.py:42-47) for users [u_start, u_stop) and every item:
+ *   s = +0; for the entries j of row u of the CSR IN STORED ORDER (the order of the reference's train dict): where T[j, i] is
+ *   no NaN, s = s + T[j, i] (one round-to-nearest add) and cnt += 1;  P[u - u_start, i] = user_mean[u] + s / cnt (one correctly
+ *   rounded division, one add), user_mean[u] itself when cnt == 0 (an empty row included).  No fma, no atomics.
+ *   indptr int64 / indices int32 / user_mean fp64 indexed by absolute user id; P fp64 [(u_stop-u_start), I] (ldp).  Select
+ *   with el_dense_topk_f64.                                                                                                 */
+int el_slope_scores(el_ctx* ctx, void* stream, const int64_t* indptr, const int32_t* indices, const double* user_mean,
+                    int64_t u_start, int64_t u_stop, const double* T, int64_t ldt, int64_t I, double* P, int64_t ldp);
+
+/* el_dense_topk for an fp64 block: the same masks, the (value desc, index asc) rule of el_score_topk_f64, fp64 out_val.       */
+int el_dense_topk_f64(el_ctx* ctx, void* stream, const double* preds, int64_t ld, int64_t u_start, int64_t u_stop, int64_t I,
+                      const int64_t* excl_indptr, const int32_t* excl_indices,
+                      const int64_t* cand_indptr, const int32_t* cand_indices,
+                      int32_t k, int32_t* out_idx, double* out_val);
+
+/* el_topk_pad for fp64 values.                                                                                              */
+int el_topk_pad_f64(el_ctx* ctx, void* stream, int32_t* idx, const double* val, int64_t n);
+
 /* ---- PureSVD: tall-skinny fp64 linear algebra for the randomized truncated SVD ------------------------------------ */
 
 #define EL_PSVD_MAX_R 256      /* widest table: factors + 10 (sklearn's oversampling)                                   */
