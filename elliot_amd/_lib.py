@@ -321,6 +321,16 @@ PROTOTYPES = {
     "el_dense_topk_f64": (C.c_int, [C.c_void_p, C.c_void_p, _f64p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                     _i64p, _i32p, _i64p, _i32p, C.c_int32, _i32p, _f64p]),
     "el_topk_pad_f64": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, _f64p, C.c_int64]),
+    "el_bprslim_levels_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                         C.POINTER(C.c_int64)]),
+    "el_bprslim_apply": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, _i32p, _i32p, C.c_int64, C.c_int64, _i64p, _i32p, C.c_int64,
+                                   _f64p, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, _f64p, _f64p]),
+    "el_bprslim_apply_levels": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, _i32p, _i32p, C.c_void_p, C.c_int64, _i64p, _i32p,
+                                          C.c_int64, _f64p, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, _f64p,
+                                          _f64p]),
+    "el_bprslim_table": (C.c_int, [C.c_void_p, C.c_void_p, _f64p, C.c_int64, C.c_int64, _f64p, C.c_int64]),
+    "el_bprslim_scores": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, C.c_int64, C.c_int64, _f64p, C.c_int64, C.c_int64,
+                                    _f64p, C.c_int64]),
     "el_spmm_csr_f64_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "el_spmm_csr_f64": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _f32p, C.c_int64, C.c_int64, _f64p, C.c_int64, C.c_int32,
                                   _f64p, C.c_int64, _i32p, _i64p, C.c_int64, C.c_int64, C.c_int64, _i32p, C.c_void_p, C.c_size_t]),

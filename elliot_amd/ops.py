@@ -1100,6 +1100,183 @@ class SlopeDeviceState:
 
 
 # ------------------------------------------------------------------------------------------
+# BPRSlim (per-triplet BPR SGD on a dense fp64 item-item matrix, ordered fp64 scoring)
+# ------------------------------------------------------------------------------------------
+BPRSLIM_SCORE_BLOCK_BYTES = 1 << 28  # bound of one [Ub, I] float64 score block
+
+
+def bprslim_levels(i_host, j_host, I):
+    """Host-only: (order int32 [n], level_start int64 [n_levels + 1]) of a BPRSlim triplet sequence (el_bprslim_levels_host).
+    A triplet depends on the last earlier one that shares row i or row j of S; the user is no dependency."""
+    lib = _lib.load()
+    i = np.ascontiguousarray(i_host, dtype=np.int32).reshape(-1)
+    j = np.ascontiguousarray(j_host, dtype=np.int32).reshape(-1)
+    if i.shape != j.shape:
+        raise ValueError("bprslim_levels: i and j differ in length")
+    n = i.shape[0]
+    order = np.empty(n, dtype=np.int32)
+    starts = np.empty(n + 2, dtype=np.int64)
+    nl = C.c_int64()
+    check(lib.el_bprslim_levels_host(i.ctypes.data_as(C.c_void_p), j.ctypes.data_as(C.c_void_p), n, int(I),
+                                     order.ctypes.data_as(C.c_void_p), starts.ctypes.data_as(C.c_void_p), n + 2, C.byref(nl)),
+          "el_bprslim_levels_host")
+    return order, starts[: nl.value + 1].copy()
+
+
+def _bprslim_matrix(S, I, name):
+    """(I, leading dimension) of a contiguous float64 [rows >= I, ld >= I] device tensor that holds an [I, I] matrix."""
+    I = int(S.shape[1] if I is None else I)
+    if S.dim() != 2 or S.shape[0] < I or S.shape[1] < I:
+        raise ValueError(f"{name}: a [{I}, {I}] matrix does not fit a tensor of shape {tuple(S.shape)}")
+    return I, int(S.stride(0))
+
+
+def bprslim_apply(ctx, u, i, j, rows, S, lr, li_reg, lj_reg, first=0, n=None, I=None, x_out=None, g_out=None, level_start=None):
+    """BPRSlimModel.train_step (bprslim_model.py:36-67) for the device triplets [first, first + n), concurrently
+    (el_bprslim_apply); with level_start (int64 host array) one launch per level instead (el_bprslim_apply_levels).
+    rows: the train matrix as a DeviceCSR; S: float64 device tensor holding the [I, I] matrix in its leading rows and columns;
+    x_out / g_out: optional float64 [>= number of triplets], the sum and the gradient of every triplet."""
+    I, lds = _bprslim_matrix(S, I, "bprslim_apply")
+    total = int(u.numel())
+    if int(i.numel()) != total or int(j.numel()) != total:
+        raise ValueError("bprslim_apply: u, i and j differ in length")
+    for name, t in (("x_out", x_out), ("g_out", g_out)):
+        if t is not None and int(t.numel()) < total:
+            raise ValueError(f"bprslim_apply: {name} holds fewer than {total} values")
+    tail = (_ptr(rows.indptr, torch.int64), _ptr(rows.indices, torch.int32), int(rows.n_rows), _ptr(S, torch.float64, "S"), lds, I,
+            float(lr), float(li_reg), float(lj_reg), _ptr(x_out, torch.float64, "x_out"), _ptr(g_out, torch.float64, "g_out"))
+    head = (ctx.handle, ctx.stream(), _ptr(u, torch.int32, "u"), _ptr(i, torch.int32, "i"), _ptr(j, torch.int32, "j"))
+    if level_start is not None:
+        starts = np.ascontiguousarray(level_start, dtype=np.int64)
+        if starts.shape[0] < 1 or int(starts[-1]) > total or np.any(np.diff(starts) < 0) or int(starts[0]) < 0:
+            raise ValueError("bprslim_apply: the level table does not describe the triplet arrays")
+        check(ctx.lib.el_bprslim_apply_levels(*head, starts.ctypes.data_as(C.c_void_p), int(starts.shape[0] - 1), *tail),
+              "el_bprslim_apply_levels")
+        return
+    n = total - int(first) if n is None else int(n)
+    if first < 0 or n < 0 or first + n > total:
+        raise ValueError(f"bprslim_apply: triplets [{first}, {first + n}) of {total}")
+    check(ctx.lib.el_bprslim_apply(*head, int(first), n, *tail), "el_bprslim_apply")
+
+
+def bprslim_table(ctx, S, out=None, I=None):
+    """St[s, i] = S[i, s] (el_bprslim_table): the table el_bprslim_scores reads."""
+    I, lds = _bprslim_matrix(S, I, "bprslim_table")
+    if out is None:
+        out = torch.empty((I, I), dtype=torch.float64, device=ctx.device)
+    _, ldt = _bprslim_matrix(out, I, "bprslim_table")
+    check(ctx.lib.el_bprslim_table(ctx.handle, ctx.stream(), _ptr(S, torch.float64, "S"), lds, I, _ptr(out, torch.float64, "St"),
+                                   ldt), "el_bprslim_table")
+    return out
+
+
+def bprslim_scores(ctx, rows, St, u_start, u_stop, out=None, I=None):
+    """BPRSlimModel.predict (bprslim_model.py:69-84) for users [u_start, u_stop) and every item: float64 [n, I]
+    (el_bprslim_scores).  rows: the train matrix as a DeviceCSR, summed in its stored order."""
+    I, ldt = _bprslim_matrix(St, I, "bprslim_scores")
+    n = int(u_stop) - int(u_start)
+    if u_start < 0 or n < 0 or u_stop > rows.n_rows:
+        raise ValueError(f"bprslim_scores: users [{u_start}, {u_stop}) of {rows.n_rows}")
+    if out is None:
+        out = torch.empty((n, I), dtype=torch.float64, device=ctx.device)
+    if out.shape[0] < n or out.shape[1] < I:
+        raise ValueError("bprslim_scores: the output block is smaller than [n, I]")
+    check(ctx.lib.el_bprslim_scores(ctx.handle, ctx.stream(), _ptr(rows.indptr, torch.int64), _ptr(rows.indices, torch.int32),
+                                    int(u_start), int(u_stop), _ptr(St, torch.float64, "St"), ldt, I,
+                                    _ptr(out, torch.float64, "P"), int(out.stride(0))), "el_bprslim_scores")
+    return out
+
+
+def bprslim_block_rows(I, U):
+    return min(max(BPRSLIM_SCORE_BLOCK_BYTES // (8 * max(int(I), 1)), 1), max(int(U), 1))
+
+
+def bprslim_memory_need(I, U):
+    """Device bytes BprSlimDeviceState needs: S and the scoring table St (8 I^2 each) and one float64 score block."""
+    I, U = int(I), int(U)
+    return 8 * I * I + 8 * I * I + bprslim_block_rows(I, U) * 8 * I
+
+
+class BprSlimDeviceState:
+    """The train matrix (DeviceCSR, rows in the order the reference's scipy matrix stores them: ascending item id), the dense
+    item-item matrix S and its transposed scoring table St (float64 [I, I]) of BPRSlim in HBM.
+
+    S starts as zero (the reference starts it from np.empty).  apply_sequential_equivalent() applies a triplet sequence in
+    dependency levels (el_bprslim_levels_host, el_bprslim_apply_levels); set_model() takes a restored S; recommend() rebuilds St
+    when S has moved (el_bprslim_table), scores blocks of at most BPRSLIM_SCORE_BLOCK_BYTES with el_bprslim_scores and selects
+    with el_dense_topk_f64; lists short of k are padded with (-1, -inf).  The device memory is checked before anything is
+    allocated."""
+
+    def __init__(self, ctx, R, lr, li_reg, lj_reg):
+        import scipy.sparse as sp
+        self.ctx = ctx
+        self.U, self.I = int(R.shape[0]), int(R.shape[1])
+        self.need = bprslim_memory_need(self.I, self.U)
+        free, _total = torch.cuda.mem_get_info(ctx.device)
+        if self.need > free:
+            raise ValueError(f"BPRSlim: {self.I} items need {self.need} bytes of device memory (S and the scoring table 2 x "
+                             f"{8 * self.I * self.I}, one score block); {free} bytes are free")
+        R = sp.csr_matrix(R)
+        if not R.has_canonical_format:
+            R = R.copy()
+            R.sum_duplicates()
+        self.lr, self.li_reg, self.lj_reg = float(lr), float(li_reg), float(lj_reg)
+        self.rows = DeviceCSR(np.asarray(R.indptr, dtype=np.int64), R.indices, self.I, ctx.device)
+        self.S = torch.zeros((self.I, self.I), dtype=torch.float64, device=ctx.device)
+        self.St = None                                # rebuilt from S by the first recommend() after S has moved
+        self.block_rows = bprslim_block_rows(self.I, self.U)
+        self._P = None
+
+    def apply_sequential_equivalent(self, u_host, i_host, j_host):
+        """The sequential order of BPRSlimModel.train_step on these triplets: (n_levels, x) with x the float64 host array of
+        every triplet's sum x_uij in the order given."""
+        u, i, j = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (u_host, i_host, j_host))
+        n = u.shape[0]
+        if n and (u.min() < 0 or u.max() >= self.U or min(i.min(), j.min()) < 0 or max(i.max(), j.max()) >= self.I):
+            raise ValueError("BPRSlim: a triplet is out of range")
+        if n == 0:
+            return 0, np.zeros(0, dtype=np.float64)
+        order, starts = bprslim_levels(i, j, self.I)
+        dev = self.ctx.device
+        du, di, dj = (torch.from_numpy(np.ascontiguousarray(a[order])).to(dev) for a in (u, i, j))
+        x_dev = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        bprslim_apply(self.ctx, du, di, dj, self.rows, self.S, self.lr, self.li_reg, self.lj_reg, x_out=x_dev, level_start=starts)
+        self.St = None
+        x = np.empty(n, dtype=np.float64)
+        x[order] = x_dev[:n].cpu().numpy()
+        return int(starts.shape[0] - 1), x
+
+    def set_model(self, S):
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        if S.shape != (self.I, self.I):
+            raise ValueError(f"BPRSlim state has shape {S.shape}; the model expects {(self.I, self.I)}")
+        self.S.copy_(torch.from_numpy(S))
+        self.St = None
+
+    def recommend(self, mask, k, start, stop):
+        """Top-k of users [start, stop) under the tagged mask ("excl" | "cand", DeviceCSR): (idx int32, val float64) [n, k] on
+        the device."""
+        if self.St is None:
+            self.St = bprslim_table(self.ctx, self.S)
+        kind, csr = mask if mask is not None else (None, None)
+        excl, cand = (csr if kind == "excl" else None), (csr if kind == "cand" else None)
+        n = int(stop) - int(start)
+        out_idx = torch.empty((n, k), dtype=torch.int32, device=self.ctx.device)
+        out_val = torch.empty((n, k), dtype=torch.float64, device=self.ctx.device)
+        if self._P is None:
+            self._P = torch.empty((self.block_rows, self.I), dtype=torch.float64, device=self.ctx.device)
+        for s in range(int(start), int(stop), self.block_rows):
+            e = min(s + self.block_rows, int(stop))
+            bprslim_scores(self.ctx, self.rows, self.St, s, e, out=self._P)
+            r = s - int(start)
+            dense_topk_f64(self.ctx, self._P, s, e, k, excl=excl, cand=cand, out_idx=out_idx[r:r + e - s],
+                           out_val=out_val[r:r + e - s])
+        check(self.ctx.lib.el_topk_pad_f64(self.ctx.handle, self.ctx.stream(), _ptr(out_idx, torch.int32),
+                                           _ptr(out_val, torch.float64), int(n * k)), "el_topk_pad_f64")
+        return out_idx, out_val
+
+
+# ------------------------------------------------------------------------------------------
 # PureSVD (randomized truncated SVD: CSR x dense fp64, Gram, Cholesky-QR2, projection)
 # ------------------------------------------------------------------------------------------
 PSVD_PIECE_LEN = 2048         # rows longer than this are summed in pieces (el_spmm_csr_f64's long-row plan)

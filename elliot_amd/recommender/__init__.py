@@ -29,8 +29,9 @@ from .autoencoders.EASE_R.ease_r import EASER
 from .latent_factor_models.Slim.slim import Slim
 from .latent_factor_models.PureSVD.pure_svd import PureSVD
 from .algebric.slope_one.slope_one import SlopeOne
+from .latent_factor_models.BPRSlim.bprslim import BPRSlim
 
 __all__ = ["BaseRecommenderModel", "init_charger", "RecMixin", "BPRMF_batch", "BPRMF", "MultiVAE", "MultiDAE", "NeuMF", "GMF",
            "MF", "PMF", "FunkSVD", "LogisticMatrixFactorization", "LMF", "CML", "MF2020", "LightGCN", "NGCF", "ProxyRecommender",
            "ItemKNN", "UserKNN", "iALS", "WRMF", "EASER", "RP3beta", "Slim", "PureSVD",
-           "AttributeItemKNN", "AttributeUserKNN", "VSM", "KaHFM", "SlopeOne"]
+           "AttributeItemKNN", "AttributeUserKNN", "VSM", "KaHFM", "SlopeOne", "BPRSlim"]

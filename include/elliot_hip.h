@@ -759,6 +759,49 @@ int el_dense_topk_f64(el_ctx* ctx, void* stream, const double* preds, int64_t ld
 /* el_topk_pad for fp64 values.                                                                                              */
 int el_topk_pad_f64(el_ctx* ctx, void* stream, int32_t* idx, const double* val, int64_t n);
 
+/* ---- BPRSlim: per-triplet BPR SGD on a dense fp64 item-item matrix, ordered fp64 scoring -------------------------- */
+
+/* Host helper (no GPU): dependency levels that make concurrent application equal to the sequential order of
+ * BPRSlimModel.train_step (bprslim_model.py:36-67).  Triplet t reads and writes rows i_t and j_t of S and nothing else:
+ *   level[t] = 1 + max(level of the last earlier triplet whose i or j equals i_t or j_t);  the user is no dependency.
+ * order_host / level_start_host / n_levels as el_bprsgd_levels_host.  Two triplets on one row are ordered even when their
+ * users' columns are disjoint.                                                                                            */
+int el_bprslim_levels_host(const int32_t* i_host, const int32_t* j_host, int64_t n, int64_t I,
+                           int32_t* order_host, int64_t* level_start_host, int64_t level_start_cap, int64_t* n_levels);
+
+/* Replaces BPRSlimModel.train_step (bprslim_model.py:36-67) for triplets [first, first+n), applied concurrently: the caller
+ * guarantees that no two of them share a row of S (el_bprslim_levels_host) for the result to equal the sequential reference.
+ *   x = sum over the entries s of row u of the CSR (indptr int64 [U + 1], indices int32, distinct columns) of the rounded
+ *       differences S[i, s] - S[j, s];  g = 1 / (1 + exp(x)), one correctly rounded division;
+ *   S[i, s] = S[i, s] + lr * (g - li_reg * S[i, s]) for s != i;  S[j, s] = S[j, s] - lr * (g - lj_reg * S[j, s]) for s != j,
+ *       every operation rounded on its own, row i's cell stored before row j's is read.
+ * One wave per triplet: lane l adds the differences of positions l, l + 64, ... in ascending order from +0, the 64 lane sums go
+ * through the xor shuffle tree.  The shape of the sum depends on the row length alone; no float atomics; the same input gives
+ * the same bytes on every run.  A row of length 0 gives x = +0, g = 0.5 and no store.  No cell outside the seen columns of rows
+ * i and j is touched.  A triplet or a column out of range is skipped, its x_out and g_out are NaN.
+ *   S fp64 [I, I] (lds);  x_out / g_out (either may be NULL): fp64 indexed by the triplet's position, the sum and the gradient
+ *   the kernel used.                                                                                                      */
+int el_bprslim_apply(el_ctx* ctx, void* stream, const int32_t* u, const int32_t* i, const int32_t* j, int64_t first, int64_t n,
+                     const int64_t* indptr, const int32_t* indices, int64_t U, double* S, int64_t lds, int64_t I,
+                     double lr, double li_reg, double lj_reg, double* x_out, double* g_out);
+
+/* One launch of el_bprslim_apply per level: segments [level_start_host[L], level_start_host[L+1]) of the (already
+ * level-ordered) device triplet arrays, L = 0..n_levels-1, in stream order.                                              */
+int el_bprslim_apply_levels(el_ctx* ctx, void* stream, const int32_t* u, const int32_t* i, const int32_t* j,
+                            const int64_t* level_start_host, int64_t n_levels,
+                            const int64_t* indptr, const int32_t* indices, int64_t U, double* S, int64_t lds, int64_t I,
+                            double lr, double li_reg, double lj_reg, double* x_out, double* g_out);
+
+/* The scoring table St[s, i] = S[i, s]: fp64 [I, I] on both sides (lds, ldt), any I; cells beyond column I are not touched.  */
+int el_bprslim_table(el_ctx* ctx, void* stream, const double* S, int64_t lds, int64_t I, double* St, int64_t ldt);
+
+/* Replaces BPRSlimModel.predict (bprslim_model.py:69-84) for users [u_start, u_stop) and every item:
+ *   P[u - u_start, i] = +0 + St[s, i] over the entries s of row u IN STORED ORDER, one round-to-nearest add each (an empty row:
+ *   +0).  No fma, no atomics.  indptr int64 / indices int32 indexed by absolute user id; P fp64 [(u_stop-u_start), I] (ldp).
+ *   Select with el_dense_topk_f64.                                                                                        */
+int el_bprslim_scores(el_ctx* ctx, void* stream, const int64_t* indptr, const int32_t* indices, int64_t u_start, int64_t u_stop,
+                      const double* St, int64_t ldt, int64_t I, double* P, int64_t ldp);
+
 /* ---- PureSVD: tall-skinny fp64 linear algebra for the randomized truncated SVD ------------------------------------ */
 
 #define EL_PSVD_MAX_R 256      /* widest table: factors + 10 (sklearn's oversampling)                                   */
