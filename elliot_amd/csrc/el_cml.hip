@@ -227,7 +227,7 @@ template <int VW, int PHASE>
 int launch_rows(CmlArgs p, el_ctx* ctx, hipStream_t s) {
     int cpl = 1;
     p.lpt = el_pick_lpt(p.st.F, VW, &cpl);
-    EL_REQUIRE(cpl <= 4, "el_cml_train_step: F=%d too large for this build (max %d)", p.st.F, 64 * 4 * VW);
+    EL_REQUIRE(cpl <= 4, "k_cml_rows: F=%d reached the launch (cml_check refuses such a size, with the caller's name)", p.st.F);
     const int64_t want = (p.B * p.lpt + 255) / 256, cap = (int64_t)ctx->cus * 16;
     const unsigned grid = (unsigned)(want < cap ? want : cap);
     const char* nm = PHASE == 0 ? "k_cml_fwd" : "k_cml_bwd";
@@ -245,6 +245,12 @@ static int cml_check(const el_bprmf_state* stp, const int32_t* u, const int32_t*
     EL_REQUIRE(stp->U > 0 && stp->I > 0 && stp->F > 0, "%s: bad shape", who);
     EL_REQUIRE(u && i && j, "%s: null triplet arrays", who);
     EL_REQUIRE(B < (1LL << 31), "%s: batch too large", who);
+    // refused here, before anything is launched: el_cml_grads would otherwise have added the hinge sum to the loss (k_cml_coef) and sorted
+    // the batch by the time its row kernels turn the size down
+    int cpl = 1;
+    const int vw = vec_ok(*stp) ? 4 : 1;
+    el_pick_lpt(stp->F, vw, &cpl);
+    EL_REQUIRE(cpl <= 4, "%s: F=%d too large for this build (max %d)", who, stp->F, 64 * 4 * vw);
     return 0;
 }
 
