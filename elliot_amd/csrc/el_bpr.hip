@@ -11,6 +11,7 @@
 #include <stdlib.h>
 #include <vector>
 #include "el_common.h"
+#include "el_levels.h"
 
 // ---------------------------------------------------------------------------------------
 // K1: Philox sampler
@@ -913,45 +914,26 @@ extern "C" int el_bprsgd_apply_levels(el_ctx* ctx, void* stream, const el_bprsgd
     if (int rc = el_bind(ctx)) return rc;
     if (int rc = check_sgd_state(stp)) return rc;
     EL_REQUIRE(u && i && j && level_start_host && n_levels >= 0, "el_bprsgd_apply_levels: bad arguments");
-    for (int64_t L = 0; L < n_levels; ++L) {
-        int64_t a = level_start_host[L], b = level_start_host[L + 1];
-        if (b > a)
-            if (int rc = launch_bprsgd(*stp, u, i, j, a, b - a, (hipStream_t)stream)) return rc;
-    }
-    return 0;
+    int64_t bad = 0;
+    const int rc = el_levels_apply(level_start_host, n_levels, &bad, [&](int64_t first, int64_t n) {
+        return launch_bprsgd(*stp, u, i, j, first, n, (hipStream_t)stream);
+    });
+    EL_REQUIRE(rc != EL_LEVELS_BAD_TABLE, "el_bprsgd_apply_levels: level %lld is [%lld, %lld)", (long long)bad,
+               (long long)level_start_host[bad], (long long)level_start_host[bad + 1]);
+    return rc;
 }
 
-// Host-only scheduling helper: dependency levels of a triplet sequence.
+// Host-only scheduling helper: dependency levels of a triplet sequence (el_levels.h): row u of P, rows i and j of Q.
 extern "C" int el_bprsgd_levels_host(const int32_t* u, const int32_t* i, const int32_t* j, int64_t n, int64_t U,
                                      int64_t I, int32_t* order, int64_t* level_start, int64_t level_start_cap,
                                      int64_t* n_levels) {
     EL_REQUIRE(u && i && j && order && level_start && n_levels, "el_bprsgd_levels_host: null pointer");
     EL_REQUIRE(n >= 0 && n < 0x7fffffffLL, "el_bprsgd_levels_host: n out of range");
-    std::vector<int32_t> lu((size_t)U, 0), li((size_t)I, 0), lev((size_t)n);
-    int32_t maxl = 0;
-    for (int64_t t = 0; t < n; ++t) {
-        EL_REQUIRE(u[t] >= 0 && u[t] < U && i[t] >= 0 && i[t] < I && j[t] >= 0 && j[t] < I,
-                   "el_bprsgd_levels_host: triplet %lld out of range", (long long)t);
-        int32_t a = lu[u[t]], b = li[i[t]], c = li[j[t]];
-        int32_t l = a > b ? a : b;
-        l = (l > c ? l : c) + 1;
-        lev[t] = l;
-        lu[u[t]] = l;
-        li[i[t]] = l;
-        li[j[t]] = l;
-        if (l > maxl) maxl = l;
-    }
-    EL_REQUIRE((int64_t)maxl + 1 <= level_start_cap, "el_bprsgd_levels_host: %d levels exceed capacity %lld", maxl,
+    int64_t bad = 0;
+    const int rc = el_levels_build<0, 1, 1>({u, i, j}, {U, I}, n, order, level_start, level_start_cap, n_levels, &bad);
+    EL_REQUIRE(rc != EL_LEVELS_BAD_ID, "el_bprsgd_levels_host: triplet %lld out of range", (long long)bad);
+    EL_REQUIRE(rc != EL_LEVELS_NO_ROOM, "el_bprsgd_levels_host: %d levels exceed capacity %lld", (int)bad,
                (long long)level_start_cap);
-    // level l (1-based) occupies order[level_start[l-1] .. level_start[l])
-    std::vector<int64_t> count((size_t)maxl + 1, 0);
-    for (int64_t t = 0; t < n; ++t) count[lev[t]]++;
-    level_start[0] = 0;
-    for (int32_t l = 1; l <= maxl; ++l) level_start[l] = level_start[l - 1] + count[l];
-    std::vector<int64_t> cur((size_t)maxl + 1, 0);
-    for (int32_t l = 1; l <= maxl; ++l) cur[l] = level_start[l - 1];
-    for (int64_t t = 0; t < n; ++t) order[cur[lev[t]]++] = (int32_t)t;
-    *n_levels = maxl;
     return 0;
 }
 

@@ -23,13 +23,11 @@
 //   edges    a row of length 0: x = +0, g = 0.5, no store.  No cell outside the seen columns of rows i and j is touched.  A
 //            triplet or a column out of range is skipped (x_out = g_out = NaN for the triplet).
 #include "el_common.h"
-
-#include <vector>
+#include "el_levels.h"
+#include "el_rowscore.h"
 
 #define SLIM_WAVES 4             // triplets per workgroup of k_bprslim_apply
 #define SLIM_KEEP 4              // positions per lane that k_bprslim_apply keeps in registers between the sum and the update
-#define SLIM_TR 32               // k_bprslim_table transposes SLIM_TR x SLIM_TR tiles
-#define SLIM_SLAB 1024           // targets per workgroup of k_bprslim_scores
 
 namespace {
 
@@ -138,52 +136,18 @@ __global__ __launch_bounds__(SLIM_WAVES * 64) void k_bprslim_apply(SlimApply p, 
     }
 }
 
-// St[s, i] = S[i, s]: a transpose by SLIM_TR x SLIM_TR tiles through LDS
-__global__ __launch_bounds__(SLIM_TR * 8) void k_bprslim_table(const double* __restrict__ S, int64_t lds, int64_t I,
-                                                               double* __restrict__ St, int64_t ldt) {
-    __shared__ double tile[SLIM_TR][SLIM_TR + 1];
-    const int tx = threadIdx.x % SLIM_TR, ty = threadIdx.x / SLIM_TR;
-    const int64_t i0 = (int64_t)blockIdx.y * SLIM_TR, s0 = (int64_t)blockIdx.x * SLIM_TR;
-    for (int r = ty; r < SLIM_TR; r += 8) {
-        const int64_t i = i0 + r, s = s0 + tx;
-        if (i < I && s < I) tile[r][tx] = S[i * lds + s];
-    }
-    __syncthreads();
-    for (int r = ty; r < SLIM_TR; r += 8) {
-        const int64_t s = s0 + r, i = i0 + tx;
-        if (i < I && s < I) St[s * ldt + i] = tile[tx][r];
-    }
-}
+// St[s, i] = S[i, s] on k_transpose_f64 (el_rowscore.h)
+struct SlimTableLoad {
+    const double* S;
+    int64_t lds;
+    __device__ double operator()(int64_t i, int64_t s) const { return S[i * lds + s]; }
+};
 
-// user per blockIdx.x (workgroups in flight share one slab of St), SLIM_SLAB targets per blockIdx.y; lanes across targets, the
-// chain sequential in the row's stored order
-__global__ __launch_bounds__(256) void k_bprslim_scores(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
-                                                        int64_t u_start, const double* __restrict__ St, int64_t ldt, int64_t I,
-                                                        double* __restrict__ P, int64_t ldp) {
-    constexpr int Q = SLIM_SLAB / 256;
-    const int64_t u = u_start + blockIdx.x;
-    const int64_t c0 = (int64_t)blockIdx.y * SLIM_SLAB + threadIdx.x;
-    const int64_t e0 = indptr[u], e1 = indptr[u + 1];
-    double acc[Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) acc[q] = 0.0;
-    for (int64_t e = e0; e < e1; ++e) {
-        const int64_t s = indices[e];
-        if (s < 0 || s >= I) continue;                          // a column out of range is no cell of St
-        const double* t = St + s * ldt;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const int64_t c = c0 + 256 * q;
-            if (c < I) acc[q] = __dadd_rn(acc[q], t[c]);        // bprslim_model.py:82
-        }
-    }
-    double* out = P + (int64_t)blockIdx.x * ldp;
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        const int64_t c = c0 + 256 * q;
-        if (c < I) out[c] = acc[q];
-    }
-}
+// bprslim_model.py:82 on k_row_scores: a plain sum; a column out of range is no cell of St
+struct SlimScoreOp : RowScoreOp<double> {
+    static constexpr bool CHECK_COLS = true;
+    __device__ void step(double& a, int, double v) const { a = __dadd_rn(a, v); }
+};
 
 int check_slim_apply(const char* who, const int32_t* u, const int32_t* i, const int32_t* j, const int64_t* indptr,
                      const int32_t* indices, int64_t U, const double* S, int64_t lds, int64_t I) {
@@ -232,13 +196,13 @@ extern "C" int el_bprslim_apply_levels(el_ctx* ctx, void* stream, const int32_t*
     if (int rc = check_slim_apply("el_bprslim_apply_levels", u, i, j, indptr, indices, U, S, lds, I)) return rc;
     EL_REQUIRE(level_start_host && n_levels >= 0, "el_bprslim_apply_levels: bad level table");
     const SlimApply p = slim_args(u, i, j, indptr, indices, U, S, lds, I, lr, li_reg, lj_reg, x_out, g_out);
-    for (int64_t L = 0; L < n_levels; ++L) {
-        const int64_t a = level_start_host[L], b = level_start_host[L + 1];
-        EL_REQUIRE(a >= 0 && b >= a, "el_bprslim_apply_levels: level %lld is [%lld, %lld)", (long long)L, (long long)a, (long long)b);
-        if (b > a)
-            if (int rc = launch_slim_apply(p, a, b - a, (hipStream_t)stream)) return rc;
-    }
-    return 0;
+    int64_t bad = 0;
+    const int rc = el_levels_apply(level_start_host, n_levels, &bad, [&](int64_t first, int64_t n) {
+        return launch_slim_apply(p, first, n, (hipStream_t)stream);
+    });
+    EL_REQUIRE(rc != EL_LEVELS_BAD_TABLE, "el_bprslim_apply_levels: level %lld is [%lld, %lld)", (long long)bad,
+               (long long)level_start_host[bad], (long long)level_start_host[bad + 1]);
+    return rc;
 }
 
 // Host-only scheduling helper: rows i and j of S are all a triplet reads or writes, so the user is no dependency.
@@ -247,54 +211,21 @@ extern "C" int el_bprslim_levels_host(const int32_t* i, const int32_t* j, int64_
     EL_REQUIRE(i && j && order && level_start && n_levels, "el_bprslim_levels_host: null pointer");
     EL_REQUIRE(n >= 0 && n < 0x7fffffffLL && I >= 1, "el_bprslim_levels_host: n or I out of range");
     EL_REQUIRE(level_start_cap >= 1, "el_bprslim_levels_host: no room for the level table");
-    std::vector<int32_t> li((size_t)I, 0), lev((size_t)n);
-    int32_t maxl = 0;
-    for (int64_t t = 0; t < n; ++t) {
-        EL_REQUIRE(i[t] >= 0 && i[t] < I && j[t] >= 0 && j[t] < I, "el_bprslim_levels_host: triplet %lld out of range", (long long)t);
-        const int32_t a = li[i[t]], b = li[j[t]];
-        const int32_t l = (a > b ? a : b) + 1;
-        lev[t] = l;
-        li[i[t]] = l;
-        li[j[t]] = l;
-        if (l > maxl) maxl = l;
-    }
-    EL_REQUIRE((int64_t)maxl + 1 <= level_start_cap, "el_bprslim_levels_host: %d levels exceed capacity %lld", maxl,
+    int64_t bad = 0;
+    const int rc = el_levels_build<0, 0>({i, j}, {I}, n, order, level_start, level_start_cap, n_levels, &bad);
+    EL_REQUIRE(rc != EL_LEVELS_BAD_ID, "el_bprslim_levels_host: triplet %lld out of range", (long long)bad);
+    EL_REQUIRE(rc != EL_LEVELS_NO_ROOM, "el_bprslim_levels_host: %d levels exceed capacity %lld", (int)bad,
                (long long)level_start_cap);
-    // level l (1-based) occupies order[level_start[l-1] .. level_start[l]); within a level the sequence order is kept
-    std::vector<int64_t> count((size_t)maxl + 1, 0);
-    for (int64_t t = 0; t < n; ++t) count[lev[t]]++;
-    level_start[0] = 0;
-    for (int32_t l = 1; l <= maxl; ++l) level_start[l] = level_start[l - 1] + count[l];
-    std::vector<int64_t> cur((size_t)maxl + 1, 0);
-    for (int32_t l = 1; l <= maxl; ++l) cur[l] = level_start[l - 1];
-    for (int64_t t = 0; t < n; ++t) order[cur[lev[t]]++] = (int32_t)t;
-    *n_levels = maxl;
     return 0;
 }
 
 extern "C" int el_bprslim_table(el_ctx* ctx, void* stream, const double* S, int64_t lds, int64_t I, double* St, int64_t ldt) {
-    if (int rc = el_bind(ctx)) return rc;
-    EL_REQUIRE(S && St, "el_bprslim_table: null pointer");
-    EL_REQUIRE(I >= 1 && I < 0x7fffffffLL && (I + SLIM_TR - 1) / SLIM_TR < 65536, "el_bprslim_table: bad item count %lld",
-               (long long)I);
-    EL_REQUIRE(lds >= I && ldt >= I, "el_bprslim_table: leading dimensions below I");
-    const unsigned nt = (unsigned)((I + SLIM_TR - 1) / SLIM_TR);
-    EL_LAUNCH("k_bprslim_table", k_bprslim_table, dim3(nt, nt), dim3(SLIM_TR * 8), 0, (hipStream_t)stream, S, lds, I, St, ldt);
-    EL_CHECK_LAUNCH();
-    return 0;
+    return el_transpose_f64("el_bprslim_table", "k_bprslim_table", ctx, stream, S && St, lds >= I && ldt >= I,
+                            SlimTableLoad{S, lds}, I, St, ldt);
 }
 
 extern "C" int el_bprslim_scores(el_ctx* ctx, void* stream, const int64_t* indptr, const int32_t* indices, int64_t u_start,
                                  int64_t u_stop, const double* St, int64_t ldt, int64_t I, double* P, int64_t ldp) {
-    if (int rc = el_bind(ctx)) return rc;
-    EL_REQUIRE(indptr && indices && St && P, "el_bprslim_scores: null pointer");
-    EL_REQUIRE(u_start >= 0 && u_stop >= u_start && u_stop - u_start < 0x7fffffffLL, "el_bprslim_scores: bad user range");
-    EL_REQUIRE(I >= 1 && I < 0x7fffffffLL && (I + SLIM_SLAB - 1) / SLIM_SLAB < 65536, "el_bprslim_scores: bad item count %lld",
-               (long long)I);
-    EL_REQUIRE(ldt >= I && ldp >= I, "el_bprslim_scores: leading dimensions below I");
-    if (u_stop == u_start) return 0;
-    EL_LAUNCH("k_bprslim_scores", k_bprslim_scores, dim3((unsigned)(u_stop - u_start), (unsigned)((I + SLIM_SLAB - 1) / SLIM_SLAB)),
-              dim3(256), 0, (hipStream_t)stream, indptr, indices, u_start, St, ldt, I, P, ldp);
-    EL_CHECK_LAUNCH();
-    return 0;
+    return el_row_scores("el_bprslim_scores", "k_bprslim_scores", ctx, stream, indptr && indices && St && P, indptr, indices,
+                         u_start, u_stop, SlimScoreOp{{St, ldt}}, I, P, ldp);
 }

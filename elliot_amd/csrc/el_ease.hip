@@ -16,13 +16,13 @@
 // one owner and a fixed order and nothing floating-point is added with atomics: the same input gives the same bits on every run.
 // Kernel boundaries are the only grid-wide synchronisation.
 #include "el_common.h"
+#include "el_rowscore.h"
 
 #define EASE_GRAM_THREADS 256
 #define EASE_GRAM_TILE 16384     // LDS counters per pass over the catalogue
 #define INV_NB 64                // panel width of the LU (the inner dimension of every MFMA update)
 #define INV_TILE 64              // rows and columns of C per workgroup of k_inv_update
 #define INV_NONE 0x7fffffff
-#define EASE_SLAB 1024           // columns of B per workgroup of k_csr_dense_scores
 
 typedef double el_d4 __attribute__((ext_vector_type(4)));
 
@@ -252,34 +252,12 @@ __global__ __launch_bounds__(256) void k_ease_weights(const double* __restrict__
     B[j * ldb + i] = i == j ? 0.0f : __double2float_rn(__ddiv_rn(-P[j * ldp + i], d[i]));
 }
 
-// user per blockIdx.x (the fastest-dispatched index: workgroups in flight share one slab of B), EASE_SLAB columns per blockIdx.y
-__global__ __launch_bounds__(256) void k_csr_dense_scores(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
-                                                          const float* __restrict__ vals, int64_t u_start,
-                                                          const float* __restrict__ B, int64_t ldb, int64_t I,
-                                                          float* __restrict__ S, int64_t lds) {
-    constexpr int Q = EASE_SLAB / 256;
-    const int64_t u = u_start + blockIdx.x;
-    const int64_t c0 = (int64_t)blockIdx.y * EASE_SLAB + threadIdx.x;
-    const int64_t e0 = indptr[u], e1 = indptr[u + 1];
-    float acc[Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) acc[q] = 0.0f;
-    for (int64_t e = e0; e < e1; ++e) {
-        const float v = vals[e];
-        const float* b = B + (int64_t)indices[e] * ldb;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const int64_t c = c0 + 256 * q;
-            if (c < I) acc[q] = __fadd_rn(acc[q], __fmul_rn(v, b[c]));
-        }
-    }
-    float* s = S + (int64_t)blockIdx.x * lds;
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        const int64_t c = c0 + 256 * q;
-        if (c < I) s[c] = acc[q];
-    }
-}
+// scipy's csr_matvecs on k_row_scores (el_rowscore.h): fp32, one rounded product and one rounded sum per entry
+struct EaseScoreOp : RowScoreOp<float> {
+    const float* vals;
+    __device__ float weight(int64_t e) const { return vals[e]; }
+    __device__ void step(float& a, float w, float x) const { a = __fadd_rn(a, __fmul_rn(w, x)); }
+};
 
 // el_dense_topk fills a short list with masked items at -inf; EASER pads with (-1, -inf) instead (the KNN and ALS convention)
 __global__ void k_topk_pad(int32_t* __restrict__ idx, const float* __restrict__ val, int64_t n) {
@@ -446,15 +424,6 @@ extern "C" int el_ease_weights(el_ctx* ctx, void* stream, const double* P, int64
 
 extern "C" int el_csr_dense_scores(el_ctx* ctx, void* stream, const int64_t* indptr, const int32_t* indices, const float* vals,
                                    int64_t u_start, int64_t u_stop, const float* B, int64_t ldb, int64_t I, float* S, int64_t lds) {
-    if (int rc = el_bind(ctx)) return rc;
-    EL_REQUIRE(indptr && indices && vals && B && S, "el_csr_dense_scores: null pointer");
-    EL_REQUIRE(u_start >= 0 && u_stop >= u_start && u_stop - u_start < 0x7fffffffLL, "el_csr_dense_scores: bad user range");
-    EL_REQUIRE(I >= 1 && I < 0x7fffffffLL && (I + EASE_SLAB - 1) / EASE_SLAB < 65536, "el_csr_dense_scores: bad item count %lld",
-               (long long)I);
-    EL_REQUIRE(ldb >= I && lds >= I, "el_csr_dense_scores: leading dimensions below I");
-    if (u_stop == u_start) return 0;
-    EL_LAUNCH("k_csr_dense_scores", k_csr_dense_scores, dim3((unsigned)(u_stop - u_start), (unsigned)((I + EASE_SLAB - 1) / EASE_SLAB)),
-              dim3(256), 0, (hipStream_t)stream, indptr, indices, vals, u_start, B, ldb, I, S, lds);
-    EL_CHECK_LAUNCH();
-    return 0;
+    return el_row_scores("el_csr_dense_scores", "k_csr_dense_scores", ctx, stream, indptr && indices && vals && B && S, indptr,
+                         indices, u_start, u_stop, EaseScoreOp{{B, ldb}, vals}, I, S, lds);
 }

@@ -10,11 +10,10 @@
 // __dadd_rn per cell in the stored order of the row, from +0.  Nothing floating-point is added with atomics and there is no
 // fma: with integer or half-step ratings freq, dev and every prediction equal the reference's bit for bit.
 #include "el_common.h"
+#include "el_rowscore.h"
 
 #define SLOPE_THREADS 256
 #define SLOPE_TILE 8192          // LDS cells per pass over the catalogue (a freq and an S counter each)
-#define SLOPE_SLAB 1024          // targets per workgroup of k_slope_scores
-#define SLOPE_TR 32              // k_slope_table transposes SLOPE_TR x SLOPE_TR tiles
 
 namespace {
 
@@ -77,63 +76,28 @@ __global__ __launch_bounds__(SLOPE_THREADS) void k_slope_build(SlopeBuild p) {
     }
 }
 
-// T[j, i] = dev[i, j] where freq[i, j] > 0: a transpose by SLOPE_TR x SLOPE_TR tiles through LDS
-__global__ __launch_bounds__(SLOPE_TR * 8) void k_slope_table(const int32_t* __restrict__ freq, int64_t ldf,
-                                                              const double* __restrict__ dev, int64_t ldd, int64_t I,
-                                                              double* __restrict__ T, int64_t ldt) {
-    __shared__ double tile[SLOPE_TR][SLOPE_TR + 1];
-    const int tx = threadIdx.x % SLOPE_TR, ty = threadIdx.x / SLOPE_TR;
-    const int64_t i0 = (int64_t)blockIdx.y * SLOPE_TR, j0 = (int64_t)blockIdx.x * SLOPE_TR;
-    for (int r = ty; r < SLOPE_TR; r += 8) {
-        const int64_t i = i0 + r, j = j0 + tx;
-        if (i < I && j < I) tile[r][tx] = freq[i * ldf + j] > 0 ? dev[i * ldd + j] : slope_nan();
-    }
-    __syncthreads();
-    for (int r = ty; r < SLOPE_TR; r += 8) {
-        const int64_t j = j0 + r, i = i0 + tx;
-        if (i < I && j < I) T[j * ldt + i] = tile[tx][r];
-    }
-}
+// T[j, i] = dev[i, j] where freq[i, j] > 0, on k_transpose_f64 (el_rowscore.h)
+struct SlopeTableLoad {
+    const int32_t* freq;
+    int64_t ldf;
+    const double* dev;
+    int64_t ldd;
+    __device__ double operator()(int64_t i, int64_t j) const { return freq[i * ldf + j] > 0 ? dev[i * ldd + j] : slope_nan(); }
+};
 
-// user per blockIdx.x (the fastest-dispatched index: workgroups in flight share one slab of T), SLOPE_SLAB targets per
-// blockIdx.y; lanes across targets, the chain sequential in the row's stored order
-__global__ __launch_bounds__(256) void k_slope_scores(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
-                                                      const double* __restrict__ mean, int64_t u_start,
-                                                      const double* __restrict__ T, int64_t ldt, int64_t I,
-                                                      double* __restrict__ P, int64_t ldp) {
-    constexpr int Q = SLOPE_SLAB / 256;
-    const int64_t u = u_start + blockIdx.x;
-    const int64_t c0 = (int64_t)blockIdx.y * SLOPE_SLAB + threadIdx.x;
-    const int64_t e0 = indptr[u], e1 = indptr[u + 1];
-    double acc[Q];
-    int cnt[Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        acc[q] = 0.0;
-        cnt[q] = 0;
-    }
-    for (int64_t e = e0; e < e1; ++e) {
-        const double* t = T + (int64_t)indices[e] * ldt;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const int64_t c = c0 + 256 * q;
-            if (c < I) {
-                const double v = t[c];
-                if (v == v) {                             // a NaN cell: freq[c, j] == 0, not part of Ri
-                    acc[q] = __dadd_rn(acc[q], v);
-                    ++cnt[q];
-                }
-            }
+// slope_one_model.py:42-47 on k_row_scores: a NaN cell (freq[c, j] == 0) is not part of Ri
+struct SlopeScoreOp : RowScoreOp<double> {
+    struct Acc { double a; int n; };
+    const double* mean;
+    __device__ void step(Acc& s, int, double v) const {
+        if (v == v) {
+            s.a = __dadd_rn(s.a, v);
+            ++s.n;
         }
     }
-    const double m = mean[u];
-    double* s = P + (int64_t)blockIdx.x * ldp;
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        const int64_t c = c0 + 256 * q;
-        if (c < I) s[c] = cnt[q] ? __dadd_rn(m, __ddiv_rn(acc[q], (double)cnt[q])) : m;
-    }
-}
+    __device__ double base(int64_t u) const { return mean[u]; }
+    __device__ double finish(const Acc& s, double m) const { return s.n ? __dadd_rn(m, __ddiv_rn(s.a, (double)s.n)) : m; }
+};
 
 }  // namespace
 
@@ -174,29 +138,12 @@ extern "C" int el_slope_build(el_ctx* ctx, void* stream, const int64_t* t_indptr
 
 extern "C" int el_slope_table(el_ctx* ctx, void* stream, const int32_t* freq, int64_t ldf, const double* dev, int64_t ldd,
                               int64_t I, double* T, int64_t ldt) {
-    if (int rc = el_bind(ctx)) return rc;
-    EL_REQUIRE(freq && dev && T, "el_slope_table: null pointer");
-    EL_REQUIRE(I >= 1 && I < 0x7fffffffLL && (I + SLOPE_TR - 1) / SLOPE_TR < 65536, "el_slope_table: bad item count %lld",
-               (long long)I);
-    EL_REQUIRE(ldf >= I && ldd >= I && ldt >= I, "el_slope_table: leading dimensions below I");
-    const unsigned nt = (unsigned)((I + SLOPE_TR - 1) / SLOPE_TR);
-    EL_LAUNCH("k_slope_table", k_slope_table, dim3(nt, nt), dim3(SLOPE_TR * 8), 0, (hipStream_t)stream, freq, ldf, dev, ldd, I, T,
-              ldt);
-    EL_CHECK_LAUNCH();
-    return 0;
+    return el_transpose_f64("el_slope_table", "k_slope_table", ctx, stream, freq && dev && T, ldf >= I && ldd >= I && ldt >= I,
+                            SlopeTableLoad{freq, ldf, dev, ldd}, I, T, ldt);
 }
 
 extern "C" int el_slope_scores(el_ctx* ctx, void* stream, const int64_t* indptr, const int32_t* indices, const double* user_mean,
                                int64_t u_start, int64_t u_stop, const double* T, int64_t ldt, int64_t I, double* P, int64_t ldp) {
-    if (int rc = el_bind(ctx)) return rc;
-    EL_REQUIRE(indptr && indices && user_mean && T && P, "el_slope_scores: null pointer");
-    EL_REQUIRE(u_start >= 0 && u_stop >= u_start && u_stop - u_start < 0x7fffffffLL, "el_slope_scores: bad user range");
-    EL_REQUIRE(I >= 1 && I < 0x7fffffffLL && (I + SLOPE_SLAB - 1) / SLOPE_SLAB < 65536, "el_slope_scores: bad item count %lld",
-               (long long)I);
-    EL_REQUIRE(ldt >= I && ldp >= I, "el_slope_scores: leading dimensions below I");
-    if (u_stop == u_start) return 0;
-    EL_LAUNCH("k_slope_scores", k_slope_scores, dim3((unsigned)(u_stop - u_start), (unsigned)((I + SLOPE_SLAB - 1) / SLOPE_SLAB)),
-              dim3(256), 0, (hipStream_t)stream, indptr, indices, user_mean, u_start, T, ldt, I, P, ldp);
-    EL_CHECK_LAUNCH();
-    return 0;
+    return el_row_scores("el_slope_scores", "k_slope_scores", ctx, stream, indptr && indices && user_mean && T && P, indptr,
+                         indices, u_start, u_stop, SlopeScoreOp{{T, ldt}, user_mean}, I, P, ldp);
 }

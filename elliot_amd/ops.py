@@ -761,9 +761,57 @@ class AlsDeviceState:
 
 
 # ------------------------------------------------------------------------------------------
+# what the dense item-item models (EASE^R, SlopeOne, BPRSlim) share: the memory guard and the blocked recommend()
+# ------------------------------------------------------------------------------------------
+SCORE_BLOCK_BYTES = 1 << 28          # bound of one [Ub, I] score block
+EASE_SCORE_BLOCK_BYTES = SLOPE_SCORE_BLOCK_BYTES = BPRSLIM_SCORE_BLOCK_BYTES = SCORE_BLOCK_BYTES
+
+
+def score_block_rows(I, U, itemsize):
+    return min(max(SCORE_BLOCK_BYTES // (itemsize * max(int(I), 1)), 1), max(int(U), 1))
+
+
+class _DenseScoreState:
+    """A model that scores [Ub, I] blocks of SCORE_DTYPE (float32 | float64) with _score_block(s, e, out) and selects from them.
+    A subclass sets ctx, U and I, then calls _guard_memory() before it allocates anything."""
+    SCORE_DTYPE = torch.float64
+
+    def _guard_memory(self, need, what):
+        """ValueError naming the bytes when `need` exceeds the free device memory; what: the model's own sentence."""
+        self.need = need
+        free, _total = torch.cuda.mem_get_info(self.ctx.device)
+        if need > free:
+            raise ValueError(f"{what}; {free} bytes are free")
+        self.block_rows = score_block_rows(self.I, self.U, self.SCORE_DTYPE.itemsize)
+        self._S = None                            # the score block, allocated by the first recommend() from block_rows
+
+    def recommend(self, mask, k, start, stop):
+        """Top-k of users [start, stop) under the tagged mask ("excl" | "cand", DeviceCSR): (idx int32, val SCORE_DTYPE) [n, k]
+        on the device; lists short of k are padded with (-1, -inf)."""
+        ctx, dt = self.ctx, self.SCORE_DTYPE
+        kind, csr = mask if mask is not None else (None, None)
+        ep, ei = _csr_ptrs(csr if kind == "excl" else None)
+        cp, ci = _csr_ptrs(csr if kind == "cand" else None)
+        sfx = "" if dt == torch.float32 else "_f64"
+        topk, pad = getattr(ctx.lib, "el_dense_topk" + sfx), getattr(ctx.lib, "el_topk_pad" + sfx)
+        start, stop = int(start), int(stop)
+        n = stop - start
+        out_idx = torch.empty((n, k), dtype=torch.int32, device=ctx.device)
+        out_val = torch.empty((n, k), dtype=dt, device=ctx.device)
+        if self._S is None:
+            self._S = torch.empty((self.block_rows, self.I), dtype=dt, device=ctx.device)
+        for s in range(start, stop, self.block_rows):
+            e = min(s + self.block_rows, stop)
+            self._score_block(s, e, self._S)
+            check(topk(ctx.handle, ctx.stream(), _ptr(self._S, dt), int(self._S.stride(0)), s, e, int(self.I), ep, ei, cp,
+                       ci, int(k), _ptr(out_idx[s - start:], torch.int32), _ptr(out_val[s - start:], dt)), "el_dense_topk" + sfx)
+        check(pad(ctx.handle, ctx.stream(), _ptr(out_idx, torch.int32), _ptr(out_val, dt), int(n * k)), "el_topk_pad" + sfx)
+        return out_idx, out_val
+
+
+# ------------------------------------------------------------------------------------------
 # EASE^R (Gram, fp64 inverse, weights, CSR x dense scores)
 # ------------------------------------------------------------------------------------------
-EASE_SCORE_BLOCK_BYTES = 1 << 28     # bound of one [Ub, I] float32 score block
 
 
 def ease_integer_ratings(values):
@@ -845,7 +893,7 @@ def csr_dense_scores(ctx, R, R_vals, B, u_start, u_stop, out=None):
         raise ValueError("csr_dense_scores: the output block is smaller than [n, I]")
     check(ctx.lib.el_csr_dense_scores(ctx.handle, ctx.stream(), _ptr(R.indptr, torch.int64), _ptr(R.indices, torch.int32),
                                       _ptr(R_vals, torch.float32), int(u_start), int(u_stop),
-                                      _ptr(B, torch.float32, "B"), int(B.stride(0)), I, _ptr(out, torch.float32, "S"),
+                                      _rows_ptr(B, torch.float32, "B"), int(B.stride(0)), I, _rows_ptr(out, torch.float32, "S"),
                                       int(out.stride(0))), "el_csr_dense_scores")
     return out
 
@@ -854,16 +902,16 @@ def ease_memory_need(I, U):
     """Device bytes EaseDeviceState needs at its peak: G / P and the inverse's right-hand sides (8 I^2 each), B (4 I^2), one
     score block and the CSRs."""
     I, U = int(I), int(U)
-    block = min(max(EASE_SCORE_BLOCK_BYTES // (4 * max(I, 1)), 1), max(U, 1)) * 4 * I
-    return 8 * I * I + 8 * I * I + 4 * I * I + block
+    return 8 * I * I + 8 * I * I + 4 * I * I + score_block_rows(I, U, 4) * 4 * I
 
 
-class EaseDeviceState:
+class EaseDeviceState(_DenseScoreState):
     """R (float32 CSR, stored order) and B (float32 [I, I]) of EASE^R in HBM.
 
     build() forms G (el_ease_gram), P = G^-1 (el_inv_f64), B (el_ease_weights) and frees G / P; recommend() scores blocks of at
     most EASE_SCORE_BLOCK_BYTES with el_csr_dense_scores and selects with el_dense_topk; lists short of k are padded with
     (-1, -inf) (el_topk_pad).  The device memory is checked before anything is allocated."""
+    SCORE_DTYPE = torch.float32
 
     def __init__(self, ctx, R, l2_norm):
         import scipy.sparse as sp
@@ -871,18 +919,14 @@ class EaseDeviceState:
         R = sp.csr_matrix(R, dtype=np.float32)
         self.U, self.I = int(R.shape[0]), int(R.shape[1])
         self.l2_norm = float(l2_norm)
-        self.need = ease_memory_need(self.I, self.U)
-        free, _total = torch.cuda.mem_get_info(ctx.device)
-        if self.need > free:
-            raise ValueError(f"EASER: {self.I} items need {self.need} bytes of device memory (G / P and the inverse's right-hand "
-                             f"sides 2 x {8 * self.I * self.I}, B {4 * self.I * self.I}, one score block); {free} bytes are free")
+        need = ease_memory_need(self.I, self.U)
+        self._guard_memory(need, f"EASER: {self.I} items need {need} bytes of device memory (G / P and the inverse's right-hand "
+                                 f"sides 2 x {8 * self.I * self.I}, B {4 * self.I * self.I}, one score block)")
         ease_integer_ratings(R.data)
         self._host = R
         self.R = DeviceCSR(R.indptr, R.indices, self.I, ctx.device)
         self.R_vals = device_values(R.data, ctx.device)
         self.B = None
-        self.block_rows = min(max(EASE_SCORE_BLOCK_BYTES // (4 * max(self.I, 1)), 1), max(self.U, 1))
-        self._S = None
 
     def build(self):
         G = ease_gram(self.ctx, self._host, self.l2_norm)
@@ -898,32 +942,13 @@ class EaseDeviceState:
             raise ValueError(f"EASER weights have shape {B.shape}, the model expects {(self.I, self.I)}")
         self.B = torch.from_numpy(B).to(self.ctx.device)
 
-    def recommend(self, mask, k, start, stop):
-        """Top-k of users [start, stop) under the tagged mask ("excl" | "cand", DeviceCSR): (idx, val) [n, k] on the device."""
-        kind, csr = mask if mask is not None else (None, None)
-        ep, ei = _csr_ptrs(csr if kind == "excl" else None)
-        cp, ci = _csr_ptrs(csr if kind == "cand" else None)
-        n = int(stop) - int(start)
-        out_idx = torch.empty((n, k), dtype=torch.int32, device=self.ctx.device)
-        out_val = torch.empty((n, k), dtype=torch.float32, device=self.ctx.device)
-        if self._S is None:
-            self._S = torch.empty((self.block_rows, self.I), dtype=torch.float32, device=self.ctx.device)
-        for s in range(int(start), int(stop), self.block_rows):
-            e = min(s + self.block_rows, int(stop))
-            csr_dense_scores(self.ctx, self.R, self.R_vals, self.B, s, e, out=self._S)
-            r = s - int(start)
-            check(self.ctx.lib.el_dense_topk(self.ctx.handle, self.ctx.stream(), C.c_void_p(self._S.data_ptr()), int(self.I), s, e,
-                                             int(self.I), ep, ei, cp, ci, int(k), C.c_void_p(out_idx[r].data_ptr()),
-                                             C.c_void_p(out_val[r].data_ptr())), "el_dense_topk")
-        check(self.ctx.lib.el_topk_pad(self.ctx.handle, self.ctx.stream(), _ptr(out_idx, torch.int32), _ptr(out_val, torch.float32),
-                                       int(n * k)), "el_topk_pad")
-        return out_idx, out_val
+    def _score_block(self, s, e, out):
+        csr_dense_scores(self.ctx, self.R, self.R_vals, self.B, s, e, out=out)
 
 
 # ------------------------------------------------------------------------------------------
 # SlopeOne (exact deviation build, scoring table, ordered fp64 scoring)
 # ------------------------------------------------------------------------------------------
-SLOPE_SCORE_BLOCK_BYTES = 1 << 28    # bound of one [Ub, I] float64 score block
 SLOPE_TILE = 8192                    # LDS cells per pass of k_slope_build over the catalogue (el_slope.hip)
 
 
@@ -960,8 +985,8 @@ def slope_table(ctx, freq, dev, out=None):
     I = int(freq.shape[0])
     if out is None:
         out = torch.empty((I, I), dtype=torch.float64, device=ctx.device)
-    check(ctx.lib.el_slope_table(ctx.handle, ctx.stream(), _ptr(freq, torch.int32, "freq"), int(freq.stride(0)),
-                                 _ptr(dev, torch.float64, "dev"), int(dev.stride(0)), I, _ptr(out, torch.float64, "T"),
+    check(ctx.lib.el_slope_table(ctx.handle, ctx.stream(), _rows_ptr(freq, torch.int32, "freq"), int(freq.stride(0)),
+                                 _rows_ptr(dev, torch.float64, "dev"), int(dev.stride(0)), I, _rows_ptr(out, torch.float64, "T"),
                                  int(out.stride(0))), "el_slope_table")
     return out
 
@@ -976,7 +1001,7 @@ def slope_scores(ctx, rows, user_mean, T, u_start, u_stop, out=None):
         raise ValueError("slope_scores: the output block is smaller than [n, I]")
     check(ctx.lib.el_slope_scores(ctx.handle, ctx.stream(), _ptr(rows.indptr, torch.int64), _ptr(rows.indices, torch.int32),
                                   _ptr(user_mean, torch.float64, "user_mean"), int(u_start), int(u_stop),
-                                  _ptr(T, torch.float64, "T"), int(T.stride(0)), I, _ptr(out, torch.float64, "P"),
+                                  _rows_ptr(T, torch.float64, "T"), int(T.stride(0)), I, _rows_ptr(out, torch.float64, "P"),
                                   int(out.stride(0))), "el_slope_scores")
     return out
 
@@ -1015,7 +1040,7 @@ def slope_user_mean(indptr, ratings):
 
 
 def slope_block_rows(I, U):
-    return min(max(SLOPE_SCORE_BLOCK_BYTES // (8 * max(int(I), 1)), 1), max(int(U), 1))
+    return score_block_rows(I, U, 8)
 
 
 def slope_memory_need(I, U):
@@ -1024,7 +1049,7 @@ def slope_memory_need(I, U):
     return 4 * I * I + 8 * I * I + 8 * I * I + slope_block_rows(I, U) * 8 * I
 
 
-class SlopeDeviceState:
+class SlopeDeviceState(_DenseScoreState):
     """The train matrix in dict order (DeviceCSR), user_mean, freq (int32), dev and the scoring table T (float64 [I, I]) of
     SlopeOne in HBM.
 
@@ -1040,11 +1065,9 @@ class SlopeDeviceState:
         self.ctx = ctx
         R = sp.csr_matrix(R, dtype=np.float64)
         self.U, self.I = int(R.shape[0]), int(R.shape[1])
-        self.need = slope_memory_need(self.I, self.U)
-        free, _total = torch.cuda.mem_get_info(ctx.device)
-        if self.need > free:
-            raise ValueError(f"SlopeOne: {self.I} items need {self.need} bytes of device memory (freq {4 * self.I * self.I}, dev "
-                             f"and the scoring table 2 x {8 * self.I * self.I}, one score block); {free} bytes are free")
+        need = slope_memory_need(self.I, self.U)
+        self._guard_memory(need, f"SlopeOne: {self.I} items need {need} bytes of device memory (freq {4 * self.I * self.I}, dev "
+                                 f"and the scoring table 2 x {8 * self.I * self.I}, one score block)")
         slope_integer_ratings(R.data)
         indptr, indices = rows
         indptr = np.asarray(indptr, dtype=np.int64)
@@ -1057,8 +1080,6 @@ class SlopeDeviceState:
         self.user_mean_host = slope_user_mean(indptr, ratings)
         self.user_mean = torch.from_numpy(self.user_mean_host).to(ctx.device)
         self.freq = self.dev = self.T = None
-        self.block_rows = slope_block_rows(self.I, self.U)
-        self._P = None
 
     def build(self):
         self.freq, self.dev, self.T = slope_build(self.ctx, self._host)
@@ -1077,50 +1098,37 @@ class SlopeDeviceState:
         self.T = slope_table(self.ctx, self.freq, self.dev)
 
     def recommend(self, mask, k, start, stop):
-        """Top-k of users [start, stop) under the tagged mask ("excl" | "cand", DeviceCSR): (idx int32, val float64) [n, k] on
-        the device."""
         if self.T is None:
             raise _lib.ElliotHipError("SlopeOne: recommend() before build() or set_model()")
-        kind, csr = mask if mask is not None else (None, None)
-        excl, cand = (csr if kind == "excl" else None), (csr if kind == "cand" else None)
-        n = int(stop) - int(start)
-        out_idx = torch.empty((n, k), dtype=torch.int32, device=self.ctx.device)
-        out_val = torch.empty((n, k), dtype=torch.float64, device=self.ctx.device)
-        if self._P is None:
-            self._P = torch.empty((self.block_rows, self.I), dtype=torch.float64, device=self.ctx.device)
-        for s in range(int(start), int(stop), self.block_rows):
-            e = min(s + self.block_rows, int(stop))
-            slope_scores(self.ctx, self.rows, self.user_mean, self.T, s, e, out=self._P)
-            r = s - int(start)
-            dense_topk_f64(self.ctx, self._P, s, e, k, excl=excl, cand=cand, out_idx=out_idx[r:r + e - s],
-                           out_val=out_val[r:r + e - s])
-        check(self.ctx.lib.el_topk_pad_f64(self.ctx.handle, self.ctx.stream(), _ptr(out_idx, torch.int32),
-                                           _ptr(out_val, torch.float64), int(n * k)), "el_topk_pad_f64")
-        return out_idx, out_val
+        return super().recommend(mask, k, start, stop)
+
+    def _score_block(self, s, e, out):
+        slope_scores(self.ctx, self.rows, self.user_mean, self.T, s, e, out=out)
 
 
 # ------------------------------------------------------------------------------------------
 # BPRSlim (per-triplet BPR SGD on a dense fp64 item-item matrix, ordered fp64 scoring)
 # ------------------------------------------------------------------------------------------
-BPRSLIM_SCORE_BLOCK_BYTES = 1 << 28  # bound of one [Ub, I] float64 score block
+def _levels_host(fn, ids, sizes):
+    """(order int32 [n], level_start int64 [n_levels + 1]) from one of the el_*_levels_host entry points: the id arrays (int32,
+    contiguous, of one length), n, the table sizes, then the outputs."""
+    n = ids[0].shape[0]
+    order = np.empty(n, dtype=np.int32)
+    starts = np.empty(n + 2, dtype=np.int64)
+    nl = C.c_int64()
+    check(getattr(_lib.load(), fn)(*(a.ctypes.data_as(C.c_void_p) for a in ids), n, *(int(x) for x in sizes),
+                                   order.ctypes.data_as(C.c_void_p), starts.ctypes.data_as(C.c_void_p), n + 2, C.byref(nl)), fn)
+    return order, starts[: nl.value + 1].copy()
 
 
 def bprslim_levels(i_host, j_host, I):
     """Host-only: (order int32 [n], level_start int64 [n_levels + 1]) of a BPRSlim triplet sequence (el_bprslim_levels_host).
     A triplet depends on the last earlier one that shares row i or row j of S; the user is no dependency."""
-    lib = _lib.load()
     i = np.ascontiguousarray(i_host, dtype=np.int32).reshape(-1)
     j = np.ascontiguousarray(j_host, dtype=np.int32).reshape(-1)
     if i.shape != j.shape:
         raise ValueError("bprslim_levels: i and j differ in length")
-    n = i.shape[0]
-    order = np.empty(n, dtype=np.int32)
-    starts = np.empty(n + 2, dtype=np.int64)
-    nl = C.c_int64()
-    check(lib.el_bprslim_levels_host(i.ctypes.data_as(C.c_void_p), j.ctypes.data_as(C.c_void_p), n, int(I),
-                                     order.ctypes.data_as(C.c_void_p), starts.ctypes.data_as(C.c_void_p), n + 2, C.byref(nl)),
-          "el_bprslim_levels_host")
-    return order, starts[: nl.value + 1].copy()
+    return _levels_host("el_bprslim_levels_host", (i, j), (I,))
 
 
 def _bprslim_matrix(S, I, name):
@@ -1188,7 +1196,7 @@ def bprslim_scores(ctx, rows, St, u_start, u_stop, out=None, I=None):
 
 
 def bprslim_block_rows(I, U):
-    return min(max(BPRSLIM_SCORE_BLOCK_BYTES // (8 * max(int(I), 1)), 1), max(int(U), 1))
+    return score_block_rows(I, U, 8)
 
 
 def bprslim_memory_need(I, U):
@@ -1197,7 +1205,7 @@ def bprslim_memory_need(I, U):
     return 8 * I * I + 8 * I * I + bprslim_block_rows(I, U) * 8 * I
 
 
-class BprSlimDeviceState:
+class BprSlimDeviceState(_DenseScoreState):
     """The train matrix (DeviceCSR, rows in the order the reference's scipy matrix stores them: ascending item id), the dense
     item-item matrix S and its transposed scoring table St (float64 [I, I]) of BPRSlim in HBM.
 
@@ -1211,11 +1219,9 @@ class BprSlimDeviceState:
         import scipy.sparse as sp
         self.ctx = ctx
         self.U, self.I = int(R.shape[0]), int(R.shape[1])
-        self.need = bprslim_memory_need(self.I, self.U)
-        free, _total = torch.cuda.mem_get_info(ctx.device)
-        if self.need > free:
-            raise ValueError(f"BPRSlim: {self.I} items need {self.need} bytes of device memory (S and the scoring table 2 x "
-                             f"{8 * self.I * self.I}, one score block); {free} bytes are free")
+        need = bprslim_memory_need(self.I, self.U)
+        self._guard_memory(need, f"BPRSlim: {self.I} items need {need} bytes of device memory (S and the scoring table 2 x "
+                                 f"{8 * self.I * self.I}, one score block)")
         R = sp.csr_matrix(R)
         if not R.has_canonical_format:
             R = R.copy()
@@ -1224,8 +1230,6 @@ class BprSlimDeviceState:
         self.rows = DeviceCSR(np.asarray(R.indptr, dtype=np.int64), R.indices, self.I, ctx.device)
         self.S = torch.zeros((self.I, self.I), dtype=torch.float64, device=ctx.device)
         self.St = None                                # rebuilt from S by the first recommend() after S has moved
-        self.block_rows = bprslim_block_rows(self.I, self.U)
-        self._P = None
 
     def apply_sequential_equivalent(self, u_host, i_host, j_host):
         """The sequential order of BPRSlimModel.train_step on these triplets: (n_levels, x) with x the float64 host array of
@@ -1253,27 +1257,10 @@ class BprSlimDeviceState:
         self.S.copy_(torch.from_numpy(S))
         self.St = None
 
-    def recommend(self, mask, k, start, stop):
-        """Top-k of users [start, stop) under the tagged mask ("excl" | "cand", DeviceCSR): (idx int32, val float64) [n, k] on
-        the device."""
+    def _score_block(self, s, e, out):
         if self.St is None:
             self.St = bprslim_table(self.ctx, self.S)
-        kind, csr = mask if mask is not None else (None, None)
-        excl, cand = (csr if kind == "excl" else None), (csr if kind == "cand" else None)
-        n = int(stop) - int(start)
-        out_idx = torch.empty((n, k), dtype=torch.int32, device=self.ctx.device)
-        out_val = torch.empty((n, k), dtype=torch.float64, device=self.ctx.device)
-        if self._P is None:
-            self._P = torch.empty((self.block_rows, self.I), dtype=torch.float64, device=self.ctx.device)
-        for s in range(int(start), int(stop), self.block_rows):
-            e = min(s + self.block_rows, int(stop))
-            bprslim_scores(self.ctx, self.rows, self.St, s, e, out=self._P)
-            r = s - int(start)
-            dense_topk_f64(self.ctx, self._P, s, e, k, excl=excl, cand=cand, out_idx=out_idx[r:r + e - s],
-                           out_val=out_val[r:r + e - s])
-        check(self.ctx.lib.el_topk_pad_f64(self.ctx.handle, self.ctx.stream(), _ptr(out_idx, torch.int32),
-                                           _ptr(out_val, torch.float64), int(n * k)), "el_topk_pad_f64")
-        return out_idx, out_val
+        bprslim_scores(self.ctx, self.rows, self.St, s, e, out=out)
 
 
 # ------------------------------------------------------------------------------------------
@@ -2642,19 +2629,8 @@ class Mf2020DeviceState:
 
 def sgd_levels(u_host, i_host, j_host, U, I):
     """Host-only: dependency levels of a triplet sequence (el_bprsgd_levels_host)."""
-    lib = _lib.load()
-    u = np.ascontiguousarray(u_host, dtype=np.int32)
-    i = np.ascontiguousarray(i_host, dtype=np.int32)
-    j = np.ascontiguousarray(j_host, dtype=np.int32)
-    n = u.shape[0]
-    order = np.empty(n, dtype=np.int32)
-    starts = np.empty(n + 2, dtype=np.int64)
-    nl = C.c_int64()
-    check(lib.el_bprsgd_levels_host(u.ctypes.data_as(C.c_void_p), i.ctypes.data_as(C.c_void_p),
-                                    j.ctypes.data_as(C.c_void_p), n, int(U), int(I),
-                                    order.ctypes.data_as(C.c_void_p), starts.ctypes.data_as(C.c_void_p),
-                                    n + 2, C.byref(nl)), "el_bprsgd_levels_host")
-    return order, starts[: nl.value + 1].copy()
+    return _levels_host("el_bprsgd_levels_host", [np.ascontiguousarray(a, dtype=np.int32) for a in (u_host, i_host, j_host)],
+                        (U, I))
 
 
 # ------------------------------------------------------------------------------------------
