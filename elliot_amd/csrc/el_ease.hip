@@ -259,35 +259,7 @@ struct EaseScoreOp : RowScoreOp<float> {
     __device__ void step(float& a, float w, float x) const { a = __fadd_rn(a, __fmul_rn(w, x)); }
 };
 
-// el_dense_topk fills a short list with masked items at -inf; EASER pads with (-1, -inf) instead (the KNN and ALS convention)
-__global__ void k_topk_pad(int32_t* __restrict__ idx, const float* __restrict__ val, int64_t n) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e < n && val[e] == -INFINITY) idx[e] = -1;
-}
-__global__ void k_topk_pad_f64(int32_t* __restrict__ idx, const double* __restrict__ val, int64_t n) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e < n && val[e] == -(double)INFINITY) idx[e] = -1;
-}
-
 }  // namespace
-
-extern "C" int el_topk_pad(el_ctx* ctx, void* stream, int32_t* idx, const float* val, int64_t n) {
-    if (int rc = el_bind(ctx)) return rc;
-    EL_REQUIRE(n >= 0 && (n == 0 || (idx && val)), "el_topk_pad: bad arguments");
-    if (n == 0) return 0;
-    EL_LAUNCH("k_topk_pad", k_topk_pad, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, idx, val, n);
-    EL_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int el_topk_pad_f64(el_ctx* ctx, void* stream, int32_t* idx, const double* val, int64_t n) {
-    if (int rc = el_bind(ctx)) return rc;
-    EL_REQUIRE(n >= 0 && (n == 0 || (idx && val)), "el_topk_pad_f64: bad arguments");
-    if (n == 0) return 0;
-    EL_LAUNCH("k_topk_pad_f64", k_topk_pad_f64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, idx, val, n);
-    EL_CHECK_LAUNCH();
-    return 0;
-}
 
 extern "C" int el_ease_gram(el_ctx* ctx, void* stream, const int64_t* t_indptr, const int32_t* t_indices, const int32_t* t_vals,
                             const int64_t* r_indptr, const int32_t* r_indices, const int32_t* r_vals, int64_t I, int64_t U,

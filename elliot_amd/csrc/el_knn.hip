@@ -237,8 +237,7 @@ struct KnnScore {
 __global__ __launch_bounds__(64) void k_knn_score(KnnScore p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     u64* keys = reinterpret_cast<u64*>(smem);                                  // [cap]
-    int* cnt_s = reinterpret_cast<int*>(smem + (size_t)p.cap * 8);             // [1] (+pad)
-    float* acc = reinterpret_cast<float*>(smem + (size_t)p.cap * 8 + 16);      // [tile]
+    float* acc = reinterpret_cast<float*>(smem + (size_t)p.cap * 8);           // [tile]
     const int lane = threadIdx.x;
     const int64_t urel = blockIdx.x;
     const int64_t u = p.u_start + urel;
@@ -253,7 +252,7 @@ __global__ __launch_bounds__(64) void k_knn_score(KnnScore p) {
         e1 = p.excl_indptr[u + 1];
     }
     const bool tiled = p.tile < p.I;
-    ElWaveSelect sel(keys, cnt_s, p.cap, p.k);
+    ElWaveSelect<ElPackedKey> sel(keys, p.cap, p.k);
     for (int64_t i0 = 0; i0 < p.I; i0 += p.tile) {
         const int64_t i1 = (i0 + p.tile < p.I) ? i0 + p.tile : p.I;
         const int w = (int)(i1 - i0);
@@ -426,7 +425,7 @@ extern "C" int el_knn_score_topk(el_ctx* ctx, void* stream, const int64_t* a_ind
     const int64_t max_tile = KNN_TILE_BYTES / 4;
     p.tile = (int)(I < max_tile ? ((I + 63) / 64) * 64 : max_tile);
     p.out_idx = out_idx, p.out_val = out_val;
-    const size_t lds = (size_t)p.cap * 8 + 16 + (size_t)p.tile * 4;
+    const size_t lds = (size_t)p.cap * 8 + (size_t)p.tile * 4;
     EL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_knn_score), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     EL_LAUNCH("k_knn_score", k_knn_score, dim3((unsigned)(u_stop - u_start)), dim3(64), lds, (hipStream_t)stream, p);
     EL_CHECK_LAUNCH();

@@ -42,44 +42,9 @@ __global__ __launch_bounds__(256) void k_rp3_row_l1(const int64_t* __restrict__ 
     for (int64_t e = e0; e < e1; ++e) y[e] = (float)__ddiv_rn((double)x[e], s);
 }
 
-// (key, index) pairs: larger key first, then smaller index.  Key 0 with index 0x7fffffff is the empty slot (ord(double) of a
-// value that is not a negative NaN is never 0).
-__device__ __forceinline__ bool rp3_before(u64 ka, int32_t xa, u64 kb, int32_t xb) { return ka > kb || (ka == kb && xa < xb); }
-
-// one-wave bitonic sort of n = 2^m pairs in LDS, best first
-__device__ __forceinline__ void rp3_wave_bitonic(u64* k, int32_t* x, int n, int lane) {
-    for (int size = 2; size <= n; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = lane; t < (n >> 1); t += 64) {
-                const int i = 2 * t - (t & (stride - 1));
-                const int j = i + stride;
-                const bool desc = ((i & size) == 0);
-                const u64 ka = k[i], kb = k[j];
-                const int32_t xa = x[i], xb = x[j];
-                const bool sw = desc ? rp3_before(kb, xb, ka, xa) : rp3_before(ka, xa, kb, xb);
-                if (sw) {
-                    k[i] = kb, k[j] = ka;
-                    x[i] = xb, x[j] = xa;
-                }
-            }
-            el_wave_lds_sync();
-        }
-    }
-}
-
-// keep the best N of the cnt pairs in a cap-slot buffer (wave-uniform arguments); returns the key of the N-th (0: fewer than N)
-__device__ __forceinline__ u64 rp3_wave_compact(u64* k, int32_t* x, int cnt, int cap, int N, int lane) {
-    el_wave_lds_sync();
-    for (int t = cnt + lane; t < cap; t += 64) {
-        k[t] = 0ull;
-        x[t] = 0x7fffffff;
-    }
-    el_wave_lds_sync();
-    rp3_wave_bitonic(k, x, cap, lane);
-    const u64 tau = cnt >= N ? k[N - 1] : 0ull;
-    el_wave_lds_sync();
-    return tau;
-}
+// The row cut's running selection: ord(double) keys with the column beside them, larger key first, then smaller column
+// (a key of a value that is not a negative NaN is never 0, the empty slot's).
+typedef ElWaveSelect<ElPairKey<u64>> Rp3Select;
 
 struct Rp3Rows {
     const int64_t* pp;   // Piu: item -> its users ascending
@@ -106,9 +71,7 @@ struct Rp3Rows {
 // accesses are served in program order, so every column sees its terms in user order.
 __global__ __launch_bounds__(64) void k_rp3_slice(Rp3Rows p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    u64* keys = reinterpret_cast<u64*>(smem);                                          // [cap]
-    float* acc = reinterpret_cast<float*>(smem + (size_t)p.cap * 8);                   // [width]
-    int32_t* kx = reinterpret_cast<int32_t*>(smem + (size_t)p.cap * 8 + (size_t)p.width * 4);   // [cap]
+    float* acc = reinterpret_cast<float*>(smem + (size_t)p.cap * 12);                  // [width], behind the selection's [cap] pairs
     const int lane = threadIdx.x;
     const int64_t rrel = blockIdx.x;
     const int64_t i = p.i_start + rrel;
@@ -160,8 +123,8 @@ __global__ __launch_bounds__(64) void k_rp3_slice(Rp3Rows p) {
         }
     }
     // the slice's N best non-zeros of v = (double)S * degree, and how many non-zeros / positives it holds
-    int cnt = 0, n_nz = 0, n_pos = 0;
-    u64 tau = 0ull;
+    int n_nz = 0, n_pos = 0;
+    Rp3Select sel(ElPairKey<u64>(smem, p.cap), p.cap, p.N);
     for (int base = 0; base < w; base += 64) {
         const int pos = base + lane;
         bool nz = false, hit = false;
@@ -173,31 +136,18 @@ __global__ __launch_bounds__(64) void k_rp3_slice(Rp3Rows p) {
                 v = __dmul_rn((double)sv, p.deg[c0 + pos]);
                 nz = v != 0.0;
                 key = el_d2ord(v);
-                hit = nz && key >= tau;
+                hit = nz && key >= sel.tau;
             }
         }
         n_nz += __popcll(__ballot(nz));
         n_pos += __popcll(__ballot(nz && v > 0.0));
-        const u64 bal = __ballot(hit);
-        if (bal) {
-            const int offp = __popcll(bal & ((1ull << lane) - 1ull));
-            if (hit) {
-                keys[cnt + offp] = key;
-                kx[cnt + offp] = (int32_t)(c0 + pos);
-            }
-            cnt += __popcll(bal);
-        }
-        if (cnt > p.cap - 64) {
-            tau = rp3_wave_compact(keys, kx, cnt, p.cap, p.N, lane);
-            cnt = cnt < p.N ? cnt : p.N;
-        }
+        sel.push(hit, key, (int32_t)(c0 + pos), lane);
     }
-    rp3_wave_compact(keys, kx, cnt, p.cap, p.N, lane);
-    const int m = cnt < p.N ? cnt : p.N;
+    const int m = sel.finish(lane);
     const int64_t slot = rrel * p.S + s;
     for (int t = lane; t < m; t += 64) {
-        p.sk[slot * p.N + t] = keys[t];
-        p.sx[slot * p.N + t] = kx[t];
+        p.sk[slot * p.N + t] = sel.keys.value(t);
+        p.sx[slot * p.N + t] = sel.keys.index(t);
     }
     if (lane == 0) {
         p.sc[slot * 4 + 0] = m;
@@ -211,32 +161,22 @@ __global__ __launch_bounds__(64) void k_rp3_slice(Rp3Rows p) {
 // then negatives: with P positives and Z zeros the row keeps min(N, P) positives and max(0, N - P - Z) negatives.
 __global__ __launch_bounds__(64) void k_rp3_merge(Rp3Rows p, int32_t* __restrict__ lx, float* __restrict__ lv, int32_t* __restrict__ lcnt) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    u64* keys = reinterpret_cast<u64*>(smem);                                          // [cap]
-    int32_t* kx = reinterpret_cast<int32_t*>(smem + (size_t)p.cap * 8);                // [cap]
     const int lane = threadIdx.x;
     const int64_t rrel = blockIdx.x;
-    int cnt = 0;
+    Rp3Select sel(ElPairKey<u64>(smem, p.cap), p.cap, p.N);
     int64_t n_nz = 0, n_pos = 0;
     for (int s = 0; s < p.S; ++s) {
         const int64_t slot = rrel * p.S + s;
         const int m = p.sc[slot * 4 + 0];
         n_nz += p.sc[slot * 4 + 1];
         n_pos += p.sc[slot * 4 + 2];
-        for (int base = 0; base < m; base += 64) {
+        for (int base = 0; base < m; base += 64) {             // the lanes that hold an entry are a prefix of the wave
             const int t = base + lane;
-            if (t < m) {
-                keys[cnt + t - base] = p.sk[slot * p.N + t];
-                kx[cnt + t - base] = p.sx[slot * p.N + t];
-            }
-            cnt += m - base < 64 ? m - base : 64;
-            if (cnt > p.cap - 64) {
-                rp3_wave_compact(keys, kx, cnt, p.cap, p.N, lane);
-                cnt = cnt < p.N ? cnt : p.N;
-            }
+            const bool has = t < m;
+            sel.push(has, has ? p.sk[slot * p.N + t] : 0ull, has ? p.sx[slot * p.N + t] : 0, lane);
         }
     }
-    rp3_wave_compact(keys, kx, cnt, p.cap, p.N, lane);
-    const int m = cnt < p.N ? cnt : p.N;                       // the N best non-zeros: positives first
+    const int m = sel.finish(lane);                            // the N best non-zeros: positives first
     const int64_t zeros = p.I - n_nz;
     const int take_pos = (int)(n_pos < p.N ? n_pos : p.N);
     int64_t take_neg = n_pos < p.N ? (int64_t)p.N - n_pos - zeros : 0;
@@ -244,8 +184,8 @@ __global__ __launch_bounds__(64) void k_rp3_merge(Rp3Rows p, int32_t* __restrict
     if (take_neg > m - take_pos) take_neg = m - take_pos;
     const int out = take_pos + (int)take_neg;
     for (int t = lane; t < out; t += 64) {
-        lx[rrel * p.N + t] = kx[t];
-        lv[rrel * p.N + t] = (float)el_ord2d(keys[t]);
+        lx[rrel * p.N + t] = sel.keys.index(t);
+        lv[rrel * p.N + t] = (float)el_ord2d(sel.keys.value(t));
     }
     if (lane == 0) lcnt[rrel] = out;
 }
@@ -285,11 +225,10 @@ __global__ __launch_bounds__(64) void k_rp3_coltop(const int64_t* __restrict__ c
                                                    float* __restrict__ cv, int32_t* __restrict__ ccnt, int32_t* __restrict__ rowcnt) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     u64* keys = reinterpret_cast<u64*>(smem);                                          // [cap]
-    int* cnt_s = reinterpret_cast<int*>(smem + (size_t)cap * 8);
     const int lane = threadIdx.x;
     const int64_t j = blockIdx.x;
     const int64_t e0 = colptr[j], e1 = colptr[j + 1];
-    ElWaveSelect sel(keys, cnt_s, cap, N);
+    ElWaveSelect<ElPackedKey> sel(keys, cap, N);
     for (int64_t base = e0; base < e1; base += 64) {
         const int64_t e = base + lane;
         bool hit = false;
@@ -457,8 +396,8 @@ extern "C" int el_rp3_cut(el_ctx* ctx, void* stream, const int32_t* list_idx, co
     EL_LAUNCH("k_knn_place", k_knn_place, dim3(eblocks), dim3(256), 0, st, list_idx, lv, list_cnt, I, N, w.b.cursor, w.b.tc, w.b.tv);
     EL_CHECK_LAUNCH();
     EL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rp3_coltop), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)((size_t)cap * 8 + 16)));
-    EL_LAUNCH("k_rp3_coltop", k_rp3_coltop, dim3((unsigned)I), dim3(64), (size_t)cap * 8 + 16, st, (const int64_t*)w.colptr,
+                                     (int)((size_t)cap * 8)));
+    EL_LAUNCH("k_rp3_coltop", k_rp3_coltop, dim3((unsigned)I), dim3(64), (size_t)cap * 8, st, (const int64_t*)w.colptr,
               (const int32_t*)w.b.tc, (const float*)w.b.tv, N, cap, w.cx, w.cv, w.ccnt, w.rowcnt);
     EL_CHECK_LAUNCH();
     // the per-column lists to W's rows, columns ascending (the buckets are free again)

@@ -122,7 +122,6 @@ __global__ __launch_bounds__(64) void k_slim_fit(SlimFit p) {
         r = p.gr + t * U;
         keys = reinterpret_cast<u64*>(smem);
     }
-    int* cnt_s = reinterpret_cast<int*>(keys + p.cap);
     const int64_t* __restrict__ cp = p.cp;
     const int32_t* __restrict__ ci = p.ci;
     const float* __restrict__ cv = p.cv;
@@ -277,7 +276,7 @@ __global__ __launch_bounds__(64) void k_slim_fit(SlimFit p) {
         return;
     }
     slim_sync<LDS>();
-    ElWaveSelect sel(keys, cnt_s, p.cap, K);
+    ElWaveSelect<ElPackedKey> sel(keys, p.cap, K);
     for (int64_t base = 0; base < I; base += 64) {
         const int64_t i = base + lane;
         float v = 0.f;
@@ -306,7 +305,7 @@ __global__ __launch_bounds__(64) void k_slim_norm_ref(const int64_t* __restrict_
     norm[t * I + c] = s;
 }
 
-size_t slim_cut_lds(int N) { return (size_t)el_select_cap(N) * 8 + 16; }
+size_t slim_cut_lds(int N) { return ElPackedKey::lds_bytes(el_select_cap(N)); }
 
 size_t slim_w_bytes(int64_t I) { return ((size_t)I * 4 + 15) & ~(size_t)15; }
 

@@ -13,6 +13,7 @@
 // The [users, items] score matrix is never written to HBM: selection is fused behind the
 // MFMA accumulators (threshold filter in registers, candidate lists in LDS).
 #include <stdlib.h>
+#include <type_traits>
 #include "el_common.h"
 
 #include "el_topk_common.h"
@@ -21,14 +22,22 @@
 // Wave-per-user kernel (VALU fma chain).  General k, general F, candidate protocol,
 // dense-preds source.  Also the cross-check for the MFMA kernel (bitwise-equal scores).
 // =====================================================================================
-template <bool DENSE>
-__global__ __launch_bounds__(64) void k_topk_wave(TopkParams p, int cap) {
+__device__ __forceinline__ float el_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double el_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+// T = float: packed keys; T = double (BPRMF NumPy model, KaHFM, SlopeOne, BPRSlim): (ord64(score), ~item) pairs.
+// The user list and the item split are fp32 routes.
+template <class T>
+using TopkKey = typename std::conditional<sizeof(T) == 4, ElPackedKey, ElPairKey<double>>::type;
+
+template <class T, bool DENSE>
+__global__ __launch_bounds__(64) void k_topk_wave(TopkParamsT<T> p, int cap) {
+    typedef TopkKey<T> Key;
+    constexpr bool F32 = sizeof(T) == 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    u64* keys = reinterpret_cast<u64*>(smem);              // [cap]
-    int* cnt_s = reinterpret_cast<int*>(smem + (size_t)cap * 8);  // [1] (+pad), used by el_wave_compact
     const int lane = threadIdx.x;
     int64_t urel = blockIdx.x;                             // row of out_idx / out_val
-    if (p.ulist) {                                         // (dense rows stay indexed by blockIdx.x)
+    if (F32 && p.ulist) {                                  // (dense rows stay indexed by blockIdx.x)
         int64_t n = (int64_t)*p.ulist_n;
         if (p.ulist_max > 0 && n > p.ulist_max) n = p.ulist_max;
         if ((int64_t)blockIdx.x + p.ulist_skip >= n) return;
@@ -36,7 +45,7 @@ __global__ __launch_bounds__(64) void k_topk_wave(TopkParams p, int cap) {
     }
     const int64_t user = p.u_start + urel;
     const int F = p.F;
-    const float* gu = DENSE ? nullptr : p.Gu + user * (int64_t)F;
+    const T* gu = DENSE ? nullptr : p.Gu + user * (int64_t)F;
     int64_t e0 = 0, e1 = 0, c0 = 0, c1 = 0;
     if (p.excl_indptr) {
         e0 = p.excl_indptr[user];
@@ -51,13 +60,12 @@ __global__ __launch_bounds__(64) void k_topk_wave(TopkParams p, int cap) {
     const bool use_excl = (p.excl_indptr != nullptr) && (p.cand_indptr == nullptr);
     // item-split mode (gridDim.y = nsplit, full-catalogue scan only): this wave takes one slice, writes a partial list
     int64_t pos_lo = 0, pos_hi = ncand;
-    const bool split = p.nsplit > 1 && !p.cand_indptr;
+    const bool split = F32 && p.nsplit > 1 && !p.cand_indptr;
     if (split) {
         pos_lo = ncand * blockIdx.y / p.nsplit;
         pos_hi = ncand * (blockIdx.y + 1) / p.nsplit;
     }
-    int cnt = 0;
-    float tau = -INFINITY;
+    ElWaveSelect<Key> sel(Key(smem, cap), cap, p.k);
     for (int64_t base = pos_lo; base < pos_hi; base += 64) {
         int64_t pos = base + lane;
         bool valid = pos < pos_hi;
@@ -73,42 +81,29 @@ __global__ __launch_bounds__(64) void k_topk_wave(TopkParams p, int cap) {
                 gitem = (int32_t)(p.item_offset + pos);
             }
         }
-        float s = 0.f;
+        T s = 0;
         if (valid) {
             if (DENSE) {
-                s = p.preds[(int64_t)blockIdx.x * p.ld + il] + 0.0f;
+                s = p.preds[(int64_t)blockIdx.x * p.ld + il] + T(0);
             } else {
-                const float* gi = p.Gi + il * (int64_t)F;
-                float acc = 0.f;
-                for (int f = 0; f < F; ++f) acc = __builtin_fmaf(gi[f], gu[f], acc);
-                s = (p.Bi ? acc + p.Bi[il] : acc) + 0.0f;
+                const T* gi = p.Gi + il * (int64_t)F;
+                T acc = 0;
+                for (int f = 0; f < F; ++f) acc = el_fma(gi[f], gu[f], acc);
+                s = (p.Bi ? acc + p.Bi[il] : acc) + T(0);
             }
         }
-        bool hit = valid && (s >= tau);
+        bool hit = valid && (s >= sel.tau);
         if (hit && use_excl) hit = !el_row_contains(p.excl_indices, e0, e1, gitem);
-        u64 bal = __ballot(hit);
-        if (bal) {
-            int offp = __popcll(bal & ((1ull << lane) - 1ull));
-            if (hit) keys[cnt + offp] = el_make_key(s, gitem);
-            cnt += __popcll(bal);
-        }
-        if (cnt > cap - 64) {
-            if (lane == 0) *cnt_s = cnt;
-            tau = el_wave_compact(keys, cnt_s, cap, p.k, lane);
-            cnt = cnt < p.k ? cnt : p.k;
-        }
+        sel.push(hit, s, gitem, lane);
     }
-    if (lane == 0) *cnt_s = cnt;
-    el_wave_compact(keys, cnt_s, cap, p.k, lane);
-    const int nv = cnt < p.k ? cnt : p.k;
+    const int nv = sel.finish(lane);
     const int64_t orow = split ? ((int64_t)blockIdx.y * p.part_stride + blockIdx.x) * p.k : urel * p.k;
     for (int t = lane; t < p.k; t += 64) {
         int32_t oi;
-        float ov;
+        T ov;
         if (t < nv) {
-            u64 key = keys[t];
-            oi = el_key_item(key);
-            ov = el_key_score(key);
+            oi = sel.keys.index(t);
+            ov = sel.keys.value(t);
         } else {
             oi = split ? el_fill_masked_range(p, p.item_offset + pos_lo, p.item_offset + pos_hi, e0, e1, c0, c1, t - nv)
                        : el_fill_masked(p, e0, e1, c0, c1, t - nv);
@@ -117,6 +112,14 @@ __global__ __launch_bounds__(64) void k_topk_wave(TopkParams p, int cap) {
         p.out_idx[orow + t] = oi;
         p.out_val[orow + t] = ov;
     }
+}
+
+// el_dense_topk fills a short list with masked items at -inf; EASER, SlopeOne and BPRSlim pad with (-1, -inf) instead (the KNN
+// and ALS convention)
+template <class T>
+__global__ void k_topk_pad(int32_t* __restrict__ idx, const T* __restrict__ val, int64_t n) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < n && val[e] == -(T)INFINITY) idx[e] = -1;
 }
 
 // =====================================================================================
@@ -412,152 +415,6 @@ __global__ __launch_bounds__(64) void k_topk_merge(const int32_t* parts_idx, con
 }
 
 // =====================================================================================
-// fp64 variant (BPRMF NumPy model): wave-per-user, (ord64(score), ~item) pairs
-// =====================================================================================
-struct TopkParams64 {
-    const double* P;
-    const double* Q;
-    const double* b;
-    int64_t u_start, u_stop, item_offset, I_local;
-    int F;
-    const int64_t* excl_indptr;
-    const int32_t* excl_indices;
-    const int64_t* cand_indptr;
-    const int32_t* cand_indices;
-    int k;
-    int32_t* out_idx;
-    double* out_val;
-    // dense-preds variant
-    const double* preds;
-    int64_t ld;
-};
-
-__device__ __forceinline__ bool el_pair_less(u64 pa, u32 sa, u64 pb, u32 sb) {
-    return (pa < pb) || (pa == pb && sa < sb);
-}
-
-__device__ __forceinline__ void el_wave_bitonic_desc_pair(u64* a, u32* s, int n, int lane) {
-    for (int size = 2; size <= n; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = lane; t < (n >> 1); t += 64) {
-                int i = 2 * t - (t & (stride - 1));
-                int j = i + stride;
-                bool desc = ((i & size) == 0);
-                u64 x = a[i], y = a[j];
-                u32 sx = s[i], sy = s[j];
-                bool sw = desc ? el_pair_less(x, sx, y, sy) : el_pair_less(y, sy, x, sx);
-                if (sw) {
-                    a[i] = y;
-                    a[j] = x;
-                    s[i] = sy;
-                    s[j] = sx;
-                }
-            }
-            el_wave_lds_sync();
-        }
-    }
-}
-
-template <bool DENSE>
-__global__ __launch_bounds__(64) void k_topk_wave_f64(TopkParams64 p, int cap) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    u64* prim = reinterpret_cast<u64*>(smem);        // [cap]
-    u32* sec = reinterpret_cast<u32*>(prim + cap);   // [cap]
-    const int lane = threadIdx.x;
-    const int64_t user = p.u_start + blockIdx.x;
-    const int F = p.F;
-    const double* pu = DENSE ? nullptr : p.P + user * (int64_t)F;
-    int64_t e0 = 0, e1 = 0, c0 = 0, c1 = 0;
-    if (p.excl_indptr) {
-        e0 = p.excl_indptr[user];
-        e1 = p.excl_indptr[user + 1];
-    }
-    int64_t ncand = p.I_local;
-    if (p.cand_indptr) {
-        c0 = p.cand_indptr[user];
-        c1 = p.cand_indptr[user + 1];
-        ncand = c1 - c0;
-    }
-    const bool use_excl = (p.excl_indptr != nullptr) && (p.cand_indptr == nullptr);
-    int cnt = 0;
-    double tau = -INFINITY;
-    auto compact = [&]() {
-        el_wave_lds_sync();
-        for (int t = cnt + lane; t < cap; t += 64) {
-            prim[t] = 0ull;
-            sec[t] = 0u;
-        }
-        el_wave_lds_sync();
-        el_wave_bitonic_desc_pair(prim, sec, cap, lane);
-        cnt = cnt < p.k ? cnt : p.k;
-        tau = (cnt >= p.k) ? el_ord2d(prim[p.k - 1]) : -INFINITY;
-        el_wave_lds_sync();
-    };
-    for (int64_t base = 0; base < ncand; base += 64) {
-        int64_t pos = base + lane;
-        bool valid = pos < ncand;
-        int32_t gitem = -1;
-        int64_t il = 0;
-        if (valid) {
-            if (p.cand_indptr) {
-                gitem = p.cand_indices[c0 + pos];
-                il = (int64_t)gitem - p.item_offset;
-                valid = (il >= 0 && il < p.I_local);
-            } else {
-                il = pos;
-                gitem = (int32_t)(p.item_offset + pos);
-            }
-        }
-        double s = 0.0;
-        if (valid) {
-            if (DENSE) {
-                s = p.preds[(int64_t)blockIdx.x * p.ld + il] + 0.0;
-            } else {
-                const double* qi = p.Q + il * (int64_t)F;
-                double acc = 0.0;
-                for (int f = 0; f < F; ++f) acc = __builtin_fma(qi[f], pu[f], acc);
-                s = (p.b ? acc + p.b[il] : acc) + 0.0;
-            }
-        }
-        bool hit = valid && (s >= tau);
-        if (hit && use_excl) hit = !el_row_contains(p.excl_indices, e0, e1, gitem);
-        u64 bal = __ballot(hit);
-        if (bal) {
-            int offp = __popcll(bal & ((1ull << lane) - 1ull));
-            if (hit) {
-                prim[cnt + offp] = el_d2ord(s);
-                sec[cnt + offp] = 0xffffffffu - (u32)gitem;
-            }
-            cnt += __popcll(bal);
-        }
-        if (cnt > cap - 64) compact();
-    }
-    compact();
-    const int nv = cnt;
-    const int64_t orow = (int64_t)blockIdx.x * p.k;
-    TopkParams pf = {};
-    pf.item_offset = p.item_offset;
-    pf.I_local = p.I_local;
-    pf.excl_indptr = p.excl_indptr;
-    pf.excl_indices = p.excl_indices;
-    pf.cand_indptr = p.cand_indptr;
-    pf.cand_indices = p.cand_indices;
-    for (int t = lane; t < p.k; t += 64) {
-        int32_t oi;
-        double ov;
-        if (t < nv) {
-            oi = (int32_t)(0xffffffffu - sec[t]);
-            ov = el_ord2d(prim[t]);
-        } else {
-            oi = el_fill_masked(pf, e0, e1, c0, c1, t - nv);
-            ov = -INFINITY;
-        }
-        p.out_idx[orow + t] = oi;
-        p.out_val[orow + t] = ov;
-    }
-}
-
-// =====================================================================================
 // host side
 // =====================================================================================
 static bool mfma_eligible(int F, int k, const void* cand) { return cand == nullptr && F >= 1 && F <= 256 && k >= 1 && k <= 40; }
@@ -593,14 +450,66 @@ static int dispatch_mfma_fp(const TopkParams& p, int vec, hipStream_t st) {
     return launch_mfma<256, 2, CAP, 32, 4, 1>(p, vec, st);
 }
 
-static int check_topk_args(const char* fn, int64_t u_start, int64_t u_stop, int64_t I_local, int F, int k,
-                           const void* out_idx, const void* out_val) {
+// ---- the four wave entry points: one check, one fill, one launch ------------------------------------------------------
+// every check any of the four made.  src0, src1: the two factor tables, or (dense) the block of leading dimension ld
+static int check_topk_args(const char* fn, bool dense, const void* src0, const void* src1, int64_t ld, int64_t u_start, int64_t u_stop,
+                           int64_t I_local, int F, const void* excl_indptr, const void* excl_indices, const void* cand_indptr,
+                           const void* cand_indices, int k, const void* out_idx, const void* out_val) {
     EL_REQUIRE(u_stop >= u_start, "%s: u_stop < u_start", fn);
     EL_REQUIRE(I_local >= 0 && I_local < 0x7fffffffLL, "%s: I_local out of range", fn);
     EL_REQUIRE(F >= 1, "%s: F must be >= 1", fn);
     EL_REQUIRE(k >= 1 && k <= 4032, "%s: k=%d unsupported (1..4032)", fn, k);
     EL_REQUIRE(u_stop == u_start || (out_idx && out_val), "%s: null output", fn);
+    if (dense) {
+        EL_REQUIRE(src0 && ld >= I_local, "%s: bad preds/ld", fn);
+    } else {
+        EL_REQUIRE(src0 && src1, "%s: null factor table", fn);
+    }
+    EL_REQUIRE(excl_indptr != nullptr || excl_indices == nullptr, "%s: excl_indices without excl_indptr", fn);
+    EL_REQUIRE(excl_indptr == nullptr || excl_indices != nullptr, "%s: excl_indptr without excl_indices", fn);
+    EL_REQUIRE((cand_indptr == nullptr) == (cand_indices == nullptr), "%s: cand CSR needs both arrays", fn);
     return 0;
+}
+
+// tables (scoring) or preds / ld (dense, F = 1, item_offset = 0); the fp32 list and split fields stay zero
+template <class T>
+static TopkParamsT<T> topk_params(const T* Gu, const T* Gi, const T* Bi, const T* preds, int64_t ld, int64_t u_start, int64_t u_stop,
+                                  int64_t item_offset, int64_t I_local, int F, const int64_t* excl_indptr, const int32_t* excl_indices,
+                                  const int64_t* cand_indptr, const int32_t* cand_indices, int k, int32_t* out_idx, T* out_val) {
+    TopkParamsT<T> p;
+    memset(&p, 0, sizeof(p));
+    p.Gu = Gu, p.Gi = Gi, p.Bi = Bi, p.preds = preds, p.ld = ld;
+    p.u_start = u_start, p.u_stop = u_stop, p.item_offset = item_offset, p.I_local = I_local, p.F = F;
+    p.excl_indptr = excl_indptr, p.excl_indices = excl_indices, p.cand_indptr = cand_indptr, p.cand_indices = cand_indices;
+    p.k = k, p.out_idx = out_idx, p.out_val = out_val;
+    return p;
+}
+
+// one wave per row of the grid (grid.y: item slices of the fp32 list route)
+template <class T, bool DENSE>
+static int launch_topk_wave(const TopkParamsT<T>& p, dim3 grid, hipStream_t st) {
+    const int cap = el_select_cap(p.k);
+    EL_LAUNCH(sizeof(T) == 4 ? "k_topk_wave" : "k_topk_wave_f64", (k_topk_wave<T, DENSE>), grid, dim3(64), TopkKey<T>::lds_bytes(cap), st, p,
+              cap);
+    EL_CHECK_LAUNCH();
+    return 0;
+}
+
+// check, fill, launch: all of el_dense_topk, el_score_topk_f64 and el_dense_topk_f64 (el_score_topk makes the same three calls
+// around its choice of route)
+template <class T, bool DENSE>
+static int run_topk_wave(const char* fn, el_ctx* ctx, void* stream, const T* Gu, const T* Gi, const T* Bi, const T* preds, int64_t ld,
+                         int64_t u_start, int64_t u_stop, int64_t item_offset, int64_t I_local, int F, const int64_t* excl_indptr,
+                         const int32_t* excl_indices, const int64_t* cand_indptr, const int32_t* cand_indices, int k, int32_t* out_idx,
+                         T* out_val) {
+    if (int rc = el_bind(ctx)) return rc;
+    if (int rc = check_topk_args(fn, DENSE, DENSE ? preds : Gu, Gi, ld, u_start, u_stop, I_local, F, excl_indptr,
+                                 excl_indices, cand_indptr, cand_indices, k, out_idx, out_val))
+        return rc;
+    if (u_stop == u_start) return 0;
+    return launch_topk_wave<T, DENSE>(topk_params(Gu, Gi, Bi, preds, ld, u_start, u_stop, item_offset, I_local, F, excl_indptr, excl_indices,
+                                                  cand_indptr, cand_indices, k, out_idx, out_val),
+                                      dim3((unsigned)(u_stop - u_start)), (hipStream_t)stream);
 }
 
 int el_topk_launch_mfma(const TopkParams& p, hipStream_t st) {
@@ -710,20 +619,18 @@ int el_topk_run_list(const TopkParams& p0, const TopkListWs& scratch, hipStream_
             d.out_idx = scratch.part_idx;
             d.out_val = scratch.part_val;
         }
-        const int wcap = el_select_cap(p0.k);
-        EL_LAUNCH("k_topk_wave", k_topk_wave<true>, dim3(LIST_DENSE, DS > 1 ? DS : 1), dim3(64), (size_t)wcap * 8 + 16, st, d, wcap);
+        if (int rc = launch_topk_wave<float, true>(d, dim3(LIST_DENSE, DS > 1 ? DS : 1), st)) return rc;
         if (DS > 1) {
             int mcap = el_pow2(DS * p0.k);
             if (mcap < 64) mcap = 64;
             EL_LAUNCH("k_topk_merge", k_topk_merge, dim3(LIST_DENSE), dim3(64), (size_t)mcap * 8, st, (const int32_t*)scratch.part_idx,
                       (const float*)scratch.part_val, DS, (int64_t)LIST_DENSE, p0.k, mcap, p0.out_idx, p0.out_val, p0.ulist, p0.ulist_n, 0);
+            EL_CHECK_LAUNCH();
         }
-        EL_CHECK_LAUNCH();
     }
     const int skip1 = p0.I_local > 0 ? LIST_DENSE : 0;
     if (!mfma_eligible(p0.F, p0.k, p0.cand_indptr)) {       // large k: the wave kernel takes the rest of the list
         if (n_users > skip1) {
-            const int wcap = el_select_cap(p0.k);
             int WS = (int)((p0.I_local + 1023) / 1024);             // item slices: one wave per (entry, slice) + merge
             if (WS > LIST_SPLIT) WS = LIST_SPLIT;
             while (WS > 1 && WS * p0.k > 8192) --WS;                // merge buffer limit
@@ -737,21 +644,21 @@ int el_topk_run_list(const TopkParams& p0, const TopkListWs& scratch, hipStream_
                 q.out_val = scratch.part_val;
             }
             const int64_t rows = (n_users - skip1) < cap ? (n_users - skip1) : cap;
-            EL_LAUNCH("k_topk_wave", k_topk_wave<false>, dim3((unsigned)rows, WS > 1 ? WS : 1), dim3(64), (size_t)wcap * 8 + 16, st, q, wcap);
+            if (int rc = launch_topk_wave<float, false>(q, dim3((unsigned)rows, WS > 1 ? WS : 1), st)) return rc;
             if (WS > 1) {
                 int mcap = el_pow2(WS * p0.k);
                 if (mcap < 64) mcap = 64;
                 EL_LAUNCH("k_topk_merge", k_topk_merge, dim3((unsigned)rows), dim3(64), (size_t)mcap * 8, st, (const int32_t*)scratch.part_idx,
                           (const float*)scratch.part_val, WS, cap, p0.k, mcap, p0.out_idx, p0.out_val, p0.ulist, p0.ulist_n, skip1);
+                EL_CHECK_LAUNCH();
             }
             if (n_users > skip1 + cap) {                             // beyond the split scratch: unsplit
                 TopkParams r = p0;
                 r.ulist_skip = (int)(skip1 + cap);
                 r.ulist_max = 0;
                 r.nsplit = 0;
-                EL_LAUNCH("k_topk_wave", k_topk_wave<false>, dim3((unsigned)(n_users - skip1 - cap)), dim3(64), (size_t)wcap * 8 + 16, st, r, wcap);
+                if (int rc = launch_topk_wave<float, false>(r, dim3((unsigned)(n_users - skip1 - cap)), st)) return rc;
             }
-            EL_CHECK_LAUNCH();
         }
         return 0;
     }
@@ -795,33 +702,15 @@ extern "C" int el_score_topk(el_ctx* ctx, void* stream, const float* Gu, const f
     // el_topk_screen_stats describes the LAST el_score_topk call: cleared here, set again only by a screened run that completed (a call
     // on another route, a failed call or a freed workspace must not leave pointers of an earlier call behind)
     ctx->scr_cnt = nullptr, ctx->scr_flagged = nullptr, ctx->scr_users = 0;
-    if (int rc = check_topk_args("el_score_topk", u_start, u_stop, I_local, F, k, out_idx, out_val)) return rc;
     const bool items_unchanged = (algo & EL_TOPK_ITEMS_UNCHANGED) != 0;
     algo &= 0xff;
-    EL_REQUIRE(Gu && Gi, "el_score_topk: null factor table");
-    EL_REQUIRE((excl_indptr == nullptr) == (excl_indices == nullptr) || excl_indptr != nullptr,
-               "el_score_topk: excl_indices without excl_indptr");
-    EL_REQUIRE((cand_indptr == nullptr) == (cand_indices == nullptr), "el_score_topk: cand CSR needs both arrays");
+    if (int rc = check_topk_args("el_score_topk", false, Gu, Gi, 0, u_start, u_stop, I_local, F, excl_indptr, excl_indices, cand_indptr,
+                                 cand_indices, k, out_idx, out_val))
+        return rc;
     if (u_stop == u_start) return 0;
     hipStream_t st = (hipStream_t)stream;
-    TopkParams p;
-    memset(&p, 0, sizeof(p));
-    p.Gu = Gu;
-    p.Gi = Gi;
-    p.Bi = Bi;
-    p.u_start = u_start;
-    p.u_stop = u_stop;
-    p.item_offset = item_offset;
-    p.I_local = I_local;
-    p.F = F;
-    p.excl_indptr = excl_indptr;
-    p.excl_indices = excl_indices;
-    p.cand_indptr = cand_indptr;
-    p.cand_indices = cand_indices;
-    p.k = k;
-    p.out_idx = out_idx;
-    p.out_val = out_val;
-    p.dbg = 0;
+    const TopkParams p = topk_params<float>(Gu, Gi, Bi, nullptr, 0, u_start, u_stop, item_offset, I_local, F, excl_indptr, excl_indices,
+                                            cand_indptr, cand_indices, k, out_idx, out_val);
     const bool selig = el_topk_screen_eligible(F, k, cand_indptr);
     if (algo == EL_TOPK_SCREEN) EL_REQUIRE(selig, "el_score_topk: screened kernel needs F<=256, k<=128 and no candidate list");
     if (algo == EL_TOPK_SCREEN ||
@@ -831,105 +720,48 @@ extern "C" int el_score_topk(el_ctx* ctx, void* stream, const float* Gu, const f
     if (algo == EL_TOPK_MFMA) EL_REQUIRE(elig, "el_score_topk: MFMA kernel needs F<=256, k<=40 and no candidate list");
     bool use_mfma = (algo == EL_TOPK_MFMA) || (algo == EL_TOPK_AUTO && elig);
     if (use_mfma) return el_topk_launch_mfma(p, st);
-    int cap = el_select_cap(k);
-    EL_LAUNCH("k_topk_wave", k_topk_wave<false>, dim3((unsigned)(u_stop - u_start)), dim3(64), (size_t)cap * 8 + 16, st, p, cap);
-    EL_CHECK_LAUNCH();
-    return 0;
+    return launch_topk_wave<float, false>(p, dim3((unsigned)(u_stop - u_start)), st);
 }
 
 extern "C" int el_dense_topk(el_ctx* ctx, void* stream, const float* preds, int64_t ld, int64_t u_start,
                              int64_t u_stop, int64_t I, const int64_t* excl_indptr, const int32_t* excl_indices,
                              const int64_t* cand_indptr, const int32_t* cand_indices, int32_t k, int32_t* out_idx,
                              float* out_val) {
-    if (int rc = el_bind(ctx)) return rc;
-    if (int rc = check_topk_args("el_dense_topk", u_start, u_stop, I, 1, k, out_idx, out_val)) return rc;
-    EL_REQUIRE(preds && ld >= I, "el_dense_topk: bad preds/ld");
-    if (u_stop == u_start) return 0;
-    TopkParams p;
-    memset(&p, 0, sizeof(p));
-    p.u_start = u_start;
-    p.u_stop = u_stop;
-    p.item_offset = 0;
-    p.I_local = I;
-    p.F = 1;
-    p.excl_indptr = excl_indptr;
-    p.excl_indices = excl_indices;
-    p.cand_indptr = cand_indptr;
-    p.cand_indices = cand_indices;
-    p.k = k;
-    p.out_idx = out_idx;
-    p.out_val = out_val;
-    p.preds = preds;
-    p.ld = ld;
-    int cap = el_select_cap(k);
-    EL_LAUNCH("k_topk_wave", k_topk_wave<true>, dim3((unsigned)(u_stop - u_start)), dim3(64), (size_t)cap * 8 + 16,
-                       (hipStream_t)stream, p, cap);
-    EL_CHECK_LAUNCH();
-    return 0;
+    return run_topk_wave<float, true>("el_dense_topk", ctx, stream, nullptr, nullptr, nullptr, preds, ld, u_start, u_stop, 0, I, 1,
+                                      excl_indptr, excl_indices, cand_indptr, cand_indices, k, out_idx, out_val);
 }
 
 extern "C" int el_score_topk_f64(el_ctx* ctx, void* stream, const double* P, const double* Q, const double* b,
                                  int64_t u_start, int64_t u_stop, int64_t item_offset, int64_t I_local, int32_t F,
                                  const int64_t* excl_indptr, const int32_t* excl_indices, const int64_t* cand_indptr,
                                  const int32_t* cand_indices, int32_t k, int32_t* out_idx, double* out_val) {
-    if (int rc = el_bind(ctx)) return rc;
-    if (int rc = check_topk_args("el_score_topk_f64", u_start, u_stop, I_local, F, k, out_idx, out_val)) return rc;
-    EL_REQUIRE(P && Q, "el_score_topk_f64: null factor table");
-    if (u_stop == u_start) return 0;
-    TopkParams64 p;
-    memset(&p, 0, sizeof(p));
-    p.P = P;
-    p.Q = Q;
-    p.b = b;
-    p.u_start = u_start;
-    p.u_stop = u_stop;
-    p.item_offset = item_offset;
-    p.I_local = I_local;
-    p.F = F;
-    p.excl_indptr = excl_indptr;
-    p.excl_indices = excl_indices;
-    p.cand_indptr = cand_indptr;
-    p.cand_indices = cand_indices;
-    p.k = k;
-    p.out_idx = out_idx;
-    p.out_val = out_val;
-    int cap = el_select_cap(k);
-    EL_LAUNCH("k_topk_wave_f64", k_topk_wave_f64<false>, dim3((unsigned)(u_stop - u_start)), dim3(64), (size_t)cap * 12,
-                       (hipStream_t)stream, p, cap);
-    EL_CHECK_LAUNCH();
-    return 0;
+    return run_topk_wave<double, false>("el_score_topk_f64", ctx, stream, P, Q, b, nullptr, 0, u_start, u_stop, item_offset, I_local, F,
+                                        excl_indptr, excl_indices, cand_indptr, cand_indices, k, out_idx, out_val);
 }
 
 extern "C" int el_dense_topk_f64(el_ctx* ctx, void* stream, const double* preds, int64_t ld, int64_t u_start, int64_t u_stop,
                                  int64_t I, const int64_t* excl_indptr, const int32_t* excl_indices, const int64_t* cand_indptr,
                                  const int32_t* cand_indices, int32_t k, int32_t* out_idx, double* out_val) {
+    return run_topk_wave<double, true>("el_dense_topk_f64", ctx, stream, nullptr, nullptr, nullptr, preds, ld, u_start, u_stop, 0, I, 1,
+                                       excl_indptr, excl_indices, cand_indptr, cand_indices, k, out_idx, out_val);
+}
+
+template <class T>
+static int run_topk_pad(const char* fn, const char* label, el_ctx* ctx, void* stream, int32_t* idx, const T* val, int64_t n) {
     if (int rc = el_bind(ctx)) return rc;
-    if (int rc = check_topk_args("el_dense_topk_f64", u_start, u_stop, I, 1, k, out_idx, out_val)) return rc;
-    EL_REQUIRE(preds && ld >= I, "el_dense_topk_f64: bad preds/ld");
-    EL_REQUIRE((cand_indptr == nullptr) == (cand_indices == nullptr), "el_dense_topk_f64: cand CSR needs both arrays");
-    EL_REQUIRE(excl_indptr == nullptr || excl_indices != nullptr, "el_dense_topk_f64: excl_indptr without excl_indices");
-    if (u_stop == u_start) return 0;
-    TopkParams64 p;
-    memset(&p, 0, sizeof(p));
-    p.u_start = u_start;
-    p.u_stop = u_stop;
-    p.item_offset = 0;
-    p.I_local = I;
-    p.F = 1;
-    p.excl_indptr = excl_indptr;
-    p.excl_indices = excl_indices;
-    p.cand_indptr = cand_indptr;
-    p.cand_indices = cand_indices;
-    p.k = k;
-    p.out_idx = out_idx;
-    p.out_val = out_val;
-    p.preds = preds;
-    p.ld = ld;
-    int cap = el_select_cap(k);
-    EL_LAUNCH("k_topk_wave_f64", k_topk_wave_f64<true>, dim3((unsigned)(u_stop - u_start)), dim3(64), (size_t)cap * 12,
-                       (hipStream_t)stream, p, cap);
+    EL_REQUIRE(n >= 0 && (n == 0 || (idx && val)), "%s: bad arguments", fn);
+    if (n == 0) return 0;
+    EL_LAUNCH(label, k_topk_pad<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, idx, val, n);
     EL_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int el_topk_pad(el_ctx* ctx, void* stream, int32_t* idx, const float* val, int64_t n) {
+    return run_topk_pad("el_topk_pad", "k_topk_pad", ctx, stream, idx, val, n);
+}
+
+extern "C" int el_topk_pad_f64(el_ctx* ctx, void* stream, int32_t* idx, const double* val, int64_t n) {
+    return run_topk_pad("el_topk_pad_f64", "k_topk_pad_f64", ctx, stream, idx, val, n);
 }
 
 extern "C" int el_topk_merge(el_ctx* ctx, void* stream, const int32_t* parts_idx, const float* parts_val, int32_t G,

@@ -171,6 +171,17 @@ def _csr_ptrs(csr):
     return _ptr(csr.indptr, torch.int64, "indptr"), _ptr(csr.indices, torch.int32, "indices")
 
 
+def _topk_io(ctx, n, k, dtype, excl, cand, out_idx=None, out_val=None):
+    """What the four wave top-k wrappers share: the (n, k) outputs (the caller's where given) and the tail of the library call,
+    (excl indptr, excl indices, cand indptr, cand indices, k, out_idx, out_val)."""
+    if out_idx is None:
+        out_idx = torch.empty((n, k), dtype=torch.int32, device=ctx.device)
+    if out_val is None:
+        out_val = torch.empty((n, k), dtype=dtype, device=ctx.device)
+    tail = (*_csr_ptrs(excl), *_csr_ptrs(cand), int(k), _ptr(out_idx, torch.int32), _ptr(out_val, dtype))
+    return out_idx, out_val, tail
+
+
 # ------------------------------------------------------------------------------------------
 # scoring + top-k
 # ------------------------------------------------------------------------------------------
@@ -184,12 +195,7 @@ def score_topk(ctx, Gu, Gi, Bi, u_start, u_stop, k, excl=None, cand=None, item_o
     I_local, F = Gi.shape
     if Gu.shape[1] != F:
         raise ValueError("Gu/Gi factor mismatch")
-    if out_idx is None:
-        out_idx = torch.empty((n, k), dtype=torch.int32, device=ctx.device)
-    if out_val is None:
-        out_val = torch.empty((n, k), dtype=torch.float32, device=ctx.device)
-    ep, ei = _csr_ptrs(excl)
-    cp, ci = _csr_ptrs(cand)
+    out_idx, out_val, tail = _topk_io(ctx, n, k, torch.float32, excl, cand, out_idx, out_val)
     algo_id = TOPK_ALGOS[algo] if isinstance(algo, str) else int(algo)
     ws, need = None, 0
     if cand is None and algo_id in (EL_TOPK_AUTO, EL_TOPK_SCREEN):
@@ -198,8 +204,7 @@ def score_topk(ctx, Gu, Gi, Bi, u_start, u_stop, k, excl=None, cand=None, item_o
             ws = _ptr(workspace(ctx, "_topk_ws", need, ctx.device))
     check(ctx.lib.el_score_topk(ctx.handle, ctx.stream(), _ptr(Gu, torch.float32, "Gu"),
                                 _ptr(Gi, torch.float32, "Gi"), _ptr(Bi, torch.float32, "Bi"),
-                                int(u_start), int(u_stop), int(item_offset), int(I_local), int(F),
-                                ep, ei, cp, ci, int(k), _ptr(out_idx, torch.int32), _ptr(out_val, torch.float32),
+                                int(u_start), int(u_stop), int(item_offset), int(I_local), int(F), *tail,
                                 algo_id | (_lib.EL_TOPK_ITEMS_UNCHANGED if items_unchanged else 0), ws, need),
           "el_score_topk")
     return out_idx, out_val
@@ -209,14 +214,10 @@ def score_topk_f64(ctx, P, Q, b, u_start, u_stop, k, excl=None, cand=None, item_
     """MFModel.get_user_predictions (BPRMF_model.py:70-85), fp64 tables."""
     n = int(u_stop) - int(u_start)
     I_local, F = Q.shape
-    out_idx = torch.empty((n, k), dtype=torch.int32, device=ctx.device)
-    out_val = torch.empty((n, k), dtype=torch.float64, device=ctx.device)
-    ep, ei = _csr_ptrs(excl)
-    cp, ci = _csr_ptrs(cand)
+    out_idx, out_val, tail = _topk_io(ctx, n, k, torch.float64, excl, cand)
     check(ctx.lib.el_score_topk_f64(ctx.handle, ctx.stream(), _ptr(P, torch.float64, "P"),
                                     _ptr(Q, torch.float64, "Q"), _ptr(b, torch.float64, "b"),
-                                    int(u_start), int(u_stop), int(item_offset), int(I_local), int(F),
-                                    ep, ei, cp, ci, int(k), _ptr(out_idx), _ptr(out_val)), "el_score_topk_f64")
+                                    int(u_start), int(u_stop), int(item_offset), int(I_local), int(F), *tail), "el_score_topk_f64")
     return out_idx, out_val
 
 
@@ -225,13 +226,9 @@ def dense_topk(ctx, preds, u_start, u_stop, k, excl=None, cand=None):
     n, I = preds.shape
     if n != int(u_stop) - int(u_start):
         raise ValueError("preds rows must equal u_stop - u_start")
-    out_idx = torch.empty((n, k), dtype=torch.int32, device=ctx.device)
-    out_val = torch.empty((n, k), dtype=torch.float32, device=ctx.device)
-    ep, ei = _csr_ptrs(excl)
-    cp, ci = _csr_ptrs(cand)
+    out_idx, out_val, tail = _topk_io(ctx, n, k, torch.float32, excl, cand)
     check(ctx.lib.el_dense_topk(ctx.handle, ctx.stream(), _ptr(preds, torch.float32, "preds"), int(preds.stride(0)),
-                                int(u_start), int(u_stop), int(I), ep, ei, cp, ci, int(k),
-                                _ptr(out_idx), _ptr(out_val)), "el_dense_topk")
+                                int(u_start), int(u_stop), int(I), *tail), "el_dense_topk")
     return out_idx, out_val
 
 
@@ -1012,15 +1009,9 @@ def dense_topk_f64(ctx, preds, u_start, u_stop, k, excl=None, cand=None, out_idx
     n, I = int(u_stop) - int(u_start), int(preds.shape[1])
     if preds.shape[0] < n:
         raise ValueError("preds rows must cover u_stop - u_start")
-    if out_idx is None:
-        out_idx = torch.empty((n, k), dtype=torch.int32, device=ctx.device)
-    if out_val is None:
-        out_val = torch.empty((n, k), dtype=torch.float64, device=ctx.device)
-    ep, ei = _csr_ptrs(excl)
-    cp, ci = _csr_ptrs(cand)
+    out_idx, out_val, tail = _topk_io(ctx, n, k, torch.float64, excl, cand, out_idx, out_val)
     check(ctx.lib.el_dense_topk_f64(ctx.handle, ctx.stream(), _ptr(preds, torch.float64, "preds"), int(preds.stride(0)),
-                                    int(u_start), int(u_stop), I, ep, ei, cp, ci, int(k), _ptr(out_idx, torch.int32),
-                                    _ptr(out_val, torch.float64)), "el_dense_topk_f64")
+                                    int(u_start), int(u_stop), I, *tail), "el_dense_topk_f64")
     if pad:
         check(ctx.lib.el_topk_pad_f64(ctx.handle, ctx.stream(), _ptr(out_idx, torch.int32), _ptr(out_val, torch.float64),
                                       int(n * k)), "el_topk_pad_f64")

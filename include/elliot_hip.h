@@ -404,7 +404,9 @@ enum {
  *   rows with fewer than k unmasked items are padded with -inf and the lowest
  *   masked item indices, as tf.where(mask, preds, -inf) + top_k would return.
  * Gi / Bi describe the LOCAL item shard [item_offset, item_offset+I_local); out_idx
- * holds GLOBAL item indices.  CSR rows are indexed by absolute user id.
+ * holds GLOBAL item indices.  CSR rows are indexed by absolute user id.  A mask CSR is given with BOTH its arrays or with
+ * neither (an all-empty CSR still passes a non-NULL indices pointer): el_score_topk, el_score_topk_f64, el_dense_topk and
+ * el_dense_topk_f64 refuse a half-given one before they launch anything.
  *   out_idx int32[(u_stop-u_start), k], out_val float[(u_stop-u_start), k]
  * ws: el_score_topk_ws_bytes(...) bytes (0 unless the screened kernel can run);
  *     excl_nnz = entries of the exclusion rows [u_start,u_stop) (0 without a mask): the

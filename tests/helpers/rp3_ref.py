@@ -181,3 +181,24 @@ def reference_w(z, tag, I):
     W = sp.csc_matrix((z[f"{tag}_w_data"], z[f"{tag}_w_indices"], z[f"{tag}_w_indptr"]), shape=(I, I), dtype=np.float32).tocsr()
     W.sort_indices()
     return W
+
+
+# ---- device side of the GPU tests -----------------------------------------------------------------------------------------
+def to_device(ops, ctx, Piu, Pui, degree):
+    import torch
+    Piu, Pui = sp.csr_matrix(Piu), sp.csr_matrix(Pui)
+    assert Piu.has_sorted_indices and Pui.has_sorted_indices
+    return (ops.DeviceCSR(Piu.indptr, Piu.indices, Piu.shape[1], ctx.device), ops.device_values(Piu.data, ctx.device),
+            ops.DeviceCSR(Pui.indptr, Pui.indices, Pui.shape[1], ctx.device), ops.device_values(Pui.data, ctx.device),
+            torch.from_numpy(np.ascontiguousarray(degree, np.float64)).to(ctx.device))
+
+
+def host_w(W, vals):
+    n = W.n_rows
+    return sp.csr_matrix((vals[:W.nnz].cpu().numpy(), W.indices[:W.nnz].cpu().numpy(), W.indptr.cpu().numpy()), shape=(n, n))
+
+
+def assert_w_equal(Wd, Wr):
+    assert np.array_equal(Wd.indptr, Wr.indptr)
+    assert np.array_equal(Wd.indices, Wr.indices)
+    assert np.array_equal(bits(Wd.data), bits(Wr.data))

@@ -6,31 +6,12 @@ import scipy.sparse as sp
 import torch
 
 from tests.helpers import knn_ref, rp3_ref
-from tests.helpers.rp3_ref import bits, case_matrix, golden_operands, load_golden as load, reference_w
+from tests.helpers.rp3_ref import assert_w_equal, bits, case_matrix, golden_operands, host_w, load_golden as load, reference_w, to_device
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN_CASES = 7
 TILE = 4096                      # RP3_TILE of csrc/el_rp3.hip: columns of one slice
-
-
-def to_device(ops, ctx, Piu, Pui, degree):
-    Piu, Pui = sp.csr_matrix(Piu), sp.csr_matrix(Pui)
-    assert Piu.has_sorted_indices and Pui.has_sorted_indices
-    return (ops.DeviceCSR(Piu.indptr, Piu.indices, Piu.shape[1], ctx.device), ops.device_values(Piu.data, ctx.device),
-            ops.DeviceCSR(Pui.indptr, Pui.indices, Pui.shape[1], ctx.device), ops.device_values(Pui.data, ctx.device),
-            torch.from_numpy(np.ascontiguousarray(degree, np.float64)).to(ctx.device))
-
-
-def host_w(W, vals):
-    n = W.n_rows
-    return sp.csr_matrix((vals[:W.nnz].cpu().numpy(), W.indices[:W.nnz].cpu().numpy(), W.indptr.cpu().numpy()), shape=(n, n))
-
-
-def assert_w_equal(Wd, Wr):
-    assert np.array_equal(Wd.indptr, Wr.indptr)
-    assert np.array_equal(Wd.indices, Wr.indices)
-    assert np.array_equal(bits(Wd.data), bits(Wr.data))
 
 
 def golden_case(golden, n):
