@@ -71,6 +71,15 @@ class VaeState(C.Structure):
 _P4 = C.c_void_p * 4
 
 
+class AutoRecState(C.Structure):
+    _fields_ = [
+        ("N", C.c_int64), ("H", C.c_int32), ("out_act", C.c_int32), ("Bmax", C.c_int64), ("nnz_max", C.c_int64),
+        ("w", _P4), ("g", _P4), ("m", _P4), ("v", _P4),
+        ("h", _f32p), ("dh", _f32p), ("d", _f32p),
+        ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+    ]
+
+
 class GraphCsr(C.Structure):
     _fields_ = [
         ("indptr", _i64p), ("indices", _i32p), ("vals", _f32p), ("N", C.c_int64), ("n0", C.c_int64),
@@ -221,6 +230,13 @@ PROTOTYPES = {
                                C.c_float, C.c_float, C.c_uint64, C.c_int32, _f64p]),
     "el_vae_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(VaeState), C.c_float]),
     "el_vae_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(VaeState), _i64p, _i32p, _i32p, C.c_int64, _f32p]),
+    "el_autorec_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "el_autorec_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(AutoRecState), _i64p, _i32p, _i32p, C.c_int64, C.c_int64, _f64p]),
+    "el_autorec_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(AutoRecState), C.c_float]),
+    "el_autorec_train_step": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(AutoRecState), _i64p, _i32p, _i32p, C.c_int64, C.c_float,
+                                        _f64p]),
+    "el_autorec_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(AutoRecState), _i64p, _i32p, _i32p, C.c_int64, _f32p]),
+    "el_autorec_rowbias_act": (C.c_int, [C.c_void_p, C.c_void_p, _f32p, C.c_int64, C.c_int64, C.c_int64, _f32p, C.c_int]),
     "el_pointwise_sample_meta": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, C.c_void_p, C.c_int64, C.c_int64, C.c_uint64,
                                            C.c_uint64, C.c_int64, _i32p, _i32p, _f32p]),
     "el_pointwise_sample": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64,

@@ -2751,6 +2751,104 @@ class VaeDeviceState:
         return v
 
 
+class AutoRecDeviceState:
+    """Variables, Adam slots and step buffers of ItemAutoRec / UserAutoRec in HBM (userautorec_model.py:54-90,
+    itemautorec_model.py:51-87).
+
+    weights: dict with W1[N,H] b1[H] W2[H,N] b2[N] in Keras' Dense kernel layout [in, out]; the decoder kernel is held transposed
+    on the device (W2T [N,H]).  out_act: None / "none" (UserAutoRec's linear head) or "sigmoid" (ItemAutoRec).  max_batch rows and
+    nnz_max entries are what one training batch may hold (el_autorec_state)."""
+    ORDER = ("W1", "b1", "W2T", "b2")
+
+    def __init__(self, ctx, weights, out_act, max_batch, nnz_max):
+        self.ctx = ctx
+        dev = ctx.device
+        f = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev) if isinstance(x, np.ndarray) \
+            else x.to(device=dev, dtype=torch.float32).contiguous().clone()
+        W1, W2 = f(weights["W1"]), f(weights["W2"])
+        self.N, self.H = (int(x) for x in W1.shape)
+        if tuple(W2.shape) != (self.H, self.N):
+            raise ValueError(f"W2 must be [H, N] = {(self.H, self.N)}, got {tuple(W2.shape)}")
+        self.out_act = ACTS[out_act]
+        self.Bmax, self.nnz_max = int(max_batch), int(nnz_max)
+        self.w = [W1, f(weights["b1"]), W2.t().contiguous(), f(weights["b2"])]
+        self.g = [torch.zeros_like(x) for x in self.w]
+        self.m = [torch.zeros_like(x) for x in self.w]
+        self.v = [torch.zeros_like(x) for x in self.w]
+        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
+        self.h, self.dh, self.d = z(self.Bmax, self.H), z(self.Bmax, self.H), z(max(self.nnz_max, 1))
+        need = int(ctx.lib.el_autorec_ws_bytes(self.N, self.Bmax, self.nnz_max))
+        self._ws = torch.zeros(max(need, 256), dtype=torch.uint8, device=dev)          # (zeros: its first word is the status)
+        self.loss = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.step = 0
+        arr = lambda ts: (C.c_void_p * 4)(*[x.data_ptr() for x in ts])
+        self._c = _lib.AutoRecState(N=self.N, H=self.H, out_act=self.out_act, Bmax=self.Bmax, nnz_max=self.nnz_max,
+                                    w=arr(self.w), g=arr(self.g), m=arr(self.m), v=arr(self.v), h=self.h.data_ptr(),
+                                    dh=self.dh.data_ptr(), d=self.d.data_ptr(), ws=self._ws.data_ptr(), ws_bytes=self._ws.numel())
+
+    def weights(self):
+        """Host copies keyed like the constructor argument (W2 back in Keras' [H, N] layout)."""
+        w = {n: x.cpu().numpy() for n, x in zip(self.ORDER, self.w)}
+        return {"W1": w["W1"], "b1": w["b1"], "W2": np.ascontiguousarray(w["W2T"].T), "b2": w["b2"]}
+
+    def train_step(self, csr, rows, lr):
+        """train_step (userautorec_model.py:92-107) on the rows `rows` (int32 device tensor) of `csr`."""
+        self.step += 1
+        check(self.ctx.lib.el_autorec_train_step(self.ctx.handle, self.ctx.stream(), C.byref(self._c), *_csr_ptrs(csr),
+                                                 _ptr(rows, torch.int32, "rows"), int(rows.numel()),
+                                                 float(adam_lr_t(lr, self.step)), _ptr(self.loss, torch.float64)),
+              "el_autorec_train_step")
+
+    def grads(self, csr, rows, n_global=None):
+        """Forward + loss + backward only; the batch mean runs over n_global rows."""
+        B = rows.numel()
+        check(self.ctx.lib.el_autorec_grads(self.ctx.handle, self.ctx.stream(), C.byref(self._c), *_csr_ptrs(csr),
+                                            _ptr(rows, torch.int32, "rows"), int(B), int(B if n_global is None else n_global),
+                                            _ptr(self.loss, torch.float64)), "el_autorec_grads")
+
+    def apply(self, lr):
+        self.step += 1
+        check(self.ctx.lib.el_autorec_apply(self.ctx.handle, self.ctx.stream(), C.byref(self._c),
+                                            float(adam_lr_t(lr, self.step))), "el_autorec_apply")
+
+    def dense_grads(self):
+        return list(self.g)
+
+    def encode(self, csr, rows, out=None):
+        """sigmoid(x W1 + b1) [B, H] of the rows `rows` of `csr`."""
+        B = rows.numel()
+        if out is None:
+            out = torch.empty((B, self.H), dtype=torch.float32, device=self.ctx.device)
+        check(self.ctx.lib.el_autorec_encode(self.ctx.handle, self.ctx.stream(), C.byref(self._c), *_csr_ptrs(csr),
+                                             _ptr(rows, torch.int32, "rows"), int(B), _ptr(out, torch.float32, "out")),
+              "el_autorec_encode")
+        return out
+
+    def predict_rows(self, csr, rows):
+        """The model's output [B, N] for the rows `rows` of `csr` (predict, userautorec_model.py:109-119): act(h W2 + b2)."""
+        h = self.encode(csr, rows)
+        return gemm(self.ctx, h, self.w[2], transB=True, bias=self.w[3], act={0: None, 3: "sigmoid"}[self.out_act])
+
+    def predict_columns(self, h_all, start, stop):
+        """Rows [start, stop) of the TRANSPOSED output: out[u, i] = act(W2T[u] . h_all[i] + b2[u]) for the encodings h_all [n, H] of
+        n rows -- the block itemautorec.py:104 gets by transposing on the host."""
+        out = gemm(self.ctx, self.w[2][start:stop], h_all, transB=True)
+        check(self.ctx.lib.el_autorec_rowbias_act(self.ctx.handle, self.ctx.stream(), _ptr(out, torch.float32, "C"),
+                                                  int(out.shape[0]), int(out.shape[1]), int(out.stride(0)),
+                                                  _ptr(self.w[3][start:stop], torch.float32, "bias"), int(self.out_act)),
+              "el_autorec_rowbias_act")
+        return out
+
+    def pop_loss(self):
+        """The loss summed since the last call.  Raises when a batch held more entries than nnz_max (that step computed nothing)."""
+        v = float(self.loss.item())
+        self.loss.zero_()
+        if int(self._ws[:4].view(torch.int32).item()) != 0:
+            self._ws[:4].zero_()
+            raise _lib.ElliotHipError("el_autorec: a batch held more than nnz_max = %d entries" % self.nnz_max)
+        return v
+
+
 # ------------------------------------------------------------------------------------------
 # NeuMF / GMF
 # ------------------------------------------------------------------------------------------

@@ -17,6 +17,8 @@ from .autoencoders.vae.multi_vae import MultiVAE
 from .autoencoders.dae.multi_dae import MultiDAE
 from .neural.NeuMF.neural_matrix_factorization import NeuMF
 from .neural.GeneralizedMF.generalized_matrix_factorization import GMF
+from .neural.ItemAutoRec.itemautorec import ItemAutoRec
+from .neural.UserAutoRec.userautorec import UserAutoRec
 from .knn.item_knn.item_knn import ItemKNN
 from .knn.user_knn.user_knn import UserKNN
 from .knn.attribute_item_knn.attribute_item_knn import AttributeItemKNN
@@ -34,4 +36,4 @@ from .latent_factor_models.BPRSlim.bprslim import BPRSlim
 __all__ = ["BaseRecommenderModel", "init_charger", "RecMixin", "BPRMF_batch", "BPRMF", "MultiVAE", "MultiDAE", "NeuMF", "GMF",
            "MF", "PMF", "FunkSVD", "LogisticMatrixFactorization", "LMF", "CML", "MF2020", "LightGCN", "NGCF", "ProxyRecommender",
            "ItemKNN", "UserKNN", "iALS", "WRMF", "EASER", "RP3beta", "Slim", "PureSVD",
-           "AttributeItemKNN", "AttributeUserKNN", "VSM", "KaHFM", "SlopeOne", "BPRSlim"]
+           "AttributeItemKNN", "AttributeUserKNN", "VSM", "KaHFM", "SlopeOne", "BPRSlim", "ItemAutoRec", "UserAutoRec"]

@@ -939,6 +939,53 @@ int el_vae_predict(el_ctx* ctx, void* stream, const el_vae_state* st,
                    const int64_t* indptr, const int32_t* indices, const int32_t* rows, int64_t B,
                    const float* eps);
 
+/* ---- ItemAutoRec / UserAutoRec ------------------------------------------------------------- */
+
+typedef struct el_autorec_state {
+    int64_t N;        /* layer width: items (UserAutoRec) or users (ItemAutoRec); the CSR a batch is drawn from has N columns */
+    int32_t H;        /* hidden_neuron: a multiple of 4, 4 .. 1024                                                         */
+    int32_t out_act;  /* decoder activation, el_gemm_f32's code: 0 linear (userautorec_model.py:43), 3 sigmoid (itemautorec_model.py:40) */
+    int64_t Bmax;     /* batch rows h / dh can hold; at most 262 144                                                       */
+    int64_t nnz_max;  /* entries of one batch d can hold (< 2^31)                                                          */
+    /* variables, gradients and Adam slots in the order W1[N,H] b1[H] W2T[N,H] b2[N]: the decoder kernel is held TRANSPOSED
+     * (Keras' dense_output.kernel is [H,N]); all 16-byte aligned                                                          */
+    float* w[4];
+    float* g[4];      /* gradients: every element is overwritten by every el_autorec_grads call                            */
+    float* m[4];
+    float* v[4];
+    float* h;         /* [Bmax,H]   sigmoid(x W1 + b1)                                                                     */
+    float* dh;        /* [Bmax,H]   d loss / d (x W1 + b1)                                                                 */
+    float* d;         /* [nnz_max]  d loss / d (h W2 + b2) at the batch's entries, batch row after batch row               */
+    void* ws;         /* el_autorec_ws_bytes(N, Bmax, nnz_max) bytes.  Its first int32 is a STATUS word the caller zeroes once: a
+                       * step whose batch holds more than nnz_max entries computes nothing, sets it to 1 and stores NaN in loss_out */
+    size_t ws_bytes;
+} el_autorec_state;
+
+size_t el_autorec_ws_bytes(int64_t N, int64_t Bmax, int64_t nnz_max);
+
+/* Replaces: UserAutoRecModel / ItemAutoRecModel.train_step (userautorec_model.py:92-107, itemautorec_model.py:89-104) on the batch
+ * whose rows are rows[0..B) of the binary CSR (sp_i_train for the user variant, its transpose for the item variant; column indices
+ * ascending within a row).  loss = (1/B_global) sum_b sum_{j in row b} (1 - r_bj)^2 is ADDED to loss_out (device double[1]).  The
+ * reference masks the reconstruction with sign(batch), so only the batch's entries are evaluated; no [B,N] array is formed, every sum
+ * runs in an order the batch alone fixes.  The l2 kernel_regularizers of the reference never reach its loss: there is no l_w here.
+ * el_autorec_grads leaves the four gradients complete (batch mean over B_global >= B rows: data-parallel callers all-reduce them),
+ * el_autorec_apply is Keras' dense Adam (eps 1e-7, TF ApplyAdam arithmetic) on all four variables with the bias-corrected step size
+ * lr_t; el_autorec_train_step = grads with B_global = B, then apply.                                                             */
+int el_autorec_grads(el_ctx* ctx, void* stream, const el_autorec_state* st, const int64_t* indptr, const int32_t* indices,
+                     const int32_t* rows, int64_t B, int64_t B_global, double* loss_out);
+int el_autorec_apply(el_ctx* ctx, void* stream, const el_autorec_state* st, float lr_t);
+int el_autorec_train_step(el_ctx* ctx, void* stream, const el_autorec_state* st, const int64_t* indptr, const int32_t* indices,
+                          const int32_t* rows, int64_t B, float lr_t, double* loss_out);
+
+/* out[B,H] (16-byte aligned) = sigmoid(x W1 + b1) of rows[0..B): the encoder alone, any B.  Prediction is dense from here
+ * (el_gemm_f32 against W2T, then el_dense_topk).                                                                                  */
+int el_autorec_encode(el_ctx* ctx, void* stream, const el_autorec_state* st, const int64_t* indptr, const int32_t* indices,
+                      const int32_t* rows, int64_t B, float* out);
+
+/* C[r,c] <- act(C[r,c] + bias[r]) on C [M,N] (ldc >= N); act 0 none, 3 sigmoid.  The item variant scores a block of users as
+ * W2T[u] . h[i]: the decoder bias belongs to the block's ROW (itemautorec.py:104 transposes on the host).                        */
+int el_autorec_rowbias_act(el_ctx* ctx, void* stream, float* C, int64_t M, int64_t N, int64_t ldc, const float* bias, int act);
+
 /* ---- NeuMF / GMF (K12-K13) ----------------------------------------------------------------- */
 
 typedef struct el_nmf_state {
