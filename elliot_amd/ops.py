@@ -1673,6 +1673,21 @@ def topk_screen_stats(ctx):
             "fallback_users": int(f.value)}
 
 
+def topk_fragile(ctx, Gu, Gi, idx, val, k, u_start=0, item_offset=0, flags=False, counts=None):
+    """el_topk_fragile on [n, >= k + 1] lists (idx int32 in absolute item ids, val float32) of the users u_start .. u_start + n:
+    Gu holds every user, Gi the items from item_offset on.  ADDS to `counts` (int64[2] on the device: fragile users, lists with
+    fewer than k + 1 entries); returns it, and the uint8 flag per user when flags=True."""
+    n = int(idx.shape[0])
+    if counts is None:
+        counts = torch.zeros(2, dtype=torch.int64, device=ctx.device)
+    fl = torch.zeros(n, dtype=torch.uint8, device=ctx.device) if flags else None
+    check(ctx.lib.el_topk_fragile(ctx.handle, ctx.stream(), _ptr(Gu, torch.float32), _ptr(Gi, torch.float32), int(Gu.shape[1]),
+                                  int(u_start), int(u_start + n), _ptr(idx, torch.int32), _ptr(val, torch.float32), int(idx.shape[1]),
+                                  int(k), int(item_offset), C.c_void_p(fl.data_ptr()) if fl is not None else None,
+                                  _ptr(counts, torch.int64)), "el_topk_fragile")
+    return (counts, fl) if flags else counts
+
+
 def fragile_users(ctx, Gu, Gi, Bi, u_start, u_stop, k, excl=None, cand=None, item_offset=0, algo="auto", flags=False):
     """Fragile-user report: how many of the users [u_start, u_stop) have a rank-k / rank-(k+1) score gap
     below the fp32 re-association bound F 2^-23 |u| max|i| -- for those (and only those) the top-k SET could differ under
@@ -1680,12 +1695,8 @@ def fragile_users(ctx, Gu, Gi, Bi, u_start, u_stop, k, excl=None, cand=None, ite
     user with the fused kernels, then el_topk_fragile.  Returns a dict (and the uint8 flag tensor when flags=True)."""
     idx, val = score_topk(ctx, Gu, Gi, Bi, u_start, u_stop, k + 1, excl=excl, cand=cand, item_offset=item_offset, algo=algo)
     n = u_stop - u_start
-    counts = torch.zeros(2, dtype=torch.int64, device=ctx.device)
-    fl = torch.zeros(n, dtype=torch.uint8, device=ctx.device) if flags else None
-    check(ctx.lib.el_topk_fragile(ctx.handle, ctx.stream(), _ptr(Gu, torch.float32), _ptr(Gi, torch.float32), int(Gu.shape[1]),
-                                  int(u_start), int(u_stop), _ptr(idx, torch.int32), _ptr(val, torch.float32), int(idx.shape[1]),
-                                  int(k), int(item_offset), C.c_void_p(fl.data_ptr()) if fl is not None else None,
-                                  C.c_void_p(counts.data_ptr())), "el_topk_fragile")
+    out = topk_fragile(ctx, Gu, Gi, idx, val, k, u_start=u_start, item_offset=item_offset, flags=flags)
+    counts, fl = out if flags else (out, None)
     c = counts.cpu().tolist()
     rep = {"users": int(n), "k": int(k), "fragile": int(c[0]), "short_lists": int(c[1]),
            "bound": "score[k-1] - score[k] < F * 2^-23 * |u| * max(|i_k|, |i_k+1|)"}
