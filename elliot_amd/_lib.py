@@ -206,6 +206,18 @@ PROTOTYPES = {
                                   C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
     "el_rec_metrics": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, C.c_int64, C.c_int64, C.c_int64, _i64p, _i32p, _f32p,
                                  C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "el_score_rank_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int]),
+    "el_score_rank": (C.c_int, [C.c_void_p, C.c_void_p, _f32p, _f32p, _f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+                                _i64p, _i32p, _i64p, _i32p, _i64p, _i32p, _i32p, C.c_int, C.c_void_p, C.c_size_t]),
+    "el_score_rank_f64": (C.c_int, [C.c_void_p, C.c_void_p, _f64p, _f64p, _f64p, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+                                    _i64p, _i32p, _i64p, _i32p, _i64p, _i32p, _i32p]),
+    "el_dense_rank": (C.c_int, [C.c_void_p, C.c_void_p, _f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                _i64p, _i32p, _i64p, _i32p, _i64p, _i32p, _i32p]),
+    "el_dense_rank_f64": (C.c_int, [C.c_void_p, C.c_void_p, _f64p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                    _i64p, _i32p, _i64p, _i32p, _i64p, _i32p, _i32p]),
+    "el_rank_metrics_ws_bytes": (C.c_size_t, [C.c_int64]),
+    "el_rank_metrics": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, C.c_int64, C.c_int64, _i64p, _i32p, _f32p, C.c_double, _i64p,
+                                  C.c_int64, C.c_int32, _f64p, _f64p, C.c_void_p, C.c_size_t]),
     "el_beyond_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "el_beyond_metrics": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, C.c_int64, C.c_int64, C.c_int64, _i64p, _i32p, _f32p,
                                     C.c_double, C.c_int32, _i64p, _i32p, C.c_int64, C.c_int64, _i32p, C.c_void_p, _f64p, _f64p,

@@ -11,9 +11,13 @@ Definitions follow the reference:
   HR, MAP, MRR, F1   hit_rate.py:66, map.py:69-80, mrr.py:63-70, f1.py:56-68
   averaging          over users that have recommendations AND >= 1 relevant test item (ndcg.py:124-125)
 Computation is vectorised over an [n_users, k] item matrix instead of per-user Python loops.  The remaining
-metrics of the reference (nDCGRendle2020, MAR, the AUC family, DSC, the rating-error metrics, fairness and the other
-complex_metrics, paired tests) are out of scope here; inside an Elliot process the genuine Evaluator is used instead
-(recommender/_compat.py).
+metrics of the reference (nDCGRendle2020, MAR, DSC, the rating-error metrics, fairness and the other complex_metrics, paired
+tests) are out of scope here; inside an Elliot process the genuine Evaluator is used instead (recommender/_compat.py).
+
+AUC, GAUC and LAUC (evaluation/ranks.py) are accepted only with `evaluation.rank_metrics: True`: they need the position of
+every held-out item in the user's complete ranking, which costs one more full-catalogue pass per evaluation (el_rank.hip)
+beside the top-k pass.  Full-length lists are never requested: get_needed_recommendations() stays top_k, the positions come
+from the models' rank() (eval_device) or from the caller (eval(recs, ranks=...)), never from truncated lists.
 
 The accuracy metrics average over the users with >= 1 relevant held-out item; the beyond-accuracy metrics see every
 user whose held-out row is non-empty (evaluator.py:121) and average over either population, as their classes do.
@@ -23,17 +27,20 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from . import beyond
+from . import beyond, ranks
 
 ACCURACY = ("nDCG", "Precision", "Recall", "HR", "MAP", "MRR", "F1")
 SUPPORTED = ACCURACY + beyond.NAMES
 
 
-def _canon(name):
-    for s in SUPPORTED:
+def _canon(name, rank_metrics=False):
+    for s in SUPPORTED + (ranks.NAMES if rank_metrics else ()):
         if s.lower() == name.lower():
             return s
-    raise Exception(f"Metric {name} is not available in the stand-alone evaluator (supported: {SUPPORTED})")
+    hint = ""
+    if any(s.lower() == name.lower() for s in ranks.NAMES):
+        hint = f"; {ranks.NAMES} need `evaluation.rank_metrics: True` (one more full-catalogue pass per evaluation)"
+    raise Exception(f"Metric {name} is not available in the stand-alone evaluator (supported: {SUPPORTED}){hint}")
 
 
 class _Split:
@@ -55,7 +62,10 @@ class Evaluator:
         if any(np.array(self._k) > cfg.top_k):
             raise Exception("Cutoff values must be smaller than recommendation list length (top_k)")
         self._rel_threshold = getattr(cfg.evaluation, "relevance_threshold", 0)
-        self._metrics = [_canon(m) for m in cfg.evaluation.simple_metrics]
+        gate = bool(getattr(cfg.evaluation, "rank_metrics", False))
+        self._metrics = [_canon(m, gate) for m in cfg.evaluation.simple_metrics]
+        self._rank = [m for m in self._metrics if m in ranks.NAMES]
+        self.rank_metrics = bool(self._rank)      # RecMixin: evaluate on the device and hand eval_device positions
         self._accuracy = [m for m in self._metrics if m in ACCURACY]
         self._beyond = [m for m in self._metrics if m in beyond.NAMES]
         self._item_tables = None
@@ -143,7 +153,9 @@ class Evaluator:
 
     def eval_device(self, ctx, data, blocks):
         """blocks: iterable of (first_private_user, idx_val, idx_test) with [n, k] int32 device tensors (idx_val may be
-        the same tensor).  Returns the same structure as eval().
+        the same tensor), or (first, idx_val, idx_test, pos_val, pos_test) where pos_* are the int32 positions of the block's
+        held-out entries (the models' rank() on device_sets()["val" | "test"]; pos_val None without a validation split).
+        Returns the same structure as eval().  AUC and GAUC do not depend on the cutoff; LAUC does.
 
         The accuracy kernel runs as before.  When a beyond-accuracy metric is asked for, el_beyond_metrics runs beside it
         into one item histogram (int32[num_items]) and one row of sums per (split, cutoff); the histograms are finished
@@ -164,10 +176,22 @@ class Evaluator:
                 tables = self._dev_tables = ops.DeviceItemTables(self.item_tables(data), ctx.device)
             bey = {key: (torch.zeros(ops.BEYOND_SUMS, dtype=torch.float64, device=ctx.device),
                          torch.zeros(tables.num_items, dtype=torch.int32, device=ctx.device)) for key in keys}
+        rnk = None
+        if self._rank:
+            from ..recommender.masks import device_masks
+            rank_train = device_masks(data, ctx).train
+            rnk = {key: torch.zeros(ops.RANK_SUMS, dtype=torch.float64, device=ctx.device) for key in keys}
         kept = {"val": [], "test": []} if "SEntropy" in self._beyond else None
-        for first, idx_val, idx_test in blocks:
+        for block in blocks:
+            first, idx_val, idx_test = block[:3]
+            if rnk is not None and len(block) < 5:
+                raise Exception(f"{self._rank} need the positions of the held-out items: blocks of (first, idx_val, idx_test, pos_val, pos_test)")
             for sp, c in keys:
                 idx = idx_val if sp == "val" else idx_test
+                if rnk is not None:
+                    pos = block[3] if sp == "val" else block[4]
+                    ops.rank_metrics(ctx, pos, sets[sp], self._rel_threshold, rank_train, data.num_items, c, u_start=first,
+                                     u_stop=first + idx.shape[0], sums=rnk[(sp, c)])
                 if self._accuracy:
                     ops.rec_metrics(ctx, idx, sets[sp], self._rel_threshold, c, u_start=first, sums=acc[(sp, c)])
                 if bey is not None:
@@ -187,14 +211,19 @@ class Evaluator:
                         ops.beyond_entropy(ctx, idx, sets[sp], nov, c, u_start=first, total=ent)
                 extra[(sp, c)] = (sums.cpu().numpy(), stats.cpu().numpy(), float(ent.cpu()[0]))
         host = {key: v.cpu().numpy() for key, v in acc.items()}
+        rank_host = {key: v.cpu().numpy() for key, v in rnk.items()} if rnk is not None else None
 
         def means(sp, c):
             out = {}
+            if rank_host is not None:
+                out = ranks.means(rank_host[(sp, c)])
+                if not out:
+                    return {}
             if self._accuracy:
                 s = host[(sp, c)]
                 if s[7] == 0:
                     return {}
-                out = {m: float(s[ops.METRIC_NAMES.index(m)] / s[7]) for m in self._accuracy}
+                out.update({m: float(s[ops.METRIC_NAMES.index(m)] / s[7]) for m in self._accuracy})
             if self._beyond:
                 sums, stats, ent = extra[(sp, c)]
                 if sums[0] == 0:
@@ -212,11 +241,16 @@ class Evaluator:
         return res
 
     # ---------------------------------------------------------------------------------------------
-    def _eval_split(self, recs, split, cutoff, validation=False):
+    def _eval_split(self, recs, split, cutoff, validation=False, pos=None):
         """recs: {public_user: [(public_item, score), ...]}"""
         out = self._eval_accuracy(recs, split, cutoff) if self._accuracy else {}
         if self._accuracy and not out:
             return {}
+        if self._rank:
+            more = self._eval_ranks(pos, cutoff, validation)
+            if not more:
+                return {}
+            out.update(more)
         if self._beyond:
             more = self._eval_beyond(recs, cutoff, validation)
             if not more:
@@ -232,6 +266,16 @@ class Evaluator:
             else:
                 self._host_csr[validation] = self._split_arrays(data, self._test_dict_raw(data, validation))
         return self._host_csr[validation]
+
+    def _eval_ranks(self, pos, cutoff, validation):
+        """AUC / GAUC / LAUC of one split from host positions: one int32 per entry of the split's CSR (_host_split_csr: rows =
+        private users, ids ascending), what ranks.positions or the models' rank() give."""
+        indptr, indices, ratings = self._host_split_csr(validation)
+        pos = np.asarray(pos)
+        if pos.shape[0] != indices.shape[0]:
+            raise Exception(f"ranks: {pos.shape[0]} positions for {indices.shape[0]} held-out entries")
+        train_len = np.diff(self._data.sp_i_train.tocsr().indptr)
+        return ranks.finish(pos, indptr, ratings, self._rel_threshold, train_len, self._data.num_items, cutoff)[0]
 
     def _eval_beyond(self, recs, cutoff, validation):
         """The beyond-accuracy metrics of one split from the recommendation dicts, in NumPy (beyond.numpy_terms)."""
@@ -296,13 +340,18 @@ class Evaluator:
             out[m] = float(np.average(v))
         return out
 
-    def eval(self, recommendations):
+    def eval(self, recommendations, ranks=None):
         """recommendations = (recs_val, recs_test); returns {cutoff: {"val_results", "test_results", ...}}
-        exactly as evaluator.py:79-92 (a missing validation split mirrors the test results)."""
+        exactly as evaluator.py:79-92 (a missing validation split mirrors the test results).
+        ranks = (pos_val, pos_test): host positions of the held-out entries in the users' complete rankings, required when AUC /
+        GAUC / LAUC are asked for -- they are never derived from the (truncated) recommendation lists."""
+        if self._rank and ranks is None:
+            raise Exception(f"{self._rank} need the positions of the held-out items in the complete rankings: eval(recs, ranks=(pos_val, "
+                            f"pos_test)); lists of length top_k cannot give them")
         res = {}
         for k in self._k:
-            val = self._eval_split(recommendations[0], self._val, k, validation=True) if self._val else None
-            test = self._eval_split(recommendations[1], self._test, k)
+            val = self._eval_split(recommendations[0], self._val, k, validation=True, pos=ranks[0] if ranks else None) if self._val else None
+            test = self._eval_split(recommendations[1], self._test, k, pos=ranks[1] if ranks else None)
             if not val:
                 val = test
             res[k] = {"val_results": val, "val_statistical_results": {}, "test_results": test,

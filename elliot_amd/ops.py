@@ -756,6 +756,12 @@ class AlsDeviceState:
         return score_topk_f64(self.ctx, self.X, self.Y, self._zero_bias, start, stop, k, excl=csr if kind == "excl" else None,
                               cand=csr if kind == "cand" else None)
 
+    def rank(self, mask, targets, start, stop):
+        """Positions of the entries of rows [start, stop) of `targets` in the order recommend() selects by (el_score_rank_f64)."""
+        if self._zero_bias is None:
+            self._zero_bias = torch.zeros(self.I, dtype=torch.float64, device=self.ctx.device)
+        return score_rank_f64(self.ctx, self.X, self.Y, self._zero_bias, start, stop, targets, **mask_kwargs(mask))
+
 
 # ------------------------------------------------------------------------------------------
 # what the dense item-item models (EASE^R, SlopeOne, BPRSlim) share: the memory guard and the blocked recommend()
@@ -804,6 +810,22 @@ class _DenseScoreState:
                        ci, int(k), _ptr(out_idx[s - start:], torch.int32), _ptr(out_val[s - start:], dt)), "el_dense_topk" + sfx)
         check(pad(ctx.handle, ctx.stream(), _ptr(out_idx, torch.int32), _ptr(out_val, dt), int(n * k)), "el_topk_pad" + sfx)
         return out_idx, out_val
+
+    def rank(self, mask, targets, start, stop):
+        """Positions of the entries of rows [start, stop) of `targets` in the users' full rankings under the tagged mask
+        (dense_rank / dense_rank_f64 on the blocks recommend() selects from): int32 on the device."""
+        ctx, dt = self.ctx, self.SCORE_DTYPE
+        fn = dense_rank if dt == torch.float32 else dense_rank_f64
+        start, stop = int(start), int(stop)
+        hp = _host_indptr(targets)
+        pos = torch.empty(max(int(hp[stop] - hp[start]), 1), dtype=torch.int32, device=ctx.device)[:int(hp[stop] - hp[start])]
+        if self._S is None:
+            self._S = torch.empty((self.block_rows, self.I), dtype=dt, device=ctx.device)
+        for s in range(start, stop, self.block_rows):
+            e = min(s + self.block_rows, stop)
+            self._score_block(s, e, self._S)
+            fn(ctx, self._S, s, e, targets, pos=pos[int(hp[s] - hp[start]):int(hp[e] - hp[start])], I=self.I, **mask_kwargs(mask))
+        return pos
 
 
 # ------------------------------------------------------------------------------------------
@@ -1092,6 +1114,11 @@ class SlopeDeviceState(_DenseScoreState):
         if self.T is None:
             raise _lib.ElliotHipError("SlopeOne: recommend() before build() or set_model()")
         return super().recommend(mask, k, start, stop)
+
+    def rank(self, mask, targets, start, stop):
+        if self.T is None:
+            raise _lib.ElliotHipError("SlopeOne: rank() before build() or set_model()")
+        return super().rank(mask, targets, start, stop)
 
     def _score_block(self, s, e, out):
         slope_scores(self.ctx, self.rows, self.user_mean, self.T, s, e, out=out)
@@ -1541,6 +1568,14 @@ class PureSvdDeviceState:
                                        int(idx.numel())), "el_topk_pad")
         return idx, val
 
+    def rank(self, mask, targets, start, stop):
+        """Positions of the entries of rows [start, stop) of `targets` in the order recommend() selects by (el_score_rank)."""
+        if self.user_vec is None:
+            raise _lib.ElliotHipError("PureSVD: rank() before build() or set_weights()")
+        if self._zero_bias is None:
+            self._zero_bias = torch.zeros(self.I, dtype=torch.float32, device=self.ctx.device)
+        return score_rank(self.ctx, self.user_vec, self.item_vec, self._zero_bias, start, stop, targets, **mask_kwargs(mask))
+
 
 # ------------------------------------------------------------------------------------------
 # accuracy metrics on the device (SURVEY 8f, N1)
@@ -1593,6 +1628,113 @@ def rec_metrics(ctx, rec_idx, test, threshold, cutoff, u_start=0, sums=None, per
                                  C.c_void_p(disc.data_ptr()), C.c_void_p(sums.data_ptr()),
                                  C.c_void_p(rows.data_ptr()) if rows is not None else None,
                                  C.c_void_p(ws.data_ptr()), int(ws.numel())), "el_rec_metrics")
+    return (sums, rows) if per_user else sums
+
+
+# ------------------------------------------------------------------------------------------
+# rank metrics on the device: positions of the held-out items in the full ranking, AUC / GAUC / LAUC sums (el_rank.hip)
+# ------------------------------------------------------------------------------------------
+RANK_METRIC_NAMES = ("AUC", "GAUC", "LAUC")
+RANK_SUMS = 6           # el_rank_metrics' sums (include/elliot_hip.h lists the slots)
+RANK_WAVE_CAP = 512     # targets per catalogue pass of k_rank_wave (el_rank.hip: RANK_CAP)
+RANK_MFMA_CAP = 63      # targets per user of the fused route; users with more take the wave kernel (el_rank.hip: RANK_TCAP)
+RANK_ALGOS = {"auto": EL_TOPK_AUTO, "simple": EL_TOPK_SIMPLE, "mfma": EL_TOPK_MFMA}
+
+
+def _host_indptr(csr):
+    """The row pointers of a device CSR on the host, copied once per object."""
+    h = getattr(csr, "_indptr_host", None)
+    if h is None:
+        h = csr._indptr_host = csr.indptr.cpu().numpy()
+    return h
+
+
+def _rank_io(ctx, targets, u_start, u_stop, excl, cand, pos=None):
+    """What the four rank wrappers share: the int32 positions of the target entries of rows [u_start, u_stop) (the caller's where
+    given) and the tail of the library call, (excl CSR, cand CSR, target CSR, pos)."""
+    hp = _host_indptr(targets)
+    n = int(hp[int(u_stop)] - hp[int(u_start)])
+    if pos is None:
+        pos = torch.empty(max(n, 1), dtype=torch.int32, device=ctx.device)[:n]
+    elif pos.shape[0] != n:
+        raise ValueError(f"pos must hold the {n} target entries of the rows")
+    tail = (*_csr_ptrs(excl), *_csr_ptrs(cand), _ptr(targets.indptr, torch.int64, "targets.indptr"),
+            _ptr(targets.indices, torch.int32, "targets.indices"), C.c_void_p(pos.data_ptr()) if n else _ptr(targets.indices))
+    return pos, tail
+
+
+def score_rank(ctx, Gu, Gi, Bi, u_start, u_stop, targets, excl=None, cand=None, algo="auto", pos=None):
+    """For users [u_start, u_stop) and each entry of their rows of `targets` (DeviceTestSet / DeviceCSR, absolute user rows): the
+    number of admissible items score_topk would list ahead of it -- its index in the k = I list; -1 for ids >= I and masked
+    targets.  int32 on the device, entry e at pos[e - targets.indptr[u_start]]."""
+    I, F = Gi.shape
+    if Gu.shape[1] != F:
+        raise ValueError("Gu/Gi factor mismatch")
+    pos, tail = _rank_io(ctx, targets, u_start, u_stop, excl, cand, pos)
+    algo_id = RANK_ALGOS[algo] if isinstance(algo, str) else int(algo)
+    ws, need = None, 0
+    if cand is None:
+        need = int(ctx.lib.el_score_rank_ws_bytes(int(u_stop) - int(u_start), int(I), int(F), int(pos.shape[0]),
+                                                  int(excl.nnz) if excl is not None else 0, algo_id))
+        if need:
+            ws = _ptr(workspace(ctx, "_rank_ws", need, ctx.device))
+    check(ctx.lib.el_score_rank(ctx.handle, ctx.stream(), _ptr(Gu, torch.float32, "Gu"), _ptr(Gi, torch.float32, "Gi"),
+                                _ptr(Bi, torch.float32, "Bi"), int(u_start), int(u_stop), int(I), int(F), *tail, algo_id, ws, need),
+          "el_score_rank")
+    return pos
+
+
+def score_rank_f64(ctx, P, Q, b, u_start, u_stop, targets, excl=None, cand=None, pos=None):
+    """score_rank for fp64 tables: the order of score_topk_f64."""
+    I, F = Q.shape
+    pos, tail = _rank_io(ctx, targets, u_start, u_stop, excl, cand, pos)
+    check(ctx.lib.el_score_rank_f64(ctx.handle, ctx.stream(), _ptr(P, torch.float64, "P"), _ptr(Q, torch.float64, "Q"),
+                                    _ptr(b, torch.float64, "b"), int(u_start), int(u_stop), int(I), int(F), *tail), "el_score_rank_f64")
+    return pos
+
+
+def _dense_rank(ctx, preds, dtype, u_start, u_stop, targets, excl, cand, pos, I):
+    n = int(u_stop) - int(u_start)
+    if preds.shape[0] < n:
+        raise ValueError("preds rows must cover u_stop - u_start")
+    pos, tail = _rank_io(ctx, targets, u_start, u_stop, excl, cand, pos)
+    fn = "el_dense_rank" if dtype == torch.float32 else "el_dense_rank_f64"
+    check(getattr(ctx.lib, fn)(ctx.handle, ctx.stream(), _ptr(preds, dtype, "preds"), int(preds.stride(0)), int(u_start), int(u_stop),
+                               int(preds.shape[1] if I is None else I), *tail), fn)
+    return pos
+
+
+def dense_rank(ctx, preds, u_start, u_stop, targets, excl=None, cand=None, pos=None, I=None):
+    """score_rank over a materialised float32 [n_users, I] block: the order of dense_topk."""
+    return _dense_rank(ctx, preds, torch.float32, u_start, u_stop, targets, excl, cand, pos, I)
+
+
+def dense_rank_f64(ctx, preds, u_start, u_stop, targets, excl=None, cand=None, pos=None, I=None):
+    """score_rank over a float64 block: the order of dense_topk_f64."""
+    return _dense_rank(ctx, preds, torch.float64, u_start, u_stop, targets, excl, cand, pos, I)
+
+
+def mask_kwargs(mask):
+    """The tagged mask of the models' recommend() / rank() (("excl" | "cand", DeviceCSR) or None) as excl= / cand= arguments."""
+    kind, csr = mask if mask is not None else (None, None)
+    return {"excl": csr if kind == "excl" else None, "cand": csr if kind == "cand" else None}
+
+
+def rank_metrics(ctx, pos, test, threshold, train, n_items, cutoff, u_start=0, u_stop=None, sums=None, per_user=False):
+    """The six sums of the rank metrics (RANK_SUMS; include/elliot_hip.h lists the slots) of users [u_start, u_stop) from the
+    positions of their held-out entries (score_rank and its kin on `test`): float64[6] on the device, ADDED to `sums` when
+    given.  train: the DeviceCSR whose row lengths are len(train_dict[u])."""
+    u_stop = test.n_rows if u_stop is None else int(u_stop)
+    n = u_stop - int(u_start)
+    if sums is None:
+        sums = torch.zeros(RANK_SUMS, dtype=torch.float64, device=ctx.device)
+    rows = torch.empty((n, 4), dtype=torch.float64, device=ctx.device) if per_user else None
+    ws = workspace(ctx, "_rank_metrics_ws", max(int(ctx.lib.el_rank_metrics_ws_bytes(int(n))), 8), ctx.device)
+    check(ctx.lib.el_rank_metrics(ctx.handle, ctx.stream(), C.c_void_p(pos.data_ptr()) if pos.numel() else _ptr(test.indices), int(u_start),
+                                  u_stop, _ptr(test.indptr, torch.int64), _ptr(test.indices, torch.int32),
+                                  _ptr(test.ratings, torch.float32), float(threshold), _ptr(train.indptr, torch.int64), int(n_items),
+                                  int(cutoff), C.c_void_p(sums.data_ptr()), C.c_void_p(rows.data_ptr()) if rows is not None else None,
+                                  C.c_void_p(ws.data_ptr()), int(ws.numel())), "el_rank_metrics")
     return (sums, rows) if per_user else sums
 
 

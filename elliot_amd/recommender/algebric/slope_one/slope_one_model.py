@@ -30,6 +30,10 @@ class SlopeOneModel(object):
     def recommend(self, mask, k, start, stop):
         return self.state.recommend(mask, k, start, stop)
 
+    def rank(self, mask, targets, start, stop):
+        """Positions of the entries of rows [start, stop) of `targets` in the order recommend() selects by."""
+        return self.state.rank(mask, targets, start, stop)
+
     def get_model_state(self):
         """The reference's keys and types: freq and dev float64 [I, I] arrays (dev with -0.0 below the diagonal wherever +0.0
         stands above it), user_mean a list of np.float64."""

@@ -41,6 +41,10 @@ class EaseModel(object):
     def recommend(self, mask, k, start, stop):
         return self.state.recommend(mask, k, start, stop)
 
+    def rank(self, mask, targets, start, stop):
+        """Positions of the entries of rows [start, stop) of `targets` in the order recommend() selects by."""
+        return self.state.rank(mask, targets, start, stop)
+
     def get_model_state(self):
         return {"B": self.state.B.cpu().numpy(), "l2_norm": self._l2_norm, "neighborhood": self._neighborhood}
 

@@ -81,6 +81,12 @@ class VariationalAutoEncoder:
         return ops.dense_topk(self.ctx, preds, start, stop, k, excl=csr if kind == "excl" else None,
                               cand=csr if kind == "cand" else None)
 
+    def rank(self, mask, targets, start, stop):
+        """Positions of the entries of rows [start, stop) of `targets` in the full rankings of predict(start, stop)
+        (el_dense_rank)."""
+        preds = self.predict(start, stop)
+        return ops.dense_rank(self.ctx, preds, start, stop, targets, **ops.mask_kwargs(mask))
+
     def save_weights(self, path):
         with open(path, "wb") as f:
             pickle.dump(self.state.weights(), f)

@@ -31,6 +31,11 @@ _META_FIELDS = (
 )
 
 
+# the models whose recommend() is one call on their own tables or score blocks and that carry the matching rank()
+RANK_MODELS = frozenset(("BPRMF_batch", "LightGCN", "NGCF", "PureSVD", "BPRMF", "MF2020", "iALS", "WRMF", "MultiVAE", "MultiDAE",
+                         "EASER", "SlopeOne", "BPRSlim"))
+
+
 def param(key, short, default, read=None, show=None, attr=None):
     """One entry of a model's `_params_list`: (attribute, YAML key, file-name shortcut, default, reader, printer)."""
     return (attr or "_" + key, key, short, default, read, show)
@@ -78,6 +83,17 @@ class BaseRecommenderModel(ABC):
         if k not in cutoffs:
             raise Exception("Validation cutoff must be in general cutoff values")
         return name, k
+
+    def _check_rank_metrics(self):
+        """AUC / GAUC / LAUC (stand-alone evaluator, evaluation.rank_metrics: True) need the model's rank(): wired for the
+        models in RANK_MODELS, on one device, with the metrics computed on the device."""
+        model = type(self).__name__
+        if model not in RANK_MODELS or not hasattr(getattr(self, "_model", None), "rank"):
+            raise Exception(f"{model} cannot evaluate AUC, GAUC, LAUC: they need the positions of the held-out items in the complete "
+                            f"ranking, and rank() is wired for {sorted(RANK_MODELS)} only")
+        if not getattr(self._config, "device_metrics", True):
+            raise Exception(f"{model}: AUC, GAUC, LAUC are computed on the device; `device_metrics: False` cannot be combined with "
+                            f"`evaluation.rank_metrics: True`")
 
     # -- names of result / weight files ---------------------------------------------------------------------------
     def get_base_params_shortcut(self):
@@ -144,6 +160,8 @@ def init_charger(init):
         init(self, *args, **kwargs)
 
         self.evaluator = _compat.Evaluator(self._data, self._params)
+        if getattr(self.evaluator, "rank_metrics", False):
+            self._check_rank_metrics()
         self._params.name = self.name
         weights_root = self._config.path_output_rec_weight
         _compat.build_model_folder(weights_root, self.name)

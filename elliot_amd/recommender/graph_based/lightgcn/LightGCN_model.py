@@ -75,6 +75,11 @@ class LightGCNModel:
         return ops.score_topk(self.ctx, st.Gu, st.Gi, None, start, stop, k, excl=csr if kind == "excl" else None,
                               cand=csr if kind == "cand" else None, item_offset=item_offset, items_unchanged=same)
 
+    def rank(self, mask, targets, start, stop):
+        """Positions of the entries of rows [start, stop) of `targets` in the order recommend() selects by (el_score_rank)."""
+        st = self.state
+        return ops.score_rank(self.ctx, st.Gu, st.Gi, None, start, stop, targets, **ops.mask_kwargs(mask))
+
     def get_top_k(self, predictions, train_mask, k=100):
         kind, csr = train_mask
         idx, val = ops.dense_topk(self.ctx, predictions, 0, predictions.shape[0], k, excl=csr if kind == "excl" else None,

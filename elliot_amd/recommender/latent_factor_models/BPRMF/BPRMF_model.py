@@ -67,6 +67,11 @@ class MFModel(object):
                                   excl=csr if kind == "excl" else None, cand=csr if kind == "cand" else None,
                                   item_offset=item_offset)
 
+    def rank(self, mask, targets, start, stop):
+        """Positions of the entries of rows [start, stop) of `targets` in the order recommend() selects by (el_score_rank_f64)."""
+        st = self.state
+        return ops.score_rank_f64(self.ctx, st.P, st.Q, st.b, start, stop, targets, **ops.mask_kwargs(mask))
+
     def get_model_state(self):                                        # :119-125
         st = self.state
         return {"_user_bias": np.zeros(len(self._users)), "_item_bias": st.b.cpu().numpy(),

@@ -93,6 +93,12 @@ class BPRMF_batch_model:
                               excl=csr if kind == "excl" else None, cand=csr if kind == "cand" else None,
                               item_offset=item_offset, items_unchanged=same_items)
 
+    def rank(self, mask, targets, start, stop):
+        """Positions of the entries of rows [start, stop) of `targets` (device CSR) in the users' full rankings, in the order
+        recommend() selects by (el_score_rank): int32 on the device."""
+        st = self.state
+        return ops.score_rank(self.ctx, st.Gu, st.Gi, st.Bi, start, stop, targets, **ops.mask_kwargs(mask))
+
     def get_top_k(self, predictions, train_mask, k=100):
         """get_top_k (:87-88) on a materialised [n, I] block (compatibility path)."""
         kind, csr = train_mask

@@ -36,6 +36,10 @@ class BPRSlimModel(object):
     def recommend(self, mask, k, start, stop):
         return self.state.recommend(mask, k, start, stop)
 
+    def rank(self, mask, targets, start, stop):
+        """Positions of the entries of rows [start, stop) of `targets` in the order recommend() selects by."""
+        return self.state.rank(mask, targets, start, stop)
+
     def get_model_state(self):
         """The reference's one key: `_s_dense`, a float64 [I, I] ndarray."""
         return {"_s_dense": self.state.S.cpu().numpy()}

@@ -44,6 +44,12 @@ class MFModel:
                                       cand=csr if kind == "cand" else None, item_offset=item_offset)
         return idx, val + st.bu[start:stop, None]          # (the user bias shifts a user's whole row: it does not change the order)
 
+    def rank(self, mask, targets, start, stop):
+        """Positions of the entries of rows [start, stop) of `targets` in the order recommend() selects by (el_score_rank_f64;
+        the user bias does not enter the order)."""
+        st = self.state
+        return ops.score_rank_f64(self.ctx, st.P, st.Q, st.gb + st.bi, start, stop, targets, **ops.mask_kwargs(mask))
+
     def get_model_state(self):
         st = self.state
         return {"_global_bias": float(st.gb.item()), "_user_bias": st.bu.cpu().numpy(), "_item_bias": st.bi.cpu().numpy(),

@@ -30,6 +30,10 @@ class PureSVDModel(object):
         """Top-k of users [start, stop) under the tagged mask ("excl" | "cand", DeviceCSR): (idx, val) [n, k] on the device."""
         return self.state.recommend(mask, k, start, stop)
 
+    def rank(self, mask, targets, start, stop):
+        """Positions of the entries of rows [start, stop) of `targets` in the order recommend() selects by."""
+        return self.state.rank(mask, targets, start, stop)
+
     def _tables(self):
         if self._host_tables is None:
             self._host_tables = (self.state.user_vec.cpu().numpy(), self.state.item_vec.cpu().numpy())

@@ -85,6 +85,10 @@ class AlsModel(object):
     def recommend(self, mask, k, start, stop):
         return self.state.recommend(mask, k, start, stop)
 
+    def rank(self, mask, targets, start, stop):
+        """Positions of the entries of rows [start, stop) of `targets` in the order recommend() selects by."""
+        return self.state.rank(mask, targets, start, stop)
+
     def confidence_matrix(self):
         C = sp.csr_matrix(self._data.sp_i_train, dtype=np.float32, copy=True)
         C.data[:] = self._c

@@ -46,7 +46,13 @@ class RecMixin(object):
             return
         needed = self.evaluator.get_needed_recommendations()
         recs = None
-        if self._device_metrics():
+        if self._rank_metrics():
+            # the positions of the held-out items come from the model's rank(), never from the lists: the metrics of this
+            # evaluation are the device route's, the dicts are built only to be written
+            outcome = self._evaluate_on_device(needed)
+            if self._save_recs:
+                recs = self.get_recommendations(needed)
+        elif self._device_metrics():
             outcome = self._evaluate_on_device(needed)
         else:
             recs = self.get_recommendations(needed)
@@ -85,20 +91,36 @@ class RecMixin(object):
                 and getattr(self._config, "device_metrics", True) and hasattr(self, "_model")
                 and hasattr(self._model, "recommend"))
 
+    def _rank_metrics(self):
+        """True when AUC / GAUC / LAUC are asked of the stand-alone evaluator (evaluation.rank_metrics: True)."""
+        return bool(getattr(self.evaluator, "rank_metrics", False))
+
     def _evaluate_on_device(self, k):
+        sets = self.evaluator.device_sets(self._data, self._model.ctx.device) if self._rank_metrics() else None
+
+        def with_ranks(offset, stop, idx_v, idx_t, mask_v, mask_t):
+            """The block and, with rank metrics on, the positions of its held-out entries under the same candidate masks."""
+            if sets is None:
+                return offset, idx_v, idx_t
+            pos_v = self._model.rank(mask_v, sets["val"], offset, stop) if sets["val"] is not None else None
+            return offset, idx_v, idx_t, pos_v, self._model.rank(mask_t, sets["test"], offset, stop)
+
         def blocks():
             block = self._recommendation_block()
             for offset in range(0, self._num_users, block):
                 stop = min(offset + block, self._num_users)
                 if not self._negative_sampling:
-                    idx, _ = self._model.recommend(self.get_candidate_mask(), k, offset, stop)
-                    yield offset, idx, idx
+                    mask = self.get_candidate_mask()
+                    idx, _ = self._model.recommend(mask, k, offset, stop)
+                    yield with_ranks(offset, stop, idx, idx, mask, mask)
                 else:
-                    idx_t, _ = self._model.recommend(self.get_candidate_mask(), k, offset, stop)
+                    mask_t = mask_v = self.get_candidate_mask()
+                    idx_t, _ = self._model.recommend(mask_t, k, offset, stop)
                     idx_v = idx_t
                     if hasattr(self._data, "val_dict"):
-                        idx_v, _ = self._model.recommend(self.get_candidate_mask(validation=True), k, offset, stop)
-                    yield offset, idx_v, idx_t
+                        mask_v = self.get_candidate_mask(validation=True)
+                        idx_v, _ = self._model.recommend(mask_v, k, offset, stop)
+                    yield with_ranks(offset, stop, idx_v, idx_t, mask_v, mask_t)
         return self.evaluator.eval_device(self._model.ctx, self._data, blocks())
 
     # -- scoring -------------------------------------------------------------------------------------

@@ -1261,6 +1261,50 @@ int el_rec_metrics(el_ctx* ctx, void* stream, const int32_t* rec_idx, int64_t ld
                    double threshold, int32_t cutoff, const double* discount, double* sums, double* per_user,
                    void* ws, size_t ws_bytes);
 
+/* ---- rank metrics: positions of held-out items in the full ranking, AUC / GAUC / LAUC sums (el_rank.hip) ----
+ * Replaces: the full-length lists an Evaluator with AUC / GAUC asks for (evaluation/evaluator.py:149-159) and the metric
+ * classes that read ranks off them (metrics/accuracy/AUC/{auc,gauc,lauc}.py).
+ * el_score_rank / el_score_rank_f64 / el_dense_rank / el_dense_rank_f64 take the scores, masks and CSR conventions of
+ * el_score_topk / el_score_topk_f64 / el_dense_topk / el_dense_topk_f64 (no item shard: the whole catalogue [0, I)) and,
+ * instead of a list, the target CSR (rows = absolute user ids, ids ascending, ids >= I allowed: DeviceTestSet's).
+ *   pos   device int32, one entry per target entry of rows [u_start, u_stop), at pos[e - tgt_indptr[u_start]]:
+ *         #{ j in [0, I), j != t, j admissible for u : key(u, j) ranks ahead of key(u, t) } -- the index of t in the list the
+ *         top-k kernels would produce at k = I; -1 for a target with id >= I or one the mask removes
+ *   algo  (el_score_rank) EL_TOPK_SIMPLE: the wave-per-user kernel (any F, both mask protocols; the route of the other three
+ *         entry points); EL_TOPK_MFMA: fp32 scores on the matrix cores, 128 users per workgroup (F <= 256, no candidate list,
+ *         needs ws of el_score_rank_ws_bytes; users with more than 63 targets take the wave kernel through a device-side
+ *         list); EL_TOPK_AUTO: MFMA where eligible and ws is given, else SIMPLE.  Both routes write the same bytes.
+ * A half-given CSR or a null pos is refused before anything launches.  NaN scores are outside the contract.  Integer
+ * atomics only: the same input gives the same bytes.                                                                    */
+size_t el_score_rank_ws_bytes(int64_t n_users, int64_t I, int32_t F, int64_t tgt_nnz, int64_t excl_nnz, int algo);
+int el_score_rank(el_ctx* ctx, void* stream, const float* Gu, const float* Gi, const float* Bi, int64_t u_start, int64_t u_stop,
+                  int64_t I, int32_t F, const int64_t* excl_indptr, const int32_t* excl_indices,
+                  const int64_t* cand_indptr, const int32_t* cand_indices,
+                  const int64_t* tgt_indptr, const int32_t* tgt_indices, int32_t* pos, int algo, void* ws, size_t ws_bytes);
+int el_score_rank_f64(el_ctx* ctx, void* stream, const double* P, const double* Q, const double* b, int64_t u_start, int64_t u_stop,
+                      int64_t I, int32_t F, const int64_t* excl_indptr, const int32_t* excl_indices,
+                      const int64_t* cand_indptr, const int32_t* cand_indices,
+                      const int64_t* tgt_indptr, const int32_t* tgt_indices, int32_t* pos);
+int el_dense_rank(el_ctx* ctx, void* stream, const float* preds, int64_t ld, int64_t u_start, int64_t u_stop, int64_t I,
+                  const int64_t* excl_indptr, const int32_t* excl_indices, const int64_t* cand_indptr, const int32_t* cand_indices,
+                  const int64_t* tgt_indptr, const int32_t* tgt_indices, int32_t* pos);
+int el_dense_rank_f64(el_ctx* ctx, void* stream, const double* preds, int64_t ld, int64_t u_start, int64_t u_stop, int64_t I,
+                      const int64_t* excl_indptr, const int32_t* excl_indices, const int64_t* cand_indptr, const int32_t* cand_indices,
+                      const int64_t* tgt_indptr, const int32_t* tgt_indices, int32_t* pos);
+
+/* The six sums of the rank metrics from those positions; pos laid out as above for rows [u_start, u_stop) of the test CSR.
+ *   sums      device double[6], ADDED to: 0 sum of S_u (AUC numerator), 1 sum of m_u (AUC count, exact), 2 sum of S_u / |rel_u|
+ *             (GAUC), 3 sum of S_u^c / min(cutoff, |rel_u|) (LAUC), 4 users with >= 1 relevant item, 5 users with neg_u <= 0
+ *             (they add to slot 5 alone; the reference divides by zero there)
+ *             S_u = (m neg - sum pos + m (m - 1) / 2) / neg over the relevant entries with pos >= 0, S_u^c over 0 <= pos < cutoff,
+ *             neg_u = n_items - train_len_u - |rel_u| + 1, |rel_u| counting relevant ids >= n_items too
+ *   per_user  optional device double[(u_stop-u_start), 4]: S_u, m_u, the GAUC term, the LAUC term
+ * test_ratings may be null (every entry relevant at rating 1).  Fixed-shape reduction (run-to-run identical).            */
+size_t el_rank_metrics_ws_bytes(int64_t n_users);
+int el_rank_metrics(el_ctx* ctx, void* stream, const int32_t* pos, int64_t u_start, int64_t u_stop, const int64_t* test_indptr,
+                    const int32_t* test_indices, const float* test_ratings, double threshold, const int64_t* train_indptr,
+                    int64_t n_items, int32_t cutoff, double* sums, double* per_user, void* ws, size_t ws_bytes);
+
 /* ---- beyond-accuracy metrics from the top-k index tensor -------------------------------
  * Replaces: the coverage / diversity / novelty / bias metric classes behind Evaluator._process_test_data
  * (evaluation/evaluator.py:117-147): metrics/coverage/{item_coverage,user_coverage,num_retrieved},
