@@ -225,6 +225,17 @@ PROTOTYPES = {
     "el_beyond_hist_finish": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, C.c_int64, _i64p, _f64p, C.c_void_p, C.c_size_t]),
     "el_beyond_entropy": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, C.c_int64, C.c_int64, C.c_int64, _i64p, C.c_int32, C.c_int64,
                                     _f64p, _f64p, C.c_void_p, C.c_size_t]),
+    "el_fair_metrics": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, _f32p, C.c_int64, C.c_int64, C.c_int64, _i64p, _i32p, _f32p,
+                                  C.c_double, C.c_int32, _i64p, _i32p, C.c_int64, _i32p, C.c_int32, _i64p, _i32p, C.c_int32, _f64p,
+                                  _i64p, _i64p, _i32p, _f64p, _i32p, _f32p, _i32p]),
+    "el_group_counts": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, C.c_int64, C.c_int64, _i32p, C.c_int32, _i32p, C.c_int32,
+                                  _i64p]),
+    "el_group_sums_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "el_group_sums": (C.c_int, [C.c_void_p, C.c_void_p, _f64p, C.c_int32, _i32p, C.c_int64, C.c_int32, _f64p, _i64p, C.c_void_p,
+                                C.c_size_t]),
+    "el_fair_item_finish_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "el_fair_item_finish": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i64p, _f32p, C.c_double, _i32p, _f32p, _i32p, C.c_int64, _i32p,
+                                      C.c_int32, _f64p, _i64p, _f64p, C.c_void_p, C.c_size_t]),
     "el_score_topk_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int]),
     "el_topk_screen_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "el_score_topk": (C.c_int, [C.c_void_p, C.c_void_p, _f32p, _f32p, _f32p, C.c_int64, C.c_int64, C.c_int64,

@@ -29,12 +29,12 @@
 // 0.29 / 0.28 / 0.24 ms on uniform / Zipf / identical lists, direct 0.20 / 1.11 / 1.56 ms -- the default is the aggregated form.
 #include "el_common.h"
 #include "el_metrics_tree.h"
+#include "el_metrics_hist.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
 #define BEY_N 18
 #define BEY_MAXCUT 512
-#define BEY_TILE 2048
 
 struct BeyArgs {
     const int32_t* rec;
@@ -165,59 +165,6 @@ __global__ __launch_bounds__(256) void k_beyond_users(BeyArgs a) {
     }
 }
 
-// the lists of the users of A into the histogram, one add per distinct id of a tile of BEY_TILE list entries
-__global__ __launch_bounds__(256) void k_beyond_hist(const int32_t* __restrict__ rec, int64_t ld, int64_t u_start, int64_t n,
-                                                     const int64_t* __restrict__ tp, int cutoff, int32_t I, int32_t* __restrict__ hist) {
-    __shared__ u32 key[BEY_TILE];
-    const int64_t e0 = (int64_t)blockIdx.x * BEY_TILE, total = n * cutoff;
-    const int64_t row0 = e0 / cutoff;
-    const u32 rem0 = (u32)(e0 - row0 * cutoff);
-    for (int t = threadIdx.x; t < BEY_TILE; t += 256) {
-        u32 k = 0xffffffffu;
-        if (e0 + t < total) {
-            const u32 x = rem0 + (u32)t;
-            const int64_t row = row0 + x / (u32)cutoff;
-            const u32 col = x % (u32)cutoff;
-            const int64_t user = u_start + row;
-            if (tp[user + 1] > tp[user]) {
-                const int32_t item = rec[row * ld + col];
-                if (item >= 0 && item < I) k = (u32)item;
-            }
-        }
-        key[t] = k;
-    }
-    __syncthreads();
-    for (int size = 2; size <= BEY_TILE; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = threadIdx.x; t < (BEY_TILE >> 1); t += 256) {
-                const int i = 2 * t - (t & (stride - 1));
-                const int j = i + stride;
-                const bool asc = ((i & size) == 0);
-                const u32 x = key[i], y = key[j];
-                if (asc ? (x > y) : (x < y)) {
-                    key[i] = y;
-                    key[j] = x;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (int t = threadIdx.x; t < BEY_TILE; t += 256) {
-        const u32 k = key[t];
-        if (k != 0xffffffffu && (t == 0 || key[t - 1] != k)) {
-            int lo = t + 1, hi = BEY_TILE;                    // first position behind the run of k
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (key[mid] <= k)
-                    lo = mid + 1;
-                else
-                    hi = mid;
-            }
-            atomicAdd(hist + k, lo - t);
-        }
-    }
-}
-
 // stats[0] += #non-zero counts, stats[1] += sum of the counts, stats[2] += sum_p (2p + 1 - I) sorted[p]   (64-bit integer adds)
 __global__ __launch_bounds__(256) void k_beyond_hist_stats(const u32* __restrict__ sorted, int64_t I, unsigned long long* __restrict__ stats) {
     __shared__ long long sh[3][256];
@@ -342,8 +289,8 @@ extern "C" int el_beyond_metrics(el_ctx* ctx, void* stream, const int32_t* rec_i
     } else {
         EL_LAUNCH("k_beyond_users", (k_beyond_users<false>), grid, dim3(256), 0, st, a);
         const int64_t tiles = (n * cutoff + BEY_TILE - 1) / BEY_TILE;
-        EL_LAUNCH("k_beyond_hist", k_beyond_hist, dim3((unsigned)tiles), dim3(256), 0, st, rec_idx, ld, u_start, n, test_indptr, (int)cutoff,
-                  (int32_t)n_items, hist);
+        EL_LAUNCH("k_beyond_hist", k_beyond_hist<false>, dim3((unsigned)tiles), dim3(256), 0, st, rec_idx, ld, u_start, n, test_indptr,
+                  (const double*)nullptr, 0, (int)cutoff, (int32_t)n_items, hist);
     }
     met_tree_sum<BEY_N, -1>(st, a.rows, n, m.part, sums);
     EL_CHECK_LAUNCH();

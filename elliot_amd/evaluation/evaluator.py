@@ -11,8 +11,12 @@ Definitions follow the reference:
   HR, MAP, MRR, F1   hit_rate.py:66, map.py:69-80, mrr.py:63-70, f1.py:56-68
   averaging          over users that have recommendations AND >= 1 relevant test item (ndcg.py:124-125)
 Computation is vectorised over an [n_users, k] item matrix instead of per-user Python loops.  The remaining
-metrics of the reference (nDCGRendle2020, MAR, DSC, the rating-error metrics, fairness and the other complex_metrics, paired
-tests) are out of scope here; inside an Elliot process the genuine Evaluator is used instead (recommender/_compat.py).
+metrics of the reference (nDCGRendle2020, MAR, DSC, the rating-error metrics, paired tests) are out of scope here; inside an
+Elliot process the genuine Evaluator is used instead (recommender/_compat.py).
+
+`evaluation.complex_metrics` holds the fairness family (RSP, REO, BiasDisparityBS / BR / BD, the four MADs: evaluation/fairness.py)
+with the reference's keys; their values follow the simple metrics in configuration order under the reference's names.  The
+validation metric reads simple_metrics only, as in the reference.
 
 AUC, GAUC and LAUC (evaluation/ranks.py) are accepted only with `evaluation.rank_metrics: True`: they need the position of
 every held-out item in the user's complete ranking, which costs one more full-catalogue pass per evaluation (el_rank.hip)
@@ -22,15 +26,30 @@ from the models' rank() (eval_device) or from the caller (eval(recs, ranks=...))
 The accuracy metrics average over the users with >= 1 relevant held-out item; the beyond-accuracy metrics see every
 user whose held-out row is non-empty (evaluator.py:121) and average over either population, as their classes do.
 """
+import logging
 import math
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
 
-from . import beyond, ranks
+from . import beyond, fairness, ranks
 
 ACCURACY = ("nDCG", "Precision", "Recall", "HR", "MAP", "MRR", "F1")
 SUPPORTED = ACCURACY + beyond.NAMES
+
+
+class EvalBlock(namedtuple("EvalBlock", "first idx_val idx_test pos_val pos_test val_val val_test", defaults=(None,) * 4)):
+    """One block of eval_device: the [n, k] index tensors of users first ..., optionally the positions of the held-out entries
+    (rank metrics) and the fp32 score tensors of the lists (UserMADrating / ItemMADrating)."""
+    __slots__ = ()
+
+
+def _block_fields(block):
+    """(first, idx_val, idx_test, pos_val, pos_test, val_val, val_test) of an EvalBlock or of a plain tuple of 3 or 5."""
+    if isinstance(block, EvalBlock):
+        return tuple(block)
+    return tuple(block[:5]) + (None,) * (7 - min(len(block), 5))
 
 
 def _canon(name, rank_metrics=False):
@@ -68,6 +87,10 @@ class Evaluator:
         self.rank_metrics = bool(self._rank)      # RecMixin: evaluate on the device and hand eval_device positions
         self._accuracy = [m for m in self._metrics if m in ACCURACY]
         self._beyond = [m for m in self._metrics if m in beyond.NAMES]
+        complex_metrics = getattr(cfg.evaluation, "complex_metrics", None) or []
+        self._fair = fairness.Plan(complex_metrics, data) if complex_metrics else None     # raises on an unknown complex metric
+        self.needs_scores = bool(self._fair and self._fair.needs_scores)      # RecMixin: hand eval_device the lists' scores
+        self._fair_bs, self._fair_dev, self._fair_warned = {}, None, False
         self._item_tables = None
         self._host_csr = {}
         self._dict_splits = None          # the dict-based form is only built when eval() is handed recommendation dicts
@@ -155,7 +178,13 @@ class Evaluator:
         """blocks: iterable of (first_private_user, idx_val, idx_test) with [n, k] int32 device tensors (idx_val may be
         the same tensor), or (first, idx_val, idx_test, pos_val, pos_test) where pos_* are the int32 positions of the block's
         held-out entries (the models' rank() on device_sets()["val" | "test"]; pos_val None without a validation split).
+        An EvalBlock carries the same fields by name and, optionally, val_val / val_test: the float score tensors of the lists,
+        required when UserMADrating / ItemMADrating are configured.
         Returns the same structure as eval().  AUC and GAUC do not depend on the cutoff; LAUC does.
+
+        With complex_metrics, el_fair_metrics + el_group_sums run per block and (pass, split, cutoff) into integer tables, the
+        hit arrays of the held-out entries (8 bytes per entry) and the histogram of the lists of R (4 bytes per item);
+        el_fair_item_finish runs after the last block ("Fairness metrics").
 
         The accuracy kernel runs as before.  When a beyond-accuracy metric is asked for, el_beyond_metrics runs beside it
         into one item histogram (int32[num_items]) and one row of sums per (split, cutoff); the histograms are finished
@@ -182,14 +211,25 @@ class Evaluator:
             rank_train = device_masks(data, ctx).train
             rnk = {key: torch.zeros(ops.RANK_SUMS, dtype=torch.float64, device=ctx.device) for key in keys}
         kept = {"val": [], "test": []} if "SEntropy" in self._beyond else None
+        fair = self._fair_device(ctx, data, sets, keys) if self._fair else None
         for block in blocks:
-            first, idx_val, idx_test = block[:3]
-            if rnk is not None and len(block) < 5:
+            first, idx_val, idx_test, pos_val, pos_test, sc_val, sc_test = _block_fields(block)
+            if rnk is not None and pos_test is None:
                 raise Exception(f"{self._rank} need the positions of the held-out items: blocks of (first, idx_val, idx_test, pos_val, pos_test)")
+            if self.needs_scores and (sc_test is None or (sets["val"] is not None and sc_val is None)):
+                raise Exception("UserMADrating / ItemMADrating need the scores of the lists: blocks of EvalBlock(first, idx_val, idx_test, "
+                                "val_val=..., val_test=...)")
             for sp, c in keys:
                 idx = idx_val if sp == "val" else idx_test
+                if fair is not None:
+                    sc = (sc_val if sp == "val" else sc_test) if self.needs_scores else None
+                    if sc is not None and sc.dtype != torch.float32:
+                        sc = sc.float()                       # the kernels read fp32 scores (fp64 scorers: rounded once, here)
+                    for (items, users), state in zip(fair["groups"], fair["state"][(sp, c)]):
+                        ops.fair_metrics(ctx, idx, sc, sets[sp], fair["train"], items, users, self._rel_threshold, c, data.num_items,
+                                         state, u_start=first)
                 if rnk is not None:
-                    pos = block[3] if sp == "val" else block[4]
+                    pos = pos_val if sp == "val" else pos_test
                     ops.rank_metrics(ctx, pos, sets[sp], self._rel_threshold, rank_train, data.num_items, c, u_start=first,
                                      u_stop=first + idx.shape[0], sums=rnk[(sp, c)])
                 if self._accuracy:
@@ -210,6 +250,12 @@ class Evaluator:
                     for first, idx in kept[sp]:
                         ops.beyond_entropy(ctx, idx, sets[sp], nov, c, u_start=first, total=ent)
                 extra[(sp, c)] = (sums.cpu().numpy(), stats.cpu().numpy(), float(ent.cpu()[0]))
+        fair_terms = {}
+        if fair is not None:
+            for key, states in fair["state"].items():
+                for (items, _), state in zip(fair["groups"], states):
+                    ops.fair_item_finish(ctx, sets[key[0]], fair["cols"][key[0]], items, self._rel_threshold, state)
+                fair_terms[key] = [state.host_terms() for state in states]
         host = {key: v.cpu().numpy() for key, v in acc.items()}
         rank_host = {key: v.cpu().numpy() for key, v in rnk.items()} if rnk is not None else None
 
@@ -229,7 +275,10 @@ class Evaluator:
                 if sums[0] == 0:
                     return {}
                 out.update(beyond.finish(self._beyond, sums, int(stats[0]), int(stats[1]), int(stats[2]), ent, data.num_items))
-            return {m: out[m] for m in self._metrics}
+            out = {m: out[m] for m in self._metrics}
+            if self._fair:
+                out.update(fairness.finish(self._fair, fair_terms[(sp, c)], self._fair_bs))
+            return out
 
         res = {}
         for c in self._k:
@@ -256,7 +305,10 @@ class Evaluator:
             if not more:
                 return {}
             out.update(more)
-        return {m: out[m] for m in self._metrics}
+        out = {m: out[m] for m in self._metrics}
+        if self._fair:
+            out.update(self._eval_fair(recs, cutoff, validation))
+        return out
 
     def _host_split_csr(self, validation):
         if validation not in self._host_csr:
@@ -295,6 +347,67 @@ class Evaluator:
             return {}
         n, free, G = beyond.gini_numerator(hist, data.num_items)
         return beyond.finish(self._beyond, sums, n, free, G, ent, data.num_items)
+
+    # ---- fairness metrics (evaluation.complex_metrics, fairness.py) ---------------------------------------------------------------
+    def _fair_warn(self):
+        """Held-out items the model has no row for (private ids >= num_items) belong to no item group on either route; the
+        reference would count them in REO's denominator if the clustering file lists them.  Logged once, with their number."""
+        if self._fair_warned:
+            return
+        self._fair_warned = True
+        n = 0
+        for validation in (False, True):
+            split = self._host_split_csr(validation) if not validation or self._test_dict_raw(self._data, True) else None
+            if split is not None:
+                n += int((np.asarray(split[1]) >= self._data.num_items).sum())
+        if n:
+            logging.getLogger(__name__).warning(f"fairness metrics: {n} held-out entries are items without a train interaction; they "
+                                                f"belong to no item group (REO's denominator leaves them out)")
+
+    def _host_train_csr(self):
+        train = self._data.sp_i_train.tocsr()
+        train.sort_indices()
+        return train.indptr.astype(np.int64), train.indices
+
+    def _eval_fair(self, recs, cutoff, validation):
+        """The complex metrics of one split from the recommendation dicts, in NumPy (fairness.numpy_terms)."""
+        data = self._data
+        self._fair_warn()
+        pu, pi = data.public_users, data.public_items
+        users = [u for u in recs if u in pu]
+        lists = np.full((len(users), cutoff), -1, dtype=np.int64)
+        scores = np.zeros((len(users), cutoff), dtype=np.float64)
+        for r, u in enumerate(users):
+            row = recs[u][:cutoff]
+            lists[r, :len(row)] = [pi.get(item, -1) for item, _ in row]
+            scores[r, :len(row)] = [score for _, score in row]
+        train = self._host_train_csr()
+        for n_pass in self._fair.needs_bs:
+            if n_pass not in self._fair_bs:
+                self._fair_bs[n_pass] = fairness.bs_counts(train, *self._fair.passes[n_pass])
+        rows = np.array([pu[u] for u in users], dtype=np.int64)
+        terms = [fairness.numpy_terms(lists, scores, rows, self._host_split_csr(validation), self._rel_threshold, train, ig, ug, cutoff,
+                                      data.num_items) for ig, ug in self._fair.passes]
+        return fairness.finish(self._fair, terms, self._fair_bs)
+
+    def _fair_device(self, ctx, data, sets, keys):
+        """Device copies of the groupings, the train CSR and the item-major held-out sets (built once), BiasDisparityBS's counts
+        (once per data set) and fresh accumulators per (split, cutoff, pass)."""
+        from .. import ops
+        from ..recommender.masks import device_masks
+        self._fair_warn()
+        dev = self._fair_dev
+        if dev is None or dev["device"] != ctx.device:
+            dev = self._fair_dev = {
+                "device": ctx.device, "train": device_masks(data, ctx).train,
+                "groups": [(ops.DeviceGrouping(ig, ctx.device), ops.DeviceGrouping(ug, ctx.device)) for ig, ug in self._fair.passes],
+                "cols": {sp: ops.DeviceTestColumns(*self._host_split_csr(sp == "val")[:2], data.num_items, ctx.device)
+                         for sp in ("val", "test") if sets[sp] is not None}}
+        for n_pass in self._fair.needs_bs:
+            if n_pass not in self._fair_bs:
+                self._fair_bs[n_pass] = ops.group_counts(ctx, dev["train"], data.num_items, *dev["groups"][n_pass]).cpu().numpy()
+        state = {(sp, c): [ops.FairState(ctx, sets[sp], data.num_items, items, users) for items, users in dev["groups"]] for sp, c in keys}
+        return {**dev, "state": state}
 
     def _eval_accuracy(self, recs, split, cutoff):
         users = [u for u in recs if u in split.row]

@@ -1806,6 +1806,134 @@ def beyond_entropy(ctx, rec_idx, test, nov, cutoff, u_start=0, total=None):
     return total
 
 
+# ------------------------------------------------------------------------------------------
+# fairness metrics on the device (el_metrics_fair.hip): RSP, REO, BiasDisparity, the four MADs
+# ------------------------------------------------------------------------------------------
+FAIR_MAX_GROUPS = 64
+FAIR_ROW = 4            # el_fair_metrics' per-user row: nDCG, in R, mean list score, has a score
+
+
+class DeviceGrouping:
+    """A clustering of evaluation/fairness.py::Grouping in HBM: labels int32[n] (-1 = none), sizes int64[n_groups]."""
+
+    def __init__(self, grouping, device):
+        self.host = grouping
+        self.n_groups = int(grouping.n_groups)
+        if not 1 <= self.n_groups <= FAIR_MAX_GROUPS:
+            raise ValueError(f"{self.n_groups} groups: the fairness kernels keep 1..{FAIR_MAX_GROUPS} user groups and item groups")
+        self.labels = torch.from_numpy(np.ascontiguousarray(grouping.labels, dtype=np.int32)).to(device)
+        self.sizes = torch.from_numpy(np.ascontiguousarray(grouping.sizes, dtype=np.int64)).to(device)
+
+
+class DeviceTestColumns:
+    """The item-major copy of a held-out CSR for el_fair_item_finish: col_indptr int64[I + 1], col_entry int64 = the entries'
+    indices in the CSR, users ascending inside a column; entries with an id >= I (no model row) are left out."""
+
+    def __init__(self, indptr, indices, n_items, device):
+        indices = np.asarray(indices, dtype=np.int64)
+        keep = np.flatnonzero(indices < n_items)
+        cols = indices[keep]
+        col_indptr = np.concatenate([[0], np.cumsum(np.bincount(cols, minlength=int(n_items)))]).astype(np.int64)
+        self.indptr = torch.from_numpy(col_indptr).to(device)
+        entry = keep[np.argsort(cols, kind="stable")]           # by item; entries of the CSR run by user, so users ascend
+        self.entry = torch.from_numpy(entry if entry.shape[0] else np.zeros(1, np.int64)).to(device)
+
+
+class FairState:
+    """What one (grouping pair, split, cutoff) accumulates over the blocks: 8 bytes per held-out entry, 4 bytes per item and the
+    group tables."""
+
+    def __init__(self, ctx, test, n_items, items, users):
+        dev, Gi, Gu = ctx.device, items.n_groups, users.n_groups
+        self.item_counts = torch.zeros((4, Gi), dtype=torch.int64, device=dev)
+        self.pair = torch.zeros((Gu, Gi), dtype=torch.int64, device=dev)
+        self.user_sums = torch.zeros((Gu, FAIR_ROW), dtype=torch.float64, device=dev)
+        self.user_cnt = torch.zeros(Gu, dtype=torch.int64, device=dev)
+        self.hit_pos = torch.full((max(test.nnz, 1),), -1, dtype=torch.int32, device=dev)
+        self.hit_score = torch.zeros(max(test.nnz, 1), dtype=torch.float32, device=dev)
+        self.hist = torch.zeros(int(n_items), dtype=torch.int32, device=dev)
+        self.item_sums = torch.zeros((Gi, 2), dtype=torch.float64, device=dev)
+        self.item_cnt = torch.zeros(Gi, dtype=torch.int64, device=dev)
+
+    def host_terms(self):
+        """The layout of evaluation/fairness.py::numpy_terms."""
+        return {"item_counts": self.item_counts.cpu().numpy(), "pair": self.pair.cpu().numpy(), "user_sums": self.user_sums.cpu().numpy(),
+                "item_sums": self.item_sums.cpu().numpy(), "item_cnt": self.item_cnt.cpu().numpy()}
+
+
+def group_sums(ctx, rows, labels, n_groups, sums=None, counts=None):
+    """The rows [n, W <= 4] (float64) summed by label (int32[n], -1 = none) in a shape that depends on n alone: float64
+    [n_groups, W] and the rows per label int64[n_groups], both ADDED to `sums` / `counts` when given."""
+    n, W = rows.shape
+    if sums is None:
+        sums = torch.zeros((n_groups, W), dtype=torch.float64, device=ctx.device)
+    if counts is None:
+        counts = torch.zeros(n_groups, dtype=torch.int64, device=ctx.device)
+    if not 1 <= int(n_groups) <= FAIR_MAX_GROUPS:
+        raise ValueError(f"{n_groups} groups: 1..{FAIR_MAX_GROUPS}")
+    if sums.shape[1] != W:
+        raise ValueError("sums must be [n_groups, W]")
+    ws = workspace(ctx, "_fair_ws", max(int(ctx.lib.el_group_sums_ws_bytes(int(n), int(n_groups))), 8), ctx.device)
+    check(ctx.lib.el_group_sums(ctx.handle, ctx.stream(), _ptr(rows, torch.float64), int(W), _ptr(labels, torch.int32), int(n),
+                                int(n_groups), _ptr(sums, torch.float64), _ptr(counts, torch.int64), C.c_void_p(ws.data_ptr()),
+                                int(ws.numel())), "el_group_sums")
+    return sums, counts
+
+
+def group_counts(ctx, csr, n_items, items, users, counts=None):
+    """int64[user groups, item groups]: the entries of the CSR's rows by (row label, column label), ADDED to `counts` when given
+    (BiasDisparityBS on the train matrix)."""
+    if counts is None:
+        counts = torch.zeros((users.n_groups, items.n_groups), dtype=torch.int64, device=ctx.device)
+    n_rows = int(csr.indptr.shape[0] - 1)
+    if users.labels.shape[0] < n_rows:
+        raise ValueError("user labels must cover the rows")
+    check(ctx.lib.el_group_counts(ctx.handle, ctx.stream(), _ptr(csr.indptr, torch.int64), _ptr(csr.indices, torch.int32), n_rows,
+                                  int(n_items), _ptr(items.labels, torch.int32), items.n_groups, _ptr(users.labels, torch.int32),
+                                  users.n_groups, _ptr(counts, torch.int64)), "el_group_counts")
+    return counts
+
+
+def fair_metrics(ctx, rec_idx, rec_val, test, train, items, users, threshold, cutoff, n_items, state, u_start=0):
+    """The fairness pass over the users of rec_idx's rows (absolute ids u_start ...): integer tables, hit entries and the
+    R-histogram ADDED to `state` (FairState), the per-user rows summed by user label into state.user_sums / user_cnt.
+    rec_val: the float32 scores of the lists or None.  Returns (user_label int32[n], user_rows float64[n, 4])."""
+    n, ld = rec_idx.shape
+    if items.labels.shape[0] < n_items or users.labels.shape[0] < u_start + n:
+        raise ValueError("group labels must cover the items and the users")
+    if rec_val is not None and (rec_val.shape != rec_idx.shape or rec_val.stride(0) != ld):
+        raise ValueError("rec_val must have the layout of rec_idx")
+    label = torch.empty(n, dtype=torch.int32, device=ctx.device)
+    rows = torch.empty((n, FAIR_ROW), dtype=torch.float64, device=ctx.device)
+    disc = discount_table(cutoff, ctx.device)
+    check(ctx.lib.el_fair_metrics(ctx.handle, ctx.stream(), _ptr(rec_idx, torch.int32), _ptr(rec_val, torch.float32) if rec_val is not None
+                                  else None, int(ld), int(u_start), int(u_start + n), _ptr(test.indptr, torch.int64),
+                                  _ptr(test.indices, torch.int32), _ptr(test.ratings, torch.float32), float(threshold), int(cutoff),
+                                  _ptr(train.indptr, torch.int64), _ptr(train.indices, torch.int32), int(n_items),
+                                  _ptr(items.labels, torch.int32), items.n_groups, _ptr(items.sizes, torch.int64),
+                                  _ptr(users.labels, torch.int32), users.n_groups, C.c_void_p(disc.data_ptr()),
+                                  _ptr(state.item_counts, torch.int64), _ptr(state.pair, torch.int64), _ptr(label, torch.int32),
+                                  _ptr(rows, torch.float64), _ptr(state.hit_pos, torch.int32), _ptr(state.hit_score, torch.float32),
+                                  _ptr(state.hist, torch.int32)), "el_fair_metrics")
+    group_sums(ctx, rows, label, users.n_groups, sums=state.user_sums, counts=state.user_cnt)
+    return label, rows
+
+
+def fair_item_finish(ctx, test, cols, items, threshold, state, per_item=False):
+    """After the last block: per item the mean gain / score of its hit entries over the lists of R that hold it (in ascending
+    user order), summed by item label into state.item_sums / item_cnt.  per_item=True also returns float64[I, 2]."""
+    I = int(state.hist.shape[0])
+    rows = torch.empty((I, 2), dtype=torch.float64, device=ctx.device) if per_item else None
+    ws = workspace(ctx, "_fair_ws", max(int(ctx.lib.el_fair_item_finish_ws_bytes(I, items.n_groups)), 8), ctx.device)
+    check(ctx.lib.el_fair_item_finish(ctx.handle, ctx.stream(), _ptr(cols.indptr, torch.int64), _ptr(cols.entry, torch.int64),
+                                      _ptr(test.ratings, torch.float32), float(threshold), _ptr(state.hit_pos, torch.int32),
+                                      _ptr(state.hit_score, torch.float32), _ptr(state.hist, torch.int32), I,
+                                      _ptr(items.labels, torch.int32), items.n_groups, _ptr(state.item_sums, torch.float64),
+                                      _ptr(state.item_cnt, torch.int64), C.c_void_p(rows.data_ptr()) if rows is not None else None,
+                                      C.c_void_p(ws.data_ptr()), int(ws.numel())), "el_fair_item_finish")
+    return rows
+
+
 def topk_screen_stats(ctx):
     """Diagnostics of the last screened score_topk call (el_topk_screen_stats; synchronises): users of the block, records the bf16 pass
     kept for them, users that took the exact fallback."""

@@ -98,12 +98,19 @@ class RecMixin(object):
     def _evaluate_on_device(self, k):
         sets = self.evaluator.device_sets(self._data, self._model.ctx.device) if self._rank_metrics() else None
 
-        def with_ranks(offset, stop, idx_v, idx_t, mask_v, mask_t):
+        # the lists' scores travel with the block only when UserMADrating / ItemMADrating are configured
+        scores = bool(getattr(self.evaluator, "needs_scores", False))
+
+        def with_ranks(offset, stop, idx_v, idx_t, mask_v, mask_t, val_v, val_t):
             """The block and, with rank metrics on, the positions of its held-out entries under the same candidate masks."""
-            if sets is None:
-                return offset, idx_v, idx_t
-            pos_v = self._model.rank(mask_v, sets["val"], offset, stop) if sets["val"] is not None else None
-            return offset, idx_v, idx_t, pos_v, self._model.rank(mask_t, sets["test"], offset, stop)
+            pos_v = pos_t = None
+            if sets is not None:
+                pos_v = self._model.rank(mask_v, sets["val"], offset, stop) if sets["val"] is not None else None
+                pos_t = self._model.rank(mask_t, sets["test"], offset, stop)
+            if scores:
+                from ..evaluation.evaluator import EvalBlock
+                return EvalBlock(offset, idx_v, idx_t, pos_v, pos_t, val_v, val_t)
+            return (offset, idx_v, idx_t) if sets is None else (offset, idx_v, idx_t, pos_v, pos_t)
 
         def blocks():
             block = self._recommendation_block()
@@ -111,16 +118,16 @@ class RecMixin(object):
                 stop = min(offset + block, self._num_users)
                 if not self._negative_sampling:
                     mask = self.get_candidate_mask()
-                    idx, _ = self._model.recommend(mask, k, offset, stop)
-                    yield with_ranks(offset, stop, idx, idx, mask, mask)
+                    idx, val = self._model.recommend(mask, k, offset, stop)
+                    yield with_ranks(offset, stop, idx, idx, mask, mask, val, val)
                 else:
                     mask_t = mask_v = self.get_candidate_mask()
-                    idx_t, _ = self._model.recommend(mask_t, k, offset, stop)
-                    idx_v = idx_t
+                    idx_t, val_t = self._model.recommend(mask_t, k, offset, stop)
+                    idx_v, val_v = idx_t, val_t
                     if hasattr(self._data, "val_dict"):
                         mask_v = self.get_candidate_mask(validation=True)
-                        idx_v, _ = self._model.recommend(mask_v, k, offset, stop)
-                    yield with_ranks(offset, stop, idx_v, idx_t, mask_v, mask_t)
+                        idx_v, val_v = self._model.recommend(mask_v, k, offset, stop)
+                    yield with_ranks(offset, stop, idx_v, idx_t, mask_v, mask_t, val_v, val_t)
         return self.evaluator.eval_device(self._model.ctx, self._data, blocks())
 
     # -- scoring -------------------------------------------------------------------------------------

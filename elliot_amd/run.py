@@ -36,7 +36,9 @@ def build_config(exp, base_dir):
     ev.setdefault("relevance_threshold", 0)             # run.py:55-56
     ev.setdefault("paired_ttest", False)
     ev.setdefault("wilcoxon_test", False)
-    ev.setdefault("complex_metrics", [])
+    # namespace_model.py:203-205: the clustering files of the complex metrics, resolved against the config folder, {0} = the data set
+    ev["complex_metrics"] = [{k: (_resolve(base_dir, v, ds) if isinstance(v, str) and k.endswith("_file") else v) for k, v in m.items()}
+                             for m in (ev.get("complex_metrics") or [])]
     cfg = SimpleNamespace(
         dataset=ds, top_k=exp.get("top_k", 10), evaluation=_ns(ev), config_test=False, gpu=exp.get("gpu", 0),
         path_output_rec_result=_resolve(base_dir, exp.get("path_output_rec_result", "../results/{0}/recs/"), ds),

@@ -1356,6 +1356,60 @@ int el_beyond_entropy(el_ctx* ctx, void* stream, const int32_t* rec_idx, int64_t
                       const int64_t* test_indptr, int32_t cutoff, int64_t n_items, const double* nov, double* sum,
                       void* ws, size_t ws_bytes);
 
+/* ---- fairness metrics from the top-k tensors -------------------------------------------------------------------------
+ * Replaces: the nine classes of evaluation/metrics/fairness/ (rsp/rsp.py, reo/reo.py, BiasDisparity/BiasDisparity{BR,BS,BD}.py,
+ * MAD/{User,Item}MAD{ranking,rating}.py) behind Evaluator._process_test_data (evaluation/evaluator.py:117-147).  Populations,
+ * lists, test / train CSRs, threshold, cutoff and discount as el_beyond_metrics.  Groups are label tables:
+ *   item_group int32[n_items], user_group int32[users], -1 = no label, labels 0 .. n_*_groups - 1, at most 64 groups each
+ *   (a label outside that range counts as none).  A list that holds an id twice is outside the contract (top-k never makes one).
+ *
+ * el_fair_metrics, users [u_start, u_stop):
+ *   rec_val          optional float [n, ld]: the scores of rec_idx (null: the mean score and the hit scores are 0)
+ *   item_group_size  int64[n_item_groups]: rows of the clustering file per label, ids outside the catalogue included (rsp.py:97)
+ *   item_counts      int64[4][n_item_groups], ADDED to:
+ *                      0 RSP numerator    over A: list entries with label g
+ *                      1 RSP denominator  over A: item_group_size[g] - #{train_u with label g}
+ *                      2 REO numerator    over R: relevant list entries with label g
+ *                      3 REO denominator  over R: relevant held-out items of the user with label g in [0, n_items) outside train_u
+ *   pair_counts      int64[n_user_groups][n_item_groups], ADDED to: list entries of the users of A with label h whose item has
+ *                    label g (BiasDisparityBR's count matrix)
+ *   user_label       int32[n] (written): user_group of the block's users
+ *   user_rows        double[n][4] (written): nDCG (ndcg.py; the same bits as column 0 of el_rec_metrics' per_user rows), 1 if the
+ *                    user is in R, the mean of rec_val over the list, 1 if that mean counts (in R, rec_val given, list not
+ *                    empty); all 0 for a user outside R
+ *   hit_pos, hit_score  int32 / float [nnz of the test CSR], aligned with it; the caller fills hit_pos with -1 once, the call
+ *                    writes, for every relevant held-out entry of the block's users that the list holds, its column and its score
+ *   hist             int32[n_items], ADDED to: number of lists of users of R that hold the item
+ *   Integers are aggregated in LDS per workgroup, then added with 64-bit integer adds: exact and independent of the block cut.
+ * el_group_counts: pair_counts int64[n_user_groups][n_item_groups], ADDED to: entries of the rows [0, n_rows) of a CSR whose row
+ *   has label h and whose column has label g (BiasDisparityBS on the train matrix).
+ * el_group_sums: sums double[n_groups][width] and counts int64[n_groups], both ADDED to: the rows [n, width] (width <= 4) and the
+ *   number of rows per label, in a shape that depends on n alone (the grouped sibling of the metrics' fixed-shape sum tree).
+ * el_fair_item_finish, after the last block: per item v_i = (sum over the item's column of the held-out set, in ascending user
+ *   order, of the gain 2^(rating - threshold + 1) - 1 / of hit_score where hit_pos >= 0) / hist[i];
+ *   col_indptr int64[n_items + 1], col_entry int64[entries with id < n_items]: the item-major copy of the test CSR, col_entry =
+ *   the entry's index in the CSR, users ascending inside a column
+ *   sums double[n_item_groups][2] (gain, score) and counts int64[n_item_groups], ADDED to: v_i and 1 per labelled item with
+ *   hist[i] > 0, in a fixed shape;  per_item optional double[n_items][2] = v_i (0 where hist[i] = 0)
+ * No float atomics: the same input gives the same bytes, and a per-item sum does not depend on the block cut.  cutoff <= 512.   */
+int el_fair_metrics(el_ctx* ctx, void* stream, const int32_t* rec_idx, const float* rec_val, int64_t ld, int64_t u_start,
+                    int64_t u_stop, const int64_t* test_indptr, const int32_t* test_indices, const float* test_ratings,
+                    double threshold, int32_t cutoff, const int64_t* train_indptr, const int32_t* train_indices, int64_t n_items,
+                    const int32_t* item_group, int32_t n_item_groups, const int64_t* item_group_size, const int32_t* user_group,
+                    int32_t n_user_groups, const double* discount, int64_t* item_counts, int64_t* pair_counts,
+                    int32_t* user_label, double* user_rows, int32_t* hit_pos, float* hit_score, int32_t* hist);
+int el_group_counts(el_ctx* ctx, void* stream, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_items,
+                    const int32_t* item_group, int32_t n_item_groups, const int32_t* user_group, int32_t n_user_groups,
+                    int64_t* pair_counts);
+size_t el_group_sums_ws_bytes(int64_t n, int32_t n_groups);
+int el_group_sums(el_ctx* ctx, void* stream, const double* rows, int32_t width, const int32_t* labels, int64_t n, int32_t n_groups,
+                  double* sums, int64_t* counts, void* ws, size_t ws_bytes);
+size_t el_fair_item_finish_ws_bytes(int64_t n_items, int32_t n_item_groups);
+int el_fair_item_finish(el_ctx* ctx, void* stream, const int64_t* col_indptr, const int64_t* col_entry, const float* test_ratings,
+                        double threshold, const int32_t* hit_pos, const float* hit_score, const int32_t* hist, int64_t n_items,
+                        const int32_t* item_group, int32_t n_item_groups, double* sums, int64_t* counts, double* per_item, void* ws,
+                        size_t ws_bytes);
+
 /* Fragile-user report (BASELINE.md "fragile near-tie users reported separately").  The reference scores
  * with tf.matmul (BPRMF_batch_model.py:83-84), whose fp32 summation order is unknowable here; the kernels pin the k-ordered
  * fma chain.  Any two fp32 evaluations of <u,i> differ by at most F 2^-23 |u||i|, so a user's top-k SET does not depend on
