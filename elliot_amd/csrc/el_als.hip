@@ -362,6 +362,7 @@ extern "C" int el_als_solve(el_ctx* ctx, void* stream, const int64_t* indptr, co
     EL_REQUIRE((flags & ~EL_ALS_SKIP_EMPTY) == 0, "el_als_solve: unknown flags 0x%x", flags);
     EL_REQUIRE(piece_len >= 1, "el_als_solve: piece_len must be >= 1");
     EL_REQUIRE(n_long >= 0 && (n_long == 0 || (long_rows && long_first)), "el_als_solve: long-row plan needs both arrays");
+    EL_REQUIRE(n_pieces <= 0 || n_long > 0, "el_als_solve: bad long-row plan (%lld pieces but no long row)", (long long)n_pieces);
     hipStream_t st = (hipStream_t)stream;
     EL_LAUNCH("k_als_status_init", k_als_status_init, dim3(1), dim3(64), 0, st, status);
     EL_CHECK_LAUNCH();

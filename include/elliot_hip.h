@@ -660,7 +660,8 @@ int el_als_gram(el_ctx* ctx, void* stream, const double* Y, int64_t n, int32_t F
  *   X[r] = A_r^-1 b_r by Cholesky (fp64, no pivoting); an empty row gets X[r] = 0 by the same arithmetic, or keeps its
  *   X row under EL_ALS_SKIP_EMPTY.
  * Rows with more than piece_len entries must be listed: long_rows int32[n_long] ascending, long_first int64[n_long + 1]
- * with long_first[0] = 0 and long_first[j + 1] - long_first[j] = ceil(len / piece_len); n_pieces = long_first[n_long].
+ * with long_first[0] = 0 and long_first[j + 1] - long_first[j] = ceil(len / piece_len); n_pieces = long_first[n_long]
+ * (pieces without a long row are refused before any launch).
  * Each piece of piece_len positions is summed into its own slot of ws = el_als_solve_ws_bytes(n_pieces, F) bytes and
  * the slots are added in piece order: the same bits on every run.
  * status int32[2] on the device, written by the call: [0] the smallest row met with a non-positive pivot, [1] the

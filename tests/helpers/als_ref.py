@@ -32,6 +32,29 @@ def half(G, indptr, indices, Y, w_A, w_b, lam, X, skip_empty=False):
     return X
 
 
+def backward_error(indptr, indices, Y, w_A, w_b, lam, X, rows=None):
+    """Per row r (all rows, or those of `rows`, in that order): eta_r = |b_r - A_r x_r|_inf / (|A_r|_inf |x_r|_inf + |b_r|_inf) with
+    A_r = Y^T Y + w_A sum y y^T + lam I and b_r = w_b sum y built from Y in np.longdouble -- the Gram too -- and x_r = X[r];
+    0 where the denominator is 0.  The normwise backward error of x_r as a solution of the row's normal equations: it depends on
+    the order of no sum and on no other solver.  A NaN in x_r gives NaN."""
+    ld = np.longdouble
+    Yl = np.asarray(Y, dtype=ld)
+    F = Yl.shape[1]
+    G = Yl.T.dot(Yl)
+    lamI = ld(lam) * np.eye(F, dtype=ld)
+    rows = range(len(indptr) - 1) if rows is None else rows
+    eta = np.zeros(len(rows), dtype=np.float64)
+    for n, r in enumerate(rows):
+        P = Yl[indices[indptr[r]:indptr[r + 1]]]
+        A = G + ld(w_A) * P.T.dot(P) + lamI
+        b = ld(w_b) * P.sum(axis=0)
+        x = np.asarray(X[r], dtype=ld)
+        den = np.abs(A).sum(axis=1).max() * np.abs(x).max() + np.abs(b).max()
+        if den != 0:                                      # (a NaN denominator is not 0: eta is NaN)
+            eta[n] = float(np.abs(b - A.dot(x)).max() / den)
+    return eta
+
+
 def orientations(indptr, indices, U, I):
     R = sp.csr_matrix((np.ones(len(indices)), np.asarray(indices), np.asarray(indptr)), shape=(U, I))
     R.sort_indices()
