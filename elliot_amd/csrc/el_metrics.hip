@@ -2,27 +2,17 @@
 //
 // Replaces, for the simple accuracy metrics, the reference's per-user Python: get_single_recommendation's dict building
 // (recommender_utils_mixin.py:84-88) + Evaluator.eval -> metric classes (evaluation/evaluator.py:117-147):
-//   relevance   test items with rating >= threshold                         relevance/relevance.py:87-96
-//   gain        2^(rating - threshold + 1) - 1, discount ln2 / ln(rank + 2)  relevance/relevance.py:49-55,71-82
-//   nDCG        DCG / IDCG, IDCG over the user's gains sorted descending      metrics/accuracy/ndcg/ndcg.py:68-125
+//   nDCG        DCG / IDCG; relevance, gain, discount and the IDCG pass are el_metrics_row.h's    metrics/accuracy/ndcg/ndcg.py:68-125
 //   Precision   hits / cutoff (precision.py:66)   Recall  hits / #relevant (recall.py:66)   HR  hits > 0 (hit_rate.py:66)
 //   MAP         mean over ranks r <= cutoff of (hits in the first r) / r  (map.py:69-80, the reference's definition)
 //   MRR         1 / rank of the first hit (mrr.py:63-70)        F1  harmonic mean of Precision and Recall (f1.py:56-68)
 //   averaged over the users with >= 1 relevant test item (ndcg.py:124-125)
-// Arithmetic in fp64 like the reference; the discount table comes from the host (Python's math.log values).
 // One wave per user; the per-user rows are reduced by a fixed-shape tree so that the sums are run-to-run identical.
 #include "el_common.h"
-#include "el_topk_common.h"
+#include "el_metrics_row.h"
 #include "el_metrics_tree.h"
 
 #define MET_N 8          // nDCG, Precision, Recall, HR, MAP, MRR, F1, valid
-#define MET_BUF 1024     // LDS gain buffer per wave (kept <= 512 + incoming)
-#define MET_MAXCUT 512
-
-__device__ __forceinline__ double el_wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void k_rec_metrics(const int32_t* __restrict__ rec, int64_t ld, int64_t u_start, int64_t n_users,
                                                      const int64_t* __restrict__ tp, const int32_t* __restrict__ ti,
@@ -37,36 +27,8 @@ __global__ __launch_bounds__(256) void k_rec_metrics(const int32_t* __restrict__
     const int64_t t0 = tp[user], t1 = tp[user + 1];
 
     // ---- relevant test items: count, and the `cutoff` largest gains (IDCG) -------------------------------------
-    int cnt = 0;
-    double nrel = 0.0;
-    auto sort_keep = [&]() {
-        int n2 = 64;
-        while (n2 < cnt) n2 <<= 1;
-        for (int t = cnt + lane; t < n2; t += 64) gb[t] = 0ull;
-        el_wave_lds_sync();
-        el_wave_bitonic_desc(gb, n2, lane);               // positive doubles order as their bit patterns
-        cnt = cnt < cutoff ? cnt : cutoff;
-    };
-    for (int64_t b = t0; b < t1; b += 64) {
-        const int64_t e = b + lane;
-        bool relv = false;
-        double g = 0.0;
-        if (e < t1) {
-            const double r = tr ? (double)tr[e] : 1.0;
-            relv = r >= thr;
-            if (relv) g = exp2(r - thr + 1.0) - 1.0;
-        }
-        const u64 bal = __ballot(relv);
-        if (relv) gb[cnt + __popcll(bal & ((1ull << lane) - 1ull))] = (u64)__double_as_longlong(g);
-        cnt += __popcll(bal);
-        nrel += (double)__popcll(bal);
-        el_wave_lds_sync();
-        if (cnt > MET_BUF - 64) sort_keep();
-    }
-    sort_keep();
-    double idcg = 0.0;
-    for (int t = lane; t < cnt; t += 64) idcg += __longlong_as_double((long long)gb[t]) * disc[t];
-    idcg = el_wave_sum(idcg);
+    const MetRow row = met_row_idcg(gb, tr, t0, t1, thr, cutoff, disc, lane, [](int64_t, bool) {});
+    const double nrel = row.nrel, idcg = row.idcg;
 
     // ---- the recommendation list ------------------------------------------------------------------------------------
     double dcg = 0.0, map = 0.0;
@@ -78,14 +40,9 @@ __global__ __launch_bounds__(256) void k_rec_metrics(const int32_t* __restrict__
         if (c < cutoff) {
             const int32_t item = rec[ur * ld + c];
             if (item >= 0) {
-                const int64_t pos = el_lower_bound(ti, t0, t1, item);
-                if (pos < t1 && ti[pos] == item) {
-                    const double r = tr ? (double)tr[pos] : 1.0;
-                    if (r >= thr) {
-                        hit = true;
-                        g = exp2(r - thr + 1.0) - 1.0;
-                    }
-                }
+                const MetEntry m = met_lookup(ti, tr, t0, t1, item, thr);
+                hit = m.rel;
+                g = m.gain;
             }
         }
         const u64 bal = __ballot(hit);
@@ -97,8 +54,8 @@ __global__ __launch_bounds__(256) void k_rec_metrics(const int32_t* __restrict__
         if (first < 0 && bal) first = c0 + __ffsll((long long)bal) - 1;
         nh += __popcll(bal);
     }
-    dcg = el_wave_sum(dcg);
-    map = el_wave_sum(map);
+    dcg = el_group_sum(dcg, 64);
+    map = el_group_sum(map, 64);
     if (lane == 0) {
         double* o = out + ur * MET_N;
         const double valid = nrel > 0.0 ? 1.0 : 0.0;
@@ -130,8 +87,7 @@ extern "C" int el_rec_metrics(el_ctx* ctx, void* stream, const int32_t* rec_idx,
     const int64_t n = u_stop - u_start;
     if (n == 0) return 0;
     EL_REQUIRE(rec_idx && test_indptr && test_indices && discount && sums, "el_rec_metrics: null pointer");
-    EL_REQUIRE(cutoff >= 1 && cutoff <= MET_MAXCUT && (int64_t)cutoff <= ld, "el_rec_metrics: cutoff %d unsupported (1..%d, <= ld)", cutoff,
-               MET_MAXCUT);
+    MET_REQUIRE_CUTOFF("el_rec_metrics", cutoff, ld);
     MetWs w;
     EL_REQUIRE(ws != nullptr && ws_bytes >= met_carve(n, MET_N, ws, &w), "el_rec_metrics: workspace too small");
     hipStream_t st = (hipStream_t)stream;

@@ -28,13 +28,13 @@
 // 131 072 x 10 at I = 1 M (profiles/metrics_beyond_bench.md, scripts/metrics_bench.py), whole el_beyond_metrics call: tile-aggregated
 // 0.29 / 0.28 / 0.24 ms on uniform / Zipf / identical lists, direct 0.20 / 1.11 / 1.56 ms -- the default is the aggregated form.
 #include "el_common.h"
+#include "el_metrics_row.h"          // relevance and the list-entry lookup, shared with the accuracy and fairness kernels
 #include "el_metrics_tree.h"
 #include "el_metrics_hist.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
 #define BEY_N 18
-#define BEY_MAXCUT 512
 
 struct BeyArgs {
     const int32_t* rec;
@@ -53,11 +53,6 @@ struct BeyArgs {
     int32_t* hist;
     double* rows;
 };
-
-__device__ __forceinline__ double bey_wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 template <bool DIRECT>
 __global__ __launch_bounds__(256) void k_beyond_users(BeyArgs a) {
@@ -81,8 +76,7 @@ __global__ __launch_bounds__(256) void k_beyond_users(BeyArgs a) {
         bool relv = false;
         int h = -1;
         if (e < t1) {
-            const double r = a.tr ? (double)a.tr[e] : 1.0;
-            relv = r >= a.thr;
+            relv = met_rating(a.tr, e) >= a.thr;
             const int32_t item = a.ti[e];
             if (relv && item >= 0 && item < I && !el_row_contains(a.qi, q0, q1, item)) h = a.head[item] ? 1 : 0;
         }
@@ -120,14 +114,10 @@ __global__ __launch_bounds__(256) void k_beyond_users(BeyArgs a) {
                 ps += (double)a.pop[item];
                 const double d = a.disc[c];
                 norm += d;
-                const int64_t pos = el_lower_bound(a.ti, t0, t1, item);
-                if (pos < t1 && a.ti[pos] == item) {
-                    const double r = a.tr ? (double)a.tr[pos] : 1.0;
-                    if (r >= a.thr) {
-                        hit = true;
-                        fe += d * a.efd[item];
-                        fp += d * a.epc[item];
-                    }
+                if (met_lookup(a.ti, a.tr, t0, t1, item, a.thr).rel) {
+                    hit = true;
+                    fe += d * a.efd[item];
+                    fp += d * a.epc[item];
                 }
                 if (DIRECT) atomicAdd(a.hist + item, 1);
             }
@@ -137,10 +127,10 @@ __global__ __launch_bounds__(256) void k_beyond_users(BeyArgs a) {
         rnh += __popcll(__ballot(hit && !tail));
         rnt += __popcll(__ballot(hit && tail));
     }
-    ps = bey_wave_sum(ps);
-    fe = bey_wave_sum(fe);
-    fp = bey_wave_sum(fp);
-    norm = bey_wave_sum(norm);
+    ps = el_group_sum(ps, 64);
+    fe = el_group_sum(fe, 64);
+    fp = el_group_sum(fp, 64);
+    norm = el_group_sum(norm, 64);
     if (lane == 0) {
         const double dn = (double)nu;
         const bool nov = inR && norm > 0.0;
@@ -219,7 +209,7 @@ __global__ __launch_bounds__(256) void k_beyond_entropy(const int32_t* __restric
             }
             nu += __popcll(__ballot(valid));
         }
-        s = bey_wave_sum(s);
+        s = el_group_sum(s, 64);
     }
     if (lane == 0) rows[ur] = nu > 0 ? s / (double)nu : 0.0;
 }
@@ -270,8 +260,7 @@ extern "C" int el_beyond_metrics(el_ctx* ctx, void* stream, const int32_t* rec_i
     EL_REQUIRE(rec_idx && test_indptr && test_indices && train_indptr && train_indices && pop && head && efd && epc && discount && hist &&
                    sums,
                "el_beyond_metrics: null pointer");
-    EL_REQUIRE(cutoff >= 1 && cutoff <= BEY_MAXCUT && (int64_t)cutoff <= ld, "el_beyond_metrics: cutoff %d unsupported (1..%d, <= ld)", cutoff,
-               BEY_MAXCUT);
+    MET_REQUIRE_CUTOFF("el_beyond_metrics", cutoff, ld);
     EL_REQUIRE(n_items >= 1 && n_items < (1LL << 31) && n_head >= 0 && n_head <= n_items, "el_beyond_metrics: bad item counts");
     EL_REQUIRE(n < (1LL << 31), "el_beyond_metrics: more than 2^31 users in one block");
     MetWs m;
@@ -329,8 +318,7 @@ extern "C" int el_beyond_entropy(el_ctx* ctx, void* stream, const int32_t* rec_i
     const int64_t n = u_stop - u_start;
     if (n == 0) return 0;
     EL_REQUIRE(rec_idx && test_indptr && nov && sum, "el_beyond_entropy: null pointer");
-    EL_REQUIRE(cutoff >= 1 && cutoff <= BEY_MAXCUT && (int64_t)cutoff <= ld, "el_beyond_entropy: cutoff %d unsupported (1..%d, <= ld)", cutoff,
-               BEY_MAXCUT);
+    MET_REQUIRE_CUTOFF("el_beyond_entropy", cutoff, ld);
     EL_REQUIRE(n_items >= 1 && n_items < (1LL << 31), "el_beyond_entropy: bad item count");
     MetWs m;
     EL_REQUIRE(ws != nullptr && ws_bytes >= met_carve(n, 1, ws, &m), "el_beyond_entropy: workspace too small");

@@ -14,7 +14,7 @@
 //                          denominators, the BR count matrix) are added into an LDS table per workgroup and flushed with one 64-bit
 //                          integer add per non-zero cell: with two or three groups every list entry of the block lands on the same
 //                          few words.
-//                          Per user: label, nDCG (the arithmetic of k_rec_metrics, operation for operation), mean list score, flags.
+//                          Per user: label, nDCG (k_rec_metrics' own IDCG pass and lookup, el_metrics_row.h), mean list score, flags.
 //                          Per relevant held-out entry found in the list: its column and its score (arrays aligned with the CSR).
 //      k_beyond_hist<true> the lists of the users of R into an int32[I] histogram (el_metrics_hist.h)
 //      el_group_sums       the per-user rows summed by user label in a fixed shape
@@ -24,13 +24,11 @@
 // No float atomics anywhere: integer adds do not depend on their order, every fp64 sum has a shape fixed by the sizes alone, and an
 // item's sum runs in user order whatever the block cut was.
 #include "el_common.h"
-#include "el_topk_common.h"
+#include "el_metrics_row.h"
 #include "el_metrics_tree.h"
 #include "el_metrics_hist.h"
 
 #define FAIR_MAXG 64
-#define FAIR_MAXCUT 512     // = BEY_MAXCUT
-#define FAIR_BUF 1024       // LDS gain buffer per wave, as MET_BUF
 #define FAIR_UPW 8          // users per wave: 32 per workgroup share one LDS table
 #define FAIR_ROW 4          // per-user row: nDCG, in R, mean list score, has a score
 
@@ -57,11 +55,6 @@ struct FairArgs {
     float* hit_score;
 };
 
-__device__ __forceinline__ double fair_wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __device__ __forceinline__ int fair_label(const int32_t* __restrict__ tab, int64_t i, int G) {
     const int g = tab[i];
     return (g >= 0 && g < G) ? g : -1;
@@ -74,7 +67,7 @@ __device__ __forceinline__ void fair_lds_add(int* tab, int key) {
 }
 
 __global__ __launch_bounds__(256) void k_fair_users(FairArgs a) {
-    __shared__ u64 gb_[4][FAIR_BUF];
+    __shared__ u64 gb_[4][MET_BUF];
     extern __shared__ int tab[];                               // fair_tab_ints(Gu, Gi) ints: the table is as large as the groups need
     const int Gi = a.Gi, Gu = a.Gu, cutoff = a.cutoff;
     int *rspn = tab, *tcnt = tab + FAIR_MAXG, *reon = tab + 2 * FAIR_MAXG, *reod = tab + 3 * FAIR_MAXG, *br = tab + 4 * FAIR_MAXG;
@@ -98,44 +91,16 @@ __global__ __launch_bounds__(256) void k_fair_users(FairArgs a) {
         }
         const int64_t q0 = a.qp[user], q1 = a.qp[user + 1];
 
-        // ---- held-out row: relevant items, the `cutoff` largest gains (IDCG, as k_rec_metrics), REO denominators -----------------
-        int cnt = 0;
-        double nrel = 0.0;
-        auto sort_keep = [&]() {
-            int n2 = 64;
-            while (n2 < cnt) n2 <<= 1;
-            for (int t = cnt + lane; t < n2; t += 64) gb[t] = 0ull;
-            el_wave_lds_sync();
-            el_wave_bitonic_desc(gb, n2, lane);
-            cnt = cnt < cutoff ? cnt : cutoff;
-        };
-        for (int64_t b = t0; b < t1; b += 64) {
-            const int64_t e = b + lane;
-            bool relv = false;
-            double g = 0.0;
+        // ---- held-out row: relevant items, the `cutoff` largest gains (IDCG), REO denominators ----------------------------------------
+        const MetRow row = met_row_idcg(gb, a.tr, t0, t1, thr, cutoff, a.disc, lane, [&](int64_t e, bool relv) {
             int dg = -1;
-            if (e < t1) {
-                const double r = a.tr ? (double)a.tr[e] : 1.0;
-                relv = r >= thr;
-                if (relv) {
-                    g = exp2(r - thr + 1.0) - 1.0;
-                    const int32_t item = a.ti[e];
-                    if (item >= 0 && item < a.I && !el_row_contains(a.qi, q0, q1, item)) dg = fair_label(a.item_group, item, Gi);
-                }
+            if (relv) {
+                const int32_t item = a.ti[e];
+                if (item >= 0 && item < a.I && !el_row_contains(a.qi, q0, q1, item)) dg = fair_label(a.item_group, item, Gi);
             }
-            const u64 bal = __ballot(relv);
-            if (relv) gb[cnt + __popcll(bal & ((1ull << lane) - 1ull))] = (u64)__double_as_longlong(g);
-            cnt += __popcll(bal);
-            nrel += (double)__popcll(bal);
-            el_wave_lds_sync();
-            if (cnt > FAIR_BUF - 64) sort_keep();
             fair_lds_add(reod, dg);
-        }
-        sort_keep();
-        double idcg = 0.0;
-        for (int t = lane; t < cnt; t += 64) idcg += __longlong_as_double((long long)gb[t]) * a.disc[t];
-        idcg = fair_wave_sum(idcg);
-        const bool inR = nrel > 0.0;
+        });
+        const bool inR = row.nrel > 0.0;
 
         // ---- train row: what it holds of every item group (RSP denominators) ----------------------------------------------------------
         for (int64_t b = q0; b < q1; b += 64) {
@@ -160,22 +125,17 @@ __global__ __launch_bounds__(256) void k_fair_users(FairArgs a) {
             if (c < cutoff) {
                 const int32_t item = a.rec[ur * a.ld + c];
                 if (item >= 0) {
-                    const int64_t pos = el_lower_bound(a.ti, t0, t1, item);
-                    if (pos < t1 && a.ti[pos] == item) {
-                        const double r = a.tr ? (double)a.tr[pos] : 1.0;
-                        if (r >= thr) {
-                            hit = item < a.I;
-                            g = exp2(r - thr + 1.0) - 1.0;
-                        }
-                    }
+                    const MetEntry m = met_lookup(a.ti, a.tr, t0, t1, item, thr);
+                    hit = m.rel && item < a.I;
+                    g = m.gain;
                     if (item < a.I) {
                         valid = true;
                         ig = fair_label(a.item_group, item, Gi);
                         const float sc = a.val ? a.val[ur * a.ld + c] : 0.0f;
                         ss += (double)sc;
                         if (hit) {
-                            a.hit_pos[pos] = c;
-                            a.hit_score[pos] = sc;
+                            a.hit_pos[m.pos] = c;
+                            a.hit_score[m.pos] = sc;
                         }
                     }
                 }
@@ -186,11 +146,11 @@ __global__ __launch_bounds__(256) void k_fair_users(FairArgs a) {
             fair_lds_add(br, (h >= 0 && ig >= 0) ? h * Gi + ig : -1);
             fair_lds_add(reon, hit ? ig : -1);
         }
-        dcg = fair_wave_sum(dcg);
-        ss = fair_wave_sum(ss);
+        dcg = el_group_sum(dcg, 64);
+        ss = el_group_sum(ss, 64);
         if (lane == 0) {
             const bool scored = inR && a.val != nullptr && nu > 0;
-            o[0] = (inR && dcg > 0.0 && idcg > 0.0) ? dcg / idcg : 0.0;
+            o[0] = (inR && dcg > 0.0 && row.idcg > 0.0) ? dcg / row.idcg : 0.0;
             o[1] = inR ? 1.0 : 0.0;
             o[2] = scored ? ss / (double)nu : 0.0;
             o[3] = scored ? 1.0 : 0.0;
@@ -298,8 +258,7 @@ __global__ __launch_bounds__(256) void k_fair_items(const int64_t* __restrict__ 
         for (int64_t j = cp[i]; j < cp[i + 1]; ++j) {
             const int64_t e = ce[j];
             if (hit_pos[e] >= 0) {
-                const double r = tr ? (double)tr[e] : 1.0;
-                sg += exp2(r - thr + 1.0) - 1.0;
+                sg += met_gain(met_rating(tr, e), thr);
                 ss += (double)hit_score[e];
             }
         }
@@ -358,8 +317,7 @@ extern "C" int el_fair_metrics(el_ctx* ctx, void* stream, const int32_t* rec_idx
     EL_REQUIRE(rec_idx && test_indptr && test_indices && train_indptr && train_indices && item_group && item_group_size && user_group &&
                    discount && item_counts && pair_counts && user_label && user_rows && hit_pos && hit_score && hist,
                "el_fair_metrics: null pointer");
-    EL_REQUIRE(cutoff >= 1 && cutoff <= FAIR_MAXCUT && (int64_t)cutoff <= ld, "el_fair_metrics: cutoff %d unsupported (1..%d, <= ld)", cutoff,
-               FAIR_MAXCUT);
+    MET_REQUIRE_CUTOFF("el_fair_metrics", cutoff, ld);
     EL_REQUIRE(fair_groups_ok(n_item_groups) && fair_groups_ok(n_user_groups), "el_fair_metrics: %d item / %d user groups (1..%d each)",
                n_item_groups, n_user_groups, FAIR_MAXG);
     EL_REQUIRE(n_items >= 1 && n_items < (1LL << 31), "el_fair_metrics: bad item count");

@@ -1,6 +1,7 @@
-// Column sums of per-user metric rows [n, W] (fp64) in a fixed shape, shared by the accuracy metrics (el_metrics.hip, W = 8) and the
-// beyond-accuracy metrics (el_metrics_beyond.hip): G workgroups x contiguous row ranges -> partial[G][W]; then one wave adds the G rows
-// to the caller's sums.  The shape depends on n alone, so the same input gives the same bytes.
+// Column sums of per-user metric rows [n, W] (fp64) in a fixed shape, shared by the accuracy metrics (el_metrics.hip, W = 8), the
+// beyond-accuracy metrics (el_metrics_beyond.hip, W = 18 and 1) and the rank metrics (el_rank.hip, W = 6); the fairness metrics
+// (el_metrics_fair.hip) take met_groups for their grouped sums.  G workgroups x contiguous row ranges -> partial[G][W]; then one wave
+// adds the G rows to the caller's sums.  The shape depends on n alone, so the same input gives the same bytes.
 //   VALID >= 0: only the rows whose column VALID is non-zero are added (the accuracy metrics' "has a relevant item" flag)
 //   VALID <  0: every row is added (the kernel writes zeros where a term does not count)
 #pragma once

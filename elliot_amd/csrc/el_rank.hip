@@ -38,6 +38,7 @@
 #include "el_common.h"
 
 #include "el_topk_common.h"
+#include "el_metrics_row.h"
 #include "el_metrics_tree.h"
 
 #define RANK_CAP 512         // targets per pass of k_rank_wave: 512 keys (8 or 12 bytes) + 512 counters = 6 / 8 KB of LDS a wave
@@ -645,8 +646,7 @@ __global__ __launch_bounds__(256) void k_rank_metrics(const int32_t* __restrict_
     const int64_t user = u_start + ur, base = tp[u_start];
     int64_t nrel = 0, m = 0, P = 0, mc = 0, Pc = 0;
     for (int64_t e = tp[user]; e < tp[user + 1]; ++e) {
-        const double r = tr ? (double)tr[e] : 1.0;
-        if (!(r >= thr)) continue;
+        if (!(met_rating(tr, e) >= thr)) continue;
         ++nrel;
         const int64_t q = pos[e - base];
         if (q >= 0) {

@@ -154,3 +154,42 @@ def fragile_case(F, n, seed, k=10, u_start=37, item_offset=1000, n_items=300):
     margin = float(np.min(np.abs(gap[live] - bound[live]) / bound[live])) if live.any() else np.inf
     return dict(Gu=Gu, Gi=Gi, idx=idx, val=val, k=k, u_start=u_start, item_offset=item_offset, flags=flags,
                 counts=(int(flags.sum()), int(short.sum())), margin=margin, tie=tie)
+
+
+# ---- the IDCG selection at the edges of its gain buffer: el_rec_metrics and el_fair_metrics run the same pass ----------------------
+REL_COUNTS = (0, 1, 63, 64, 65, 511, 512, 513, 960, 961, 1023, 1024, 1025, 1500, 3000)
+
+
+def idcg_case(cutoff):
+    """One user per relevant count, thr 2.5, fractional float32 ratings with runs of ties (quarter steps, 2.5 itself among them);
+    entries below the threshold sit between the relevant ones, and the largest gains fill the last 64 entries of the row."""
+    rs = np.random.RandomState(77 + cutoff)
+    thr, rws = 2.5, []
+    for c in REL_COUNTS:
+        tail = min(64, c)
+        body = c - tail
+        b = np.where(rs.rand(body) < 0.5, np.round(rs.uniform(2.5, 4.0, size=body) * 4) / 4, rs.uniform(2.5, 4.0, size=body))
+        t = np.where(rs.rand(tail) < 0.5, np.round(rs.uniform(4.5, 5.0, size=tail) * 8) / 8, rs.uniform(4.5, 5.0, size=tail))
+        r = [1.25, 2.0]
+        for x in b:
+            r.append(x)
+            if rs.rand() < 0.34:
+                r.append(rs.uniform(0.5, 2.49))
+        rws.append(np.concatenate([np.array(r), t]).astype(np.float32))
+    deg = np.array([len(r) for r in rws])
+    ip = np.zeros(len(rws) + 1, np.int64)
+    ip[1:] = np.cumsum(deg)
+    ratings = np.concatenate(rws)
+    items = np.concatenate([2 * np.arange(d) + 1 for d in deg]).astype(np.int32)        # odd ids; the even ones are in no row
+    assert [(r >= np.float32(thr)).sum() for r in rws] == list(REL_COUNTS)
+    ld = cutoff
+    recs = np.empty((len(rws), ld), np.int32)
+    for u, d in enumerate(deg):
+        row = items[ip[u]:ip[u + 1]]
+        out = 2 * rs.choice(8000, size=ld, replace=False)
+        pick = np.concatenate([row[-2:][::-1], rs.permutation(row[:-2])])[:(ld + 1) // 2]
+        if cutoff == 1 and u % 2:
+            pick = pick[:0]
+        mix = np.concatenate([pick, out])[:ld]
+        recs[u] = mix if cutoff == 1 else rs.permutation(mix)
+    return recs, ip, items, ratings, thr

@@ -11,7 +11,7 @@ from elliot_amd import ops
 from elliot_amd.evaluation import fairness
 from elliot_amd.evaluation.evaluator import EvalBlock, Evaluator
 from elliot_amd.recommender.masks import device_masks
-from tests.helpers import beyond_ref, fair_ref
+from tests.helpers import beyond_ref, fair_ref, metrics_ref
 
 pytestmark = pytest.mark.gpu
 Z = fair_ref.load()
@@ -158,6 +158,26 @@ def test_device_matches_the_host_route_random(ctx, tmp_path, cutoff, k, Gi, Gu, 
     b = raw_passes(ctx, data, ig, ug, lists, scores, thr, cutoff)
     for key in a:
         assert a[key].tobytes() == b[key].tobytes(), key
+
+
+@pytest.mark.parametrize("cutoff", [1, 64, 512])
+def test_ndcg_at_the_idcg_buffer_edges_has_the_bits_of_rec_metrics(ctx, cutoff):
+    """One user per relevant count of metrics_ref.REL_COUNTS (the edges of the LDS gain buffer): no train rows, one group each side,
+    no scores."""
+    recs, ip, items, ratings, thr = metrics_ref.idcg_case(cutoff)
+    U, I = recs.shape[0], 16000
+    assert U == 15 and max(int(items.max()), int(recs.max())) < I
+    test = ops.DeviceTestSet(ip, items, ratings, ctx.device)
+    train = ops.DeviceCSR(np.zeros(U + 1, np.int64), np.zeros(0, np.int32), I, ctx.device)
+    ig = ops.DeviceGrouping(grouping_of(np.zeros(I, np.int64), 1), ctx.device)
+    ug = ops.DeviceGrouping(grouping_of(np.zeros(U, np.int64), 1), ctx.device)
+    idx = torch.from_numpy(recs).to(ctx.device)
+    _, rows = ops.fair_metrics(ctx, idx, None, test, train, ig, ug, thr, cutoff, I, ops.FairState(ctx, test, I, ig, ug))
+    _, acc = ops.rec_metrics(ctx, idx, test, thr, cutoff, per_user=True)
+    rows, acc = rows.cpu().numpy(), acc.cpu().numpy()
+    assert acc[1:, 7].all() and acc[0, 7] == 0 and (acc[1:, 0] > 0).any()
+    assert rows[1:, 0].tobytes() == acc[1:, 0].tobytes()
+    assert rows[1:, 1].all() and not rows[0].any()
 
 
 def test_rating_metrics_without_scores_raise(ctx, tmp_path):
