@@ -49,6 +49,13 @@ class BprmfState(C.Structure):
     ]
 
 
+class AmfDelta(C.Structure):
+    _fields_ = [("dGu", _f32p), ("dGi", _f32p), ("rows_u", _i32p), ("rows_i", _i32p), ("counts", _i32p)]
+
+
+EL_AMF_ADVERSARIAL = 1
+
+
 class BprsgdState(C.Structure):
     _fields_ = [
         ("P", _f64p), ("Q", _f64p), ("b", _f64p),
@@ -187,6 +194,13 @@ PROTOTYPES = {
     "el_rows_segment_sum": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, _f32p, C.c_int64, C.c_int32, C.c_int64, _f32p,
                                       C.c_void_p, C.c_size_t]),
     "el_bprmf_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BprmfState), C.c_float, C.c_int, C.c_int32, C.c_float]),
+    "el_amf_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
+    "el_amf_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BprmfState), C.POINTER(AmfDelta), _i32p, _i32p, _i32p, C.c_int64,
+                               C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _f64p, C.c_void_p, C.c_size_t]),
+    "el_amf_perturb": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BprmfState), C.POINTER(AmfDelta), _i32p, _i32p, _i32p, C.c_int64,
+                                 C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_size_t]),
+    "el_amf_delta_clear": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BprmfState), C.POINTER(AmfDelta)]),
+    "el_amf_perturbed_tables": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BprmfState), C.POINTER(AmfDelta), _f32p, _f32p]),
     "el_spmm_csr_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GraphCsr), _f32p, _f32p, C.c_int32, _f32p, _f32p]),
     "el_lightgcn_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "el_lightgcn_propagate": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GraphCsr), _f32p, _f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t]),

@@ -2578,6 +2578,96 @@ class BprmfDeviceState:
         return v
 
 
+class AmfDeviceState:
+    """AMF_model's variables (adversarial/AMF/AMF_model.py:41-51): a BprmfDeviceState with the dense accumulators -- Gu, Gi, Bi and
+    ONE Adam whose step counter plain and adversarial steps share -- plus the two perturbation tables, which are not trained, and
+    the device list of their non-zero rows (el_amf_delta).  An AMF step is el_amf_grads + the state's own apply()."""
+
+    def __init__(self, ctx, Gu, Gi, Bi, delta_Gu=None, delta_Gi=None):
+        self.ctx = ctx
+        self.base = BprmfDeviceState(ctx, Gu, Gi, Bi, optimizer="adam", compact_user_grads=False)
+        b, dev = self.base, ctx.device
+        self.U, self.I, self.F = b.U, b.I, b.F
+        self.dGu = torch.zeros((self.U, self.F), dtype=torch.float32, device=dev)
+        self.dGi = torch.zeros((self.I, self.F), dtype=torch.float32, device=dev)
+        self.rows_u = torch.zeros(self.U, dtype=torch.int32, device=dev)
+        self.rows_i = torch.zeros(self.I, dtype=torch.int32, device=dev)
+        self.counts = torch.zeros(2, dtype=torch.int32, device=dev)
+        self._d = _lib.AmfDelta(dGu=self.dGu.data_ptr(), dGi=self.dGi.data_ptr(), rows_u=self.rows_u.data_ptr(),
+                                rows_i=self.rows_i.data_ptr(), counts=self.counts.data_ptr())
+        self.delta_is_zero = True               # known on the host: plain steps may then take the BPR fast path
+        self._ws = self._Pu = self._Pi = None
+        if delta_Gu is not None:
+            self.set_delta(delta_Gu, delta_Gi)
+
+    loss = property(lambda self: self.base.loss)
+    step = property(lambda self: self.base.step)
+
+    def pop_loss(self):
+        return self.base.pop_loss()
+
+    def _workspace(self, B):
+        return workspace(self, "_ws", int(self.ctx.lib.el_amf_ws_bytes(int(B), self.U, self.I, self.F)), self.ctx.device)
+
+    def _stand_aside(self, on):
+        """The library reads every row as current: the per-row features of the wrapped state stand aside as for its grads() / apply()."""
+        if self.base.deferred or self.base.item_fused:
+            self.base._two_pass(on)
+
+    def _call(self, fn, name, u, i, j, *rest):
+        self._stand_aside(True)
+        ws = self._workspace(u.numel())
+        head = (self.ctx.handle, self.ctx.stream(), C.byref(self.base._c), C.byref(self._d), _ptr(u, torch.int32, "u"),
+                _ptr(i, torch.int32, "i"), _ptr(j, torch.int32, "j"), int(u.numel()))
+        check(fn(*head, *rest, _ptr(ws), ws.numel()), name)
+
+    def grads(self, u, i, j, l_w, l_b, l_adv=0.0, eps=0.0, adversarial=False):
+        """Loss and tape.gradient of train_step (AMF_model.py:70-102) into the accumulators; adversarial=True adds the l_adv term and
+        rebuilds delta from this batch (the gradients still read the delta of the previous step)."""
+        self._call(self.ctx.lib.el_amf_grads, "el_amf_grads", u, i, j, float(l_w), float(l_b), float(l_adv), float(eps),
+                   _lib.EL_AMF_ADVERSARIAL if adversarial else 0, _ptr(self.base.loss, torch.float64))
+        if adversarial:
+            self.delta_is_zero = False
+
+    def apply(self, lr):
+        self.base.apply(lr)
+
+    def train_step(self, u, i, j, lr, l_w, l_b, l_adv, eps, adversarial):
+        self.grads(u, i, j, l_w, l_b, l_adv, eps, adversarial)
+        self.apply(lr)
+
+    def perturb(self, u, i, j, l_w, l_b, eps, eps_iter=0.0, nb_iter=0):
+        """build_perturbation (nb_iter = 0) / build_msap_perturbation (AMF_model.py:133-197): delta only, no optimiser."""
+        self._call(self.ctx.lib.el_amf_perturb, "el_amf_perturb", u, i, j, float(l_w), float(l_b), float(eps), float(eps_iter),
+                   int(nb_iter))
+        self._stand_aside(False)
+        self.delta_is_zero = False
+
+    def clear_delta(self):
+        check(self.ctx.lib.el_amf_delta_clear(self.ctx.handle, self.ctx.stream(), C.byref(self.base._c), C.byref(self._d)),
+              "el_amf_delta_clear")
+        self.delta_is_zero = True
+
+    def set_delta(self, delta_Gu, delta_Gi):
+        """Perturbation tables from outside (a checkpoint): the row lists are rebuilt from their non-zero rows."""
+        for dst, rows, slot, src in ((self.dGu, self.rows_u, 0, delta_Gu), (self.dGi, self.rows_i, 1, delta_Gi)):
+            dst.copy_(torch.as_tensor(np.ascontiguousarray(src)) if isinstance(src, np.ndarray) else src)
+            nz = torch.nonzero((dst != 0).any(dim=1)).flatten().to(torch.int32)
+            rows[:nz.numel()] = nz
+            self.counts[slot] = int(nz.numel())
+        self.delta_is_zero = int(self.counts.sum().item()) == 0
+
+    def perturbed_tables(self):
+        """(Gu + dGu, Gi + dGi) in fp32 scratch tables -- what predict(adversarial=True) multiplies (AMF_model.py:110-111)."""
+        if self._Pu is None:
+            self._Pu, self._Pi = torch.empty_like(self.dGu), torch.empty_like(self.dGi)
+        self._stand_aside(True)
+        check(self.ctx.lib.el_amf_perturbed_tables(self.ctx.handle, self.ctx.stream(), C.byref(self.base._c), C.byref(self._d),
+                                                   _ptr(self._Pu, torch.float32), _ptr(self._Pi, torch.float32)),
+              "el_amf_perturbed_tables")
+        self._stand_aside(False)
+        return self._Pu, self._Pi
+
 
 # ------------------------------------------------------------------------------------------
 # graph propagation: LightGCN (graph_based/lightgcn) -- SURVEY 8f N3

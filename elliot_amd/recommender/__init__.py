@@ -32,8 +32,9 @@ from .latent_factor_models.Slim.slim import Slim
 from .latent_factor_models.PureSVD.pure_svd import PureSVD
 from .algebric.slope_one.slope_one import SlopeOne
 from .latent_factor_models.BPRSlim.bprslim import BPRSlim
+from .adversarial.AMF.AMF import AMF
 
 __all__ = ["BaseRecommenderModel", "init_charger", "RecMixin", "BPRMF_batch", "BPRMF", "MultiVAE", "MultiDAE", "NeuMF", "GMF",
            "MF", "PMF", "FunkSVD", "LogisticMatrixFactorization", "LMF", "CML", "MF2020", "LightGCN", "NGCF", "ProxyRecommender",
            "ItemKNN", "UserKNN", "iALS", "WRMF", "EASER", "RP3beta", "Slim", "PureSVD",
-           "AttributeItemKNN", "AttributeUserKNN", "VSM", "KaHFM", "SlopeOne", "BPRSlim", "ItemAutoRec", "UserAutoRec"]
+           "AttributeItemKNN", "AttributeUserKNN", "VSM", "KaHFM", "SlopeOne", "BPRSlim", "ItemAutoRec", "UserAutoRec", "AMF"]

@@ -329,6 +329,54 @@ int el_bprmf_train_step_presorted(el_ctx* ctx, void* stream, const el_bprmf_stat
 /* Step 4: optimiser alone on (Gu, local Gi, local Bi); opt = EL_OPT_ADAM_TF_DENSE or EL_OPT_SGD.  */
 int el_bprmf_apply(el_ctx* ctx, void* stream, const el_bprmf_state* st, float lr, int opt, int32_t step, float lr_t);
 
+/* ---- AMF / APR: adversarial BPR-MF (adversarial/AMF/AMF_model.py; el_amf.hip) ---------------------------------------------
+ * The model is an el_bprmf_state with the DENSE accumulators (gGu / gGi / gBi given, no Gu_last / Gi_last) plus two
+ * perturbation tables that are not trained.  Entry points only: the struct and the ABI version of the BPR step do not change.
+ * Notation: x(a, b, c) = beta_i - beta_j + a . (b - c); l(x) = softplus(-clip(x, -80, 1e8)); s(x) = sigma(-x) where the clip
+ * passes the gradient (inclusive at -80), else 0; a tilde marks a row gathered from theta + delta.                          */
+typedef struct el_amf_delta {
+    float* dGu;        /* [U,F] perturbation of the user table, zero outside the listed rows (AMF_model.py:46) */
+    float* dGi;        /* [I,F] perturbation of the item table                                 (AMF_model.py:48) */
+    int32_t* rows_u;   /* [U] user rows whose perturbation may be non-zero                                        */
+    int32_t* rows_i;   /* [I] item rows                                                                            */
+    int32_t* counts;   /* device int32[2]: entries of rows_u, rows_i.  All-zero tables with zero counts = no perturbation */
+} el_amf_delta;
+
+enum {
+    EL_AMF_ADVERSARIAL = 1  /* el_amf_grads: add l_adv * sum l(x) on the plain rows and rebuild delta by FGSM (train_step(user_adv_train=True)) */
+};
+
+/* Scratch of el_amf_grads / el_amf_perturb for a batch of B triplets (0 = bad arguments). */
+size_t el_amf_ws_bytes(int64_t B, int64_t U, int64_t I, int32_t F);
+
+/* Replaces: the loss and tape.gradient of AMF_model.train_step (AMF_model.py:70-102); el_bprmf_apply is :103.
+ *   L = sum l(x~) + l_w/2 sum(|u~|^2 + |i~|^2 + |j~|^2) + l_b/2 sum beta_i^2 + l_b/20 sum beta_j^2    [+ l_adv sum l(x)]
+ * The summed row gradients of the batch (delta is a constant) go to gGu / gGi / gBi -- zero on entry, left as el_bprmf_grads
+ * leaves them --, the batch loss is ADDED to loss_out (device double[1]; a sum of per-workgroup partials, as
+ * el_bprmf_deterministic documents).  With EL_AMF_ADVERSARIAL the gradients read the delta of the PREVIOUS call, and delta is then
+ * rebuilt as eps * normalize(g) per row, g = the gradient of the plain loss at the plain rows of this batch (build_perturbation,
+ * :133-161): rows of the previous batch that are not in this one become zero.  Every row sum runs in sorted batch order without
+ * floating-point atomics: the same input gives the same bytes in the gradients and in delta.  Any F in 1 .. 512, any B >= 1.
+ * ws: el_amf_ws_bytes(B, U, I, F).                                                                                           */
+int el_amf_grads(el_ctx* ctx, void* stream, const el_bprmf_state* st, const el_amf_delta* d,
+                 const int32_t* u, const int32_t* i, const int32_t* j, int64_t B,
+                 float l_w, float l_b, float l_adv, float eps, int flags, double* loss_out, void* ws, size_t ws_bytes);
+
+/* Replaces: build_perturbation (nb_iter == 0; AMF_model.py:133-161) and build_msap_perturbation (nb_iter >= 1; :163-197):
+ * delta := 0, then FGSM as above, or nb_iter rounds of delta = clip(delta + eps_iter * normalize(g), -eps, eps) with g the
+ * gradient of the regularised loss at theta + delta.  Reads theta, writes delta and its row lists; the accumulators of `st` are
+ * scratch (zero on entry, zero on exit); the optimiser state is not touched.                                                  */
+int el_amf_perturb(el_ctx* ctx, void* stream, const el_bprmf_state* st, const el_amf_delta* d,
+                   const int32_t* u, const int32_t* i, const int32_t* j, int64_t B,
+                   float l_w, float l_b, float eps, float eps_iter, int32_t nb_iter, void* ws, size_t ws_bytes);
+
+/* delta := 0 by its row lists (only U, I, F of `st` are read). */
+int el_amf_delta_clear(el_ctx* ctx, void* stream, const el_bprmf_state* st, const el_amf_delta* d);
+
+/* Gu_out = Gu + dGu, Gi_out = Gi + dGi in fp32 -- what predict(adversarial=True) multiplies (AMF_model.py:110-111); the
+ * scratch tables then go through el_score_topk / el_score_rank.                                                           */
+int el_amf_perturbed_tables(el_ctx* ctx, void* stream, const el_bprmf_state* st, const el_amf_delta* d, float* Gu_out, float* Gi_out);
+
 /* ---- BPR-MF, NumPy semantics (BPRMF; K5) ------------------------------------- */
 
 typedef struct el_bprsgd_state {
