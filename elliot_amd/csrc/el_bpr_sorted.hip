@@ -61,8 +61,8 @@ struct SegParams {
     float l_w, l_b;
     int32_t step;
     double* loss_out;
-    // item segments: gamma_u of triplet b = ubase[uidx[b], :]  (NULL = st.Gu / bu: the user table itself, by user id; the deferred
-    // decay points them at the pre-update rows the user-side kernel left in Gu_old, by segment head position)
+    // item segments: gamma_u of triplet b = ubase[uidx[b], :]  (NULL = st.Gu / bu: the user table itself, by user id -- every form
+    // of the step leaves the pre-update rows there: the deferred decay's rows trail their last Adam move, see k_bpr_user_seg)
     const float* ubase;
     const int32_t* uidx;
 };
@@ -71,12 +71,10 @@ struct FusedParams {
     const int32_t* rowptr;    // [U + 1]
     float* Gu_new;            // [U, F]: the updated user rows (Gu keeps the pre-update values for the item segments)
     float lr_t, b1, b2, eps;
-    // deferred decay (el_bprmf_state.Gu_last): only the rows with triplets in the batch are read; their missed gradient-free steps
-    // (last, t - 1] are replayed in registers first, the caught-up row goes to old_rows[head position] for the item segments
-    // (hpos[b] = that position, per triplet) and theta is updated IN PLACE
+    // deferred decay (el_bprmf_state.Gu_last): only the rows with triplets in the batch are read; the move they still owe and their
+    // missed gradient-free steps (last, t - 1] are taken in registers first, the caught-up row goes back to Gu -- where the item
+    // segments read it -- and m, v take this step: theta now trails them by this step's move (Gu_last = ~t)
     int32_t* last;            // [U]
-    float* old_rows;          // [>= B, F]
-    int32_t* hpos;            // [B]
     float* hist;              // lr_t of step s at hist[s & hist_mask]
     int hist_mask;
     int32_t t;                // this optimiser step
@@ -87,8 +85,13 @@ struct FusedParams {
 // gradient-free steps (last, t - 1] are taken in registers when its segment starts (SER: in closed form, el_adam_series_*;
 // otherwise step by step, the same bits as the every-row pass); a group owns every segment whose head lies in its chunk (the compact
 // rule below), and where the two-kernel form writes the gradient row, this form takes Keras' Adam step on the row right away:
-// m, v (fetched when the segment starts) and theta updated IN PLACE, the pre-update theta left in old_rows[head] for the item
-// segments, hpos[b] = head for every triplet of the segment, Gu_last[user] = t.  Work proportional to B, whatever U is.
+// m, v (fetched when the segment starts) updated IN PLACE.  Theta TRAILS them by one move: Keras' move theta -= (lr_t m) / (sqrt(v) + eps)
+// is computed from the already updated m and v, both stored as fp32, and lr_t stays in the lr ring -- so the move can be taken at the
+// row's next touch (here, or in the flush) from what is in memory and give the same fp32 value.  What goes to Gu is therefore the
+// caught-up PRE-update row, which is what the item segments of this step gather (by user id, in place: no copy of the row, no
+// per-triplet index), and Gu_last[user] = ~t says "m, v current at t, theta as before the move of step t, that move owed".  A
+// segment head with a negative stamp ~s takes the owed move with hist[s] first, then the replay of (s, t - 1] as before.
+// Work proportional to B, whatever U is.
 // DEFER, PRE (round 5): the Adam slots m, v of a segment head and its Gu_last stamp are fetched TOGETHER with the row gathers of the
 // SUB positions in flight (a position is a head when its key differs from the one in front of it: known from the staged keys before
 // any row arrives) -- at 10 M users nearly every position of a 1 M-triplet batch starts a segment, and fetching m, v only once the
@@ -122,6 +125,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SER && CPL
         float gu[CPL][VW], acc[CPL][VW];
         float mrow[DEFER ? CPL : 1][VW], vrow[DEFER ? CPL : 1][VW];
         int cnt = 0;
+        bool thmoved = false;      // (group-uniform) the head's theta differs from what Gu holds: an owed move or a replay was taken
         auto flush = [&](bool ends_inside) {
             if (DEFER) {
                 const float omb1 = 1.0f - f.b1, omb2 = 1.0f - f.b2;
@@ -130,20 +134,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SER && CPL
                 for (int q = 0; q < CPL; ++q) {
                     const int e = (sub + q * lpt) * VW;
                     if (e < F) {
-                        float tn[VW], mn[VW], vn[VW];
+                        float mn[VW], vn[VW];
 #pragma unroll
                         for (int x = 0; x < VW; ++x) {
                             const float g = acc[q][x] + w * gu[q][x];
-                            tn[x] = gu[q][x], mn[x] = mrow[DEFER ? q : 0][x], vn[x] = vrow[DEFER ? q : 0][x];
-                            el_adam_elem(tn[x], mn[x], vn[x], g, f.lr_t, f.b1, f.b2, omb1, omb2, f.eps);
+                            mn[x] = mrow[DEFER ? q : 0][x], vn[x] = vrow[DEFER ? q : 0][x];
+                            el_adam_slots(mn[x], vn[x], g, f.b1, f.b2, omb1, omb2);
                         }
-                        stv<VW>(f.old_rows + head * F + e, gu[q]);          // the pre-update row, for the item segments
-                        stv<VW>(p.st.Gu + cur * F + e, tn);
+                        if (thmoved) stv<VW>(p.st.Gu + cur * F + e, gu[q]);  // the pre-update row: this step's move stays owed
                         stv<VW>(p.st.mGu + cur * F + e, mn);
                         stv<VW>(p.st.vGu + cur * F + e, vn);
                     }
                 }
-                if (sub == 0) f.last[cur] = f.t;
+                if (sub == 0) f.last[cur] = ~f.t;
                 return;
             }
             float* g = compact ? p.st.gGu_rows + head * F : p.st.gGu + cur * F;
@@ -274,8 +277,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SER && CPL
                                     }
                                 }
                             }
+                            // a negative stamp ~s: theta still owes the move of step s (m, v are already there)
+                            const bool owed = lastv < 0;
+                            if (owed) {
+                                lastv = ~lastv;
+                                const float lro = f.hist[lastv & f.hist_mask];
+#pragma unroll
+                                for (int q = 0; q < CPL; ++q)
+#pragma unroll
+                                    for (int x = 0; x < VW; ++x) el_adam_move(gu[q][x], mrow[DEFER ? q : 0][x], vrow[DEFER ? q : 0][x], lro, f.eps);
+                            }
                             // the row's postponed gradient-free steps (last, t - 1], in registers, before anything uses it
                             const int nsr = (f.t - 1) - lastv;
+                            thmoved = owed || nsr > 0;
                             if (nsr > 0) {
                                 bool nz = false;
 #pragma unroll
@@ -296,7 +310,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SER && CPL
                             }
                         }
                     }
-                    if (DEFER && sub == 0) f.hpos[b] = (int32_t)head;
                     float sb = 0.f;
                     if (p.cml) {
                         sb = 2.0f * p.s[b];                          // d|u-j|^2/du - d|u-i|^2/du = 2 (i - j), times dloss/dD_b
@@ -526,12 +539,16 @@ __global__ __launch_bounds__(256) void k_bpr_user_adam(SegParams p, FusedParams 
 // One waiting row brought forward ns steps by a whole wave: elements e = (lane + 64 q) VW, all 64 lanes on the same gap (the item
 // catch-up kernel: one wave per sorted position, the wave on a segment head owns the row; the flush walks for rows wider than one
 // pass of the wave).  m = v = 0 (a row that never had a gradient) is a fixed point of the gradient-free step: nothing to do.
-template <int VW, bool SER>
+// TRAIL (the user table, whose theta may trail m and v by one move: k_bpr_user_seg): `owed` = the move of step `last` is taken first,
+// ns may then be 0 -- theta alone is written.  Without TRAIL this is the code it was (the item rows: stamps never negative).
+template <int VW, bool SER, bool TRAIL = false>
 __device__ __forceinline__ void bpr_replay_row(float* __restrict__ tth, float* __restrict__ tm, float* __restrict__ tv, int F, int64_t row, int lane,
-                                               int last, int ns, const float* __restrict__ hist, int hist_mask) {
+                                               int last, int ns, const float* __restrict__ hist, int hist_mask, bool owed = false) {
     auto lrs = [&](int s) { return hist[(last + 1 + s) & hist_mask]; };
     el_series sr;
-    if (SER) sr = el_adam_series_sums(ns, lrs);                  // (wave-uniform: once per row)
+    if (SER && (!TRAIL || ns > 0)) sr = el_adam_series_sums(ns, lrs);                  // (wave-uniform: once per row)
+    float lro = 0.f;
+    if (TRAIL && owed) lro = hist[last & hist_mask];
     for (int f0 = 0; f0 < F; f0 += 64 * VW) {
         const int e = f0 + lane * VW;
         float th[VW], mm[VW], vv[VW];
@@ -545,13 +562,21 @@ __device__ __forceinline__ void bpr_replay_row(float* __restrict__ tth, float* _
         bool nz = false;
 #pragma unroll
         for (int x = 0; x < VW; ++x) nz = nz || mm[x] != 0.f || vv[x] != 0.f;
-        if (__ballot(nz) == 0ull) continue;                     // this chunk of the row is at its fixed point
-        if (SER) el_adam_series_apply<VW>(th, mm, vv, sr);
-        else el_adam_replay<VW>(th, mm, vv, ns, lrs);
+        if (__ballot(nz) == 0ull) continue;                     // this chunk of the row is at its fixed point (an owed move is zero there)
+        if (TRAIL && owed) {
+#pragma unroll
+            for (int x = 0; x < VW; ++x) el_adam_move(th[x], mm[x], vv[x], lro, 1e-7f);
+        }
+        if (!TRAIL || ns > 0) {
+            if (SER) el_adam_series_apply<VW>(th, mm, vv, sr);
+            else el_adam_replay<VW>(th, mm, vv, ns, lrs);
+        }
         if (e < F) {
             stv<VW>(tth + row * F + e, th);
-            stv<VW>(tm + row * F + e, mm);
-            stv<VW>(tv + row * F + e, vv);
+            if (!TRAIL || ns > 0) {
+                stv<VW>(tm + row * F + e, mm);
+                stv<VW>(tv + row * F + e, vv);
+            }
         }
     }
 }
@@ -562,21 +587,31 @@ __device__ __forceinline__ void bpr_replay_row(float* __restrict__ tth, float* _
 // consecutive rows: their stamps in ONE coalesced load (lane = row), the pending rows by ballot, then the pending rows NR at a time --
 // their theta / m / v in flight together -- each replayed for its own gap exactly as bpr_replay_row does (same element order, same
 // arithmetic: the bit-for-bit tests of the deferred decay cover it).  Rows wider than one pass of the wave (F > 64 VW) keep the old walk.
-template <int VW, int NR, bool SER>
+// TRAIL (the user table): a stamp ~s < 0 is a row whose m, v are current at s and whose theta still owes the move of step s
+// (k_bpr_user_seg).  Such a row is pending even when s == t: the owed move first, then the t - s steps (possibly none: theta alone is
+// written), and the stamp that goes back is t, never negative.  Without TRAIL -- the item table -- this compiles to the code it was.
+// own(row, last): what a pending row's lane does on its own before the rows are walked and stamped (the item rows' biases).
+template <int VW, int NR, bool SER, bool TRAIL, typename OWN>
 __device__ __forceinline__ void bpr_flush_rows64(float* __restrict__ tth, float* __restrict__ tm, float* __restrict__ tv, int32_t* __restrict__ last_arr,
-                                                 int F, int64_t n_rows, int64_t row0, int lane, int32_t t, const float* __restrict__ hist, int hist_mask) {
+                                                 int F, int64_t n_rows, int64_t row0, int lane, int32_t t, const float* __restrict__ hist, int hist_mask,
+                                                 OWN own) {
     const int64_t myrow = row0 + lane;
-    const int mylast = myrow < n_rows ? last_arr[myrow] : t;
-    unsigned long long pend = __ballot(t - mylast > 0);
+    const int myraw = myrow < n_rows ? last_arr[myrow] : t;
+    const bool myowed = TRAIL && myraw < 0;
+    const int mylast = myowed ? ~myraw : myraw;
+    const bool mypend = t - mylast > 0 || myowed;
+    unsigned long long pend = __ballot(mypend);
     if (pend == 0ull) return;
+    if (mypend) own(myrow, mylast);
     if (F > 64 * VW) {                                          // several passes per row: one row at a time
         while (pend) {
             const int l = __builtin_ctzll(pend);
             pend &= pend - 1;
             const int last = __shfl(mylast, l, 64);
-            bpr_replay_row<VW, SER>(tth, tm, tv, F, row0 + l, lane, last, t - last, hist, hist_mask);
+            const bool owed = TRAIL && __shfl((int)myowed, l, 64) != 0;
+            bpr_replay_row<VW, SER, TRAIL>(tth, tm, tv, F, row0 + l, lane, last, t - last, hist, hist_mask, owed);
         }
-        if (t - mylast > 0) last_arr[myrow] = t;
+        if (mypend) last_arr[myrow] = t;
         return;
     }
     const int e = lane * VW;
@@ -607,20 +642,29 @@ __device__ __forceinline__ void bpr_flush_rows64(float* __restrict__ tth, float*
         for (int r = 0; r < NR; ++r) {
             if (!on[r]) continue;                              // (wave-uniform)
             const int lastr = __shfl(mylast, ls[r], 64);
+            const bool owedr = TRAIL && __shfl((int)myowed, ls[r], 64) != 0;
             bool nz = false;
 #pragma unroll
             for (int x = 0; x < VW; ++x) nz = nz || mm[r][x] != 0.f || vv[r][x] != 0.f;
             if (__ballot(nz) == 0ull) continue;                // (m = v = 0: the fixed point of the step, nothing to replay or write)
-            el_adam_catchup<VW, SER>(th[r], mm[r], vv[r], t - lastr, [&](int s2) { return hist[(lastr + 1 + s2) & hist_mask]; });
+            if (TRAIL && owedr) {
+                const float lro = hist[lastr & hist_mask];
+#pragma unroll
+                for (int x = 0; x < VW; ++x) el_adam_move(th[r][x], mm[r][x], vv[r][x], lro, 1e-7f);
+            }
+            const bool steps = !TRAIL || t - lastr > 0;       // (wave-uniform)
+            if (steps) el_adam_catchup<VW, SER>(th[r], mm[r], vv[r], t - lastr, [&](int s2) { return hist[(lastr + 1 + s2) & hist_mask]; });
             if (live) {
                 const int64_t row = row0 + ls[r];
                 stv<VW>(tth + row * F + e, th[r]);
-                stv<VW>(tm + row * F + e, mm[r]);
-                stv<VW>(tv + row * F + e, vv[r]);
+                if (steps) {
+                    stv<VW>(tm + row * F + e, mm[r]);
+                    stv<VW>(tv + row * F + e, vv[r]);
+                }
             }
         }
     }
-    if (t - mylast > 0) last_arr[myrow] = t;
+    if (mypend) last_arr[myrow] = t;
 }
 
 // deferred decay: every user row up to step t (a wave per 64 consecutive rows, grid-stride)
@@ -628,13 +672,14 @@ template <int VW, int NR, bool SER>
 __global__ __launch_bounds__(256) void k_bpr_flush_users(el_bprmf_state st, int32_t t, const float* __restrict__ hist, int hist_mask) {
     const int lane = threadIdx.x & 63;
     for (int64_t row0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; row0 < st.U; row0 += (int64_t)gridDim.x * 256)
-        bpr_flush_rows64<VW, NR, SER>(st.Gu, st.mGu, st.vGu, st.Gu_last, st.F, st.U, row0, lane, t, hist, hist_mask);
+        bpr_flush_rows64<VW, NR, SER, true>(st.Gu, st.mGu, st.vGu, st.Gu_last, st.F, st.U, row0, lane, t, hist, hist_mask, [](int64_t, int) {});
 }
 
 // ---- fused item side (el_bprmf_state.Gi_last): replay kernels of the item table --------------------------------------------------
 // The item rows are the user rows' case again (k_bpr_catchup / k_bpr_flush_users) plus one bias element per row.  A wave replays
-// a row's factors; the biases are replayed by their own small kernel, one LANE per row (64 rows' gaps per wave instead of one
-// whole wave walking a single element), launched BEFORE the row kernel, which is the one that advances Gi_last.
+// a row's factors; the biases are replayed one LANE per row (64 rows' gaps per wave instead of one whole wave walking a single
+// element) BEFORE the rows advance Gi_last: by their own small kernel in front of the catch-up, by the lane that holds the row's
+// stamp inside the flush.
 template <bool SER>
 __device__ __forceinline__ void bpr_replay_bias(const el_bprmf_state& st, int64_t row, int last, int ns, const float* __restrict__ hist,
                                                 int hist_mask) {
@@ -682,22 +727,14 @@ __global__ __launch_bounds__(256) void k_bpr_catchup_items(el_bprmf_state st, co
     if (lane == 0) st.Gi_last[row] = t - 1;
 }
 
-// every item row (bias: one lane per row; factors: one wave per row, grid-stride) up to step t (lr_t of step t is in the ring: the
-// fused item-segment kernel of that step put it there)
-template <bool SER>
-__global__ __launch_bounds__(256) void k_bpr_flush_ibias(el_bprmf_state st, int32_t t, const float* __restrict__ hist, int hist_mask) {
-    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (row >= st.I) return;
-    const int last = st.Gi_last[row];
-    const int ns = t - last;
-    if (ns > 0) bpr_replay_bias<SER>(st, row, last, ns, hist, hist_mask);
-}
-
+// every item row (a wave per 64 consecutive rows, grid-stride: each lane its own row's bias, then the factors as in the user flush) up
+// to step t (lr_t of step t is in the ring: the fused item-segment kernel of that step put it there)
 template <int VW, int NR, bool SER>
 __global__ __launch_bounds__(256) void k_bpr_flush_items(el_bprmf_state st, int32_t t, const float* __restrict__ hist, int hist_mask) {
     const int lane = threadIdx.x & 63;
     for (int64_t row0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; row0 < st.I; row0 += (int64_t)gridDim.x * 256)
-        bpr_flush_rows64<VW, NR, SER>(st.Gi, st.mGi, st.vGi, st.Gi_last, st.F, st.I, row0, lane, t, hist, hist_mask);
+        bpr_flush_rows64<VW, NR, SER, false>(st.Gi, st.mGi, st.vGi, st.Gi_last, st.F, st.I, row0, lane, t, hist, hist_mask,
+                                             [&](int64_t row, int last) { bpr_replay_bias<SER>(st, row, last, t - last, hist, hist_mask); });
 }
 
 // ---- item segments -----------------------------------------------------------------------
@@ -731,6 +768,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     const int64_t grp = gid / lpt;
     const int sub = (int)(threadIdx.x & (lpt - 1));
     if (IFUSE && gid == 0) f.hist[f.t & f.hist_mask] = f.lr_t;
+    if (gid == 0) *f.split_long = 0;       // the combine kernels' counter of long cut segments: they follow on the stream, nothing here reads it
     const int64_t p0 = grp * p.chunk;
     if (p0 >= p.n) return;
     const int64_t p1 = (p0 + p.chunk < p.n) ? p0 + p.chunk : p.n;
@@ -984,7 +1022,6 @@ struct SortedWs {
     void* tmp;
     size_t tmp_bytes;
     int32_t* rowptr;       // [U + 1] first sorted position of every user row (fused user-side kernel)
-    int32_t* hpos;         // [B] per triplet: sorted head position of its user's segment (deferred decay)
     int32_t* split_long;   // the cut item segments k_seg_combine hands on to k_seg_combine_long (SegParts)
     float* part;           // [2 (B / 8 + 1), F] + [2 (B / 8 + 1)]: partial rows and bias parts of the cut item segments (NULL when carved without F)
     float* part_b;
@@ -1011,7 +1048,6 @@ static int carve_ws(int64_t B, int64_t U, int64_t I, void* base, SortedWs* w, in
     w->tmp_bytes = t1 > t2 ? t1 : t2;
     w->tmp = c.take<char>(w->tmp_bytes);
     w->rowptr = c.take<int32_t>((size_t)(U + 1));
-    w->hpos = c.take<int32_t>((size_t)B);
     w->split_long = c.take<int32_t>((size_t)(2 * (B / 8 + 4) + 4));
     w->part = w->part_b = nullptr;
     if (F > 0) {                                         // (lane groups: at most 2 B / 16 -- item_chunk_for never goes below 16 positions)
@@ -1180,13 +1216,10 @@ static int launch_flush_items(const el_bprmf_state& st, hipStream_t s, int32_t t
     const int mask = st.lr_hist_cap - 1;
     int64_t grid = (st.I + 255) / 256;                       // a wave owns 64 consecutive rows
     if (grid > (1 << 18)) grid = 1 << 18;
-    const dim3 gb((unsigned)((st.I + 255) / 256));
 #define EL_FI(VW_, SER_) EL_LAUNCH("k_bpr_flush_items", (k_bpr_flush_items<VW_, 2, SER_>), dim3((unsigned)grid), dim3(256), 0, s, st, t, st.lr_hist, mask)
     if (st.replay_series) {
-        EL_LAUNCH("k_bpr_flush_ibias", k_bpr_flush_ibias<true>, gb, dim3(256), 0, s, st, t, st.lr_hist, mask);
         if (st.F >= 256) EL_FI(4, true); else if (st.F >= 128) EL_FI(2, true); else EL_FI(1, true);
     } else {
-        EL_LAUNCH("k_bpr_flush_ibias", k_bpr_flush_ibias<false>, gb, dim3(256), 0, s, st, t, st.lr_hist, mask);
         if (st.F >= 256) EL_FI(4, false); else if (st.F >= 128) EL_FI(2, false); else EL_FI(1, false);
     }
 #undef EL_FI
@@ -1240,7 +1273,7 @@ static int launch_user_adam(const SegParams& pu, hipStream_t s, int64_t B, const
 static void defer_params(const SegParams& pu, const SortedWs& w, float lr_t, FusedParams* f) {
     memset(f, 0, sizeof(*f));
     f->lr_t = lr_t, f->b1 = 0.9f, f->b2 = 0.999f, f->eps = 1e-7f;
-    f->last = pu.st.Gu_last, f->old_rows = pu.st.Gu_old, f->hpos = w.hpos;
+    f->last = pu.st.Gu_last;
     f->hist = pu.st.lr_hist, f->hist_mask = pu.st.lr_hist_cap - 1, f->t = pu.step;
 }
 
@@ -1263,7 +1296,7 @@ static int launch_segs(const SegParams& base, hipStream_t s, int64_t B, const So
     pi.n = 2 * B;
     pi.chunk = item_chunk_for(B, base.st.I);
     pi.lpt = lpt;
-    if (defer) pi.ubase = base.st.Gu_old, pi.uidx = w.hpos;      // the pre-update user rows, one per distinct user of the batch
+    // (pi.ubase / pi.uidx stay NULL in every form: with the deferred decay too the pre-update user rows are in Gu itself)
     const int64_t gu = (B + pu.chunk - 1) / pu.chunk, gi = (2 * B + pi.chunk - 1) / pi.chunk;
     const unsigned gridU = (unsigned)((gu * lpt + 255) / 256), gridI = (unsigned)((gi * lpt + 255) / 256);
     // (7 words per staged position where the heads' Gu_last stamps ride along: the PRE instantiations)
@@ -1297,7 +1330,6 @@ static int launch_segs(const SegParams& base, hipStream_t s, int64_t B, const So
         } else {                                                                                          \
             EL_LAUNCH("k_bpr_user_seg", (k_bpr_user_seg<VW, CPL_, false>), dim3(gridU), dim3(256), ldsU, s, pu, fz);  \
         }                                                                                                 \
-        EL_CHECK_HIP(hipMemsetAsync(w.split_long, 0, 4, s));                                              \
         if (ifuse && VW == 4 && CPL_ <= 2) {                                                              \
             constexpr bool IF_ = VW == 4 && CPL_ <= 2;                                                    \
             EL_LAUNCH("k_bpr_item_seg", (k_bpr_item_seg<VW, CPL_, IF_>), dim3(gridI), dim3(256), ldsI, s, pi, fi);   \
@@ -1361,9 +1393,12 @@ static int sorted_step(el_ctx* ctx, void* stream, const el_bprmf_state* stp, con
                    "el_bprmf_sync_users; gradient-only / other-optimiser calls take a state with Gu_last = NULL after that sync");
         if (int rc = check_deferred(st)) return rc;
         EL_REQUIRE(vec && !rows_mode && cplq <= 2, "el_bprmf_train_step: deferred decay needs F %% 4 == 0, F <= 512 and 16-byte aligned tables");
-        EL_REQUIRE(st.Gu_old != nullptr && st.Gu_old_cap >= B && ((uintptr_t)st.Gu_old & 15) == 0,
-                   "el_bprmf_train_step: deferred decay needs Gu_old with >= B rows (%lld < %lld)", (long long)st.Gu_old_cap, (long long)B);
-        // the lr history is a ring: no row may fall more than half of it behind
+        // the lr history is a ring: no row may fall more than half of it behind.  With c = lr_hist_cap / 2 the flush below runs in
+        // front of every step k c + 1 and leaves every stamp at k c, non-negative.  Until the next one, at steps t in [k c + 1, k c + c],
+        // a replay reads hist[s + 1 .. t - 1] for a stamp s >= k c, and an owed move reads hist[s] for a stamp ~s -- written by the
+        // user segments of a step s >= k c + 1, after that flush.  Both stay inside [k c + 1, t - 1], the entries a replay read
+        // before rows trailed; the flush itself reads up to hist[k c + c]: at most c <= lr_hist_cap distinct slots, none of them the
+        // slot hist[t] that step t writes (t - (k c + 1) < c).  A sync at any other step only raises the stamps.  Holds for cap >= 4.
         if (step > 1 && (step - 1) % (st.lr_hist_cap / 2) == 0)
             if (int rc = launch_flush_users(st, s, step - 1)) return rc;
     }
@@ -1662,7 +1697,6 @@ extern "C" int el_bprmf_shard_grads(el_ctx* ctx, void* stream, const el_bprmf_st
     ItemFuse fi;
     memset(&fi, 0, sizeof(fi));
     fi.split_long = w.split_long, fi.part = w.part, fi.part_b = w.part_b;
-    EL_CHECK_HIP(hipMemsetAsync(w.split_long, 0, 4, s));
     const SegParts sp = {pi.keys, pi.key_off, pi.n, pi.chunk, lpt, pi.st.F, fi.split_long, fi.part, fi.part_b};
     const ItemFinish<false> fin = item_finish<false>(pi.st, fi);
     const unsigned gridC = gridI, gridL = (unsigned)(gi < 1024 ? (gi < 1 ? 1 : gi) : 1024);

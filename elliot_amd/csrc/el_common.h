@@ -418,11 +418,19 @@ __host__ __device__ inline el_philox4 el_philox4x32_10(u32 c0, u32 c1, u32 c2, u
 
 // Keras-2.3 Adam, sparse-apply arithmetic, one element:
 //   m <- m*b1 ; m += g*(1-b1) ; v <- v*b2 ; v += (g*g)*(1-b2) ; theta -= (lr_t*m)/(sqrt(v)+eps)
-__device__ __forceinline__ void el_adam_elem(float& th, float& m, float& v, float g, float lr_t, float b1, float b2,
-                                             float omb1, float omb2, float eps) {
+// The two halves apart: the slots, and the move theta takes from the UPDATED slots.  m and v are stored as fp32, so the move can be
+// taken later from what is in memory and give the same fp32 value (the trailing user rows of the deferred decay: el_bpr_sorted.hip).
+__device__ __forceinline__ void el_adam_slots(float& m, float& v, float g, float b1, float b2, float omb1, float omb2) {
     m = m * b1 + g * omb1;
     v = v * b2 + (g * g) * omb2;
+}
+__device__ __forceinline__ void el_adam_move(float& th, float m, float v, float lr_t, float eps) {
     th = th - (lr_t * m) / (sqrtf(v) + eps);
+}
+__device__ __forceinline__ void el_adam_elem(float& th, float& m, float& v, float g, float lr_t, float b1, float b2,
+                                             float omb1, float omb2, float eps) {
+    el_adam_slots(m, v, g, b1, b2, omb1, omb2);
+    el_adam_move(th, m, v, lr_t, eps);
 }
 
 // ---- the gradient-free Adam step of the deferred decay on packed fp32 instructions -------------------------------------------

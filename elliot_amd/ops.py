@@ -2379,10 +2379,9 @@ class BprmfDeviceState:
             self._c.Gu_next = self.Gu_next.data_ptr()
 
     def _ensure_old(self, B):
+        """(The deferred decay once kept a copy of the batch's pre-update user rows, Gu_old: the rows now trail their last Adam move
+        in Gu itself and the item side reads them there.  What is left is the choice of the form for this batch size.)"""
         self._resolve_deferred(B)
-        if self.deferred and (self.Gu_old is None or self.Gu_old.shape[0] < B):
-            self.Gu_old = torch.empty((int(B), self.F), dtype=torch.float32, device=self.ctx.device)
-            self._c.Gu_old, self._c.Gu_old_cap = self.Gu_old.data_ptr(), int(B)
 
     def _swap_user_tables(self, steps=1):
         """After `steps` fused train steps the current user table is the other one of the pair (include/elliot_hip.h, Gu_next)."""

@@ -185,12 +185,16 @@ typedef struct el_bprmf_state {
      * the same fp32 operations on the same operands in the same order, hence the same bits -- when a batch next contains the user
      * (inside the fused user-side kernel, before the row is used) or when el_bprmf_sync_users is called.  A step then moves only
      * the rows of the batch's users: at 10 M users and 1 M triplets per batch a tenth of the 15 GB the every-row pass streams.
-     * Every (element, step) update is still performed exactly once.  The update is IN PLACE (Gu_next is not used); the item-side
-     * gradients read the pre-update user rows from Gu_old, where the user-side kernel leaves one row per distinct user of the batch.
+     * Every (element, step) update is still performed exactly once.  The update is IN PLACE (Gu_next is not used).  A row the batch
+     * touches gets its m and v of this step at once, but its theta TRAILS them by this step's move: Gu keeps the caught-up
+     * pre-update row, which is what the item-side gradients of the step read (by user id, no copy of the row), and the move --
+     * computed from the stored m, v and lr_hist, the same fp32 value -- is taken when the row is next touched or synced.
      * Needs EL_OPT_ADAM_TF_DENSE, the SORTED gradient path, F % 4 == 0, F <= 512, consecutive `step` values from call to call,
      * and el_bprmf_sync_users(step) before anything else reads Gu / mGu / vGu (el_score_topk, el_bprmf_grads, a checkpoint).
-     *   Gu_last  int32[U], zero-initialised: the optimiser step each user row is current at
-     *   Gu_old   float[Gu_old_cap, F], Gu_old_cap >= the batch size of every step
+     *   Gu_last  int32[U], zero-initialised.  >= 0: the optimiser step theta, m and v of the row are current at.  < 0, s = ~Gu_last:
+     *            m and v are current at step s, theta is the row as it stood before the move of step s, and that move (with
+     *            lr_hist[s % cap]) is owed.  After el_bprmf_sync_users(step) every entry equals step.
+     *   Gu_old, Gu_old_cap   unused (the copy of the batch's pre-update rows earlier versions kept); may be NULL / 0
      *   lr_hist  float[lr_hist_cap], lr_hist_cap a power of two >= 4: the library keeps lr_t of step s at lr_hist[s % cap] and
      *            brings every row up to date by itself every cap / 2 steps                                              */
     int32_t* Gu_last; float* Gu_old; int64_t Gu_old_cap; float* lr_hist; int32_t lr_hist_cap;

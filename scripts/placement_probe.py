@@ -55,7 +55,7 @@ for blk in range(max(1, a.steps // 10)):                     # per-kernel means 
     for n, v in r.items():
         c = rep.get(n, (0, 0.0))
         rep[n] = (c[0] + v[0], c[1] + v[1])
-tabs = {"Gu": st._Gu, "mGu": st.mGu, "vGu": st.vGu, "Gu_old": st.Gu_old, "Gi": st._Gi, "mGi": st.mGi, "vGi": st.vGi, "gGi": st.gGi,
+tabs = {"Gu": st._Gu, "mGu": st.mGu, "vGu": st.vGu, "Gi": st._Gi, "mGi": st.mGi, "vGi": st.vGi, "gGi": st.gGi,
         "Gi_last": st.Gi_last, "Gu_last": st.Gu_last, "ws": st._ws}
 out = {"tag": a.tag, "ms": {n: round(v[1] / v[0], 4) for n, v in rep.items() if n.startswith("k_bpr")},
        "va": {n: hex(x.data_ptr()) for n, x in tabs.items() if x is not None},
