@@ -56,6 +56,11 @@ class AmfDelta(C.Structure):
 EL_AMF_ADVERSARIAL = 1
 
 
+class VbprState(C.Structure):
+    _fields_ = [("mf", BprmfState), ("Tu", _f32p), ("gTu", _f32p), ("mTu", _f32p), ("vTu", _f32p),
+                ("EB", _f32p), ("gEB", _f32p), ("mEB", _f32p), ("vEB", _f32p), ("Feat", _f32p), ("Fd", C.c_int32), ("D", C.c_int64)]
+
+
 class BprsgdState(C.Structure):
     _fields_ = [
         ("P", _f64p), ("Q", _f64p), ("b", _f64p),
@@ -201,6 +206,12 @@ PROTOTYPES = {
                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_size_t]),
     "el_amf_delta_clear": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BprmfState), C.POINTER(AmfDelta)]),
     "el_amf_perturbed_tables": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BprmfState), C.POINTER(AmfDelta), _f32p, _f32p]),
+    "el_vbpr_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64]),
+    "el_vbpr_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(VbprState), _i32p, _i32p, _i32p, C.c_int64, C.c_float, C.c_float,
+                                C.c_float, _f64p, C.POINTER(C.c_int64), C.c_void_p, C.c_size_t]),
+    "el_vbpr_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(VbprState), C.c_float, C.c_int32, C.c_float]),
+    "el_vbpr_image_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64]),
+    "el_vbpr_item_image": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(VbprState), _f32p, _f32p, _f32p, C.c_void_p, C.c_size_t]),
     "el_spmm_csr_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GraphCsr), _f32p, _f32p, C.c_int32, _f32p, _f32p]),
     "el_lightgcn_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "el_lightgcn_propagate": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GraphCsr), _f32p, _f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t]),

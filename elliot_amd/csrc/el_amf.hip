@@ -35,12 +35,6 @@ namespace {
 #define AMF_NEG 0x80000000u
 #define AMF_STG 32
 
-__device__ __forceinline__ float amf_softplus(float x) {            // tf.nn.softplus
-    if (x > 15.0f) return x + expf(-x);
-    if (x < -15.0f) return expf(x);
-    return log1pf(expf(x));
-}
-
 struct AmfFwd {
     const float *Gu, *Gi, *Bi, *dGu, *dGi;   // dGu == nullptr: the plain rows stand for the perturbed ones
     const int32_t *u, *i, *j;
@@ -108,13 +102,13 @@ __global__ __launch_bounds__(256) void k_amf_fwd(AmfFwd p) {
             const float ct = fminf(fmaxf(xt, -80.0f), 1e8f);
             p.coefT[b] = (xt >= -80.0f && xt <= 1e8f) ? 1.0f / (1.0f + expf(ct)) : 0.f;
             // (the terms of one triplet are added in double: a clipped triplet's 80 would otherwise round the small ones away)
-            double l = (double)amf_softplus(-ct) + (double)(p.l_w * 0.5f * sq) + (double)(p.l_b * 0.5f * bi * bi) +
+            double l = (double)el_softplus_tf(-ct) + (double)(p.l_w * 0.5f * sq) + (double)(p.l_b * 0.5f * bi * bi) +
                        (double)(p.l_b * 0.5f * bj * bj / 10.0f);
             if (p.coefP) {
                 const float xp = (bi + dpi) - (bj + dpj);
                 const float cp = fminf(fmaxf(xp, -80.0f), 1e8f);
                 p.coefP[b] = (xp >= -80.0f && xp <= 1e8f) ? 1.0f / (1.0f + expf(cp)) : 0.f;
-                l += (double)(p.l_adv * amf_softplus(-cp));
+                l += (double)(p.l_adv * el_softplus_tf(-cp));
             }
             lossv += l;
             if (p.key) {

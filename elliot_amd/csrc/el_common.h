@@ -416,6 +416,13 @@ __host__ __device__ inline el_philox4 el_philox4x32_10(u32 c0, u32 c1, u32 c2, u
     return o;
 }
 
+// tf.nn.softplus as the AMF and VBPR forward kernels evaluate it
+__device__ __forceinline__ float el_softplus_tf(float x) {
+    if (x > 15.0f) return x + expf(-x);
+    if (x < -15.0f) return expf(x);
+    return log1pf(expf(x));
+}
+
 // Keras-2.3 Adam, sparse-apply arithmetic, one element:
 //   m <- m*b1 ; m += g*(1-b1) ; v <- v*b2 ; v += (g*g)*(1-b2) ; theta -= (lr_t*m)/(sqrt(v)+eps)
 // The two halves apart: the slots, and the move theta takes from the UPDATED slots.  m and v are stored as fp32, so the move can be

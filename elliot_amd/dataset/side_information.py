@@ -1,8 +1,8 @@
-"""Side information of the data plane: item attributes and knowledge-graph features, narrowed together with the rating frames and
-with each training fold.
+"""Side information of the data plane: item attributes, knowledge-graph features and visual feature vectors, narrowed together
+with the rating frames and with each training fold.
 
-What Elliot's `ItemAttributes` and `ChainedKG` loaders, their coordination and `DataSet`'s alignment with the training fold produce, on this
-package's column frames.  One routine, `_settle`, serves both stages: it intersects the running (users, items) with what every
+What Elliot's `ItemAttributes`, `ChainedKG` and `VisualAttribute` loaders, their coordination and `DataSet`'s alignment with the
+training fold produce, on this package's column frames.  One routine, `_settle`, serves both stages: it intersects the running (users, items) with what every
 loader covers until nothing shrinks any more.
 
 The contract that fixes the results is small.  The feature columns are `list({f for i in items for f in feature_map[i]})`, so their
@@ -16,7 +16,9 @@ and documented where they happen; everything else here is free:
 out its REDUCED map instead (features of the selected properties that occur often enough, items that keep one), reduced again
 every time the loader is narrowed.
 """
+import os
 from collections import Counter
+from concurrent.futures import ThreadPoolExecutor
 from types import SimpleNamespace
 
 import numpy as np
@@ -148,7 +150,87 @@ class ChainedKG:
                                public_features={f: p for p, f in enumerate(features)})
 
 
-LOADERS = {"ItemAttributes": ItemAttributes, "ChainedKG": ChainedKG}
+class VisualAttribute:
+    """A folder of `<item id>.npy` files, one fp32 feature vector per item (visual_attribute.py).  The items are the rated items
+    that have a file.  Their vectors are read ONCE, when the loader is made, by at most 16 threads, into one matrix that every
+    fold shares; the row of an item is the file named by its PUBLIC id on the training path and on the evaluation path alike
+    (DESIGN 3.28 has what the reference does instead).  `feature_matrix(items, device)` hands the rows out in the order asked
+    for -- a data set's private-item order -- from one device copy that is uploaded at the first call."""
+    name = "VisualAttributes"                                    # (the namespace's name in the reference, and VBPR's `loader` default)
+    UNSUPPORTED = ("visual_pca_features", "visual_feat_map_features", "images_src_folder")
+    MAX_READERS = 16
+
+    def __init__(self, users, items, folder, item_mapping, store):
+        self.users, self.items, self.folder, self.item_mapping, self.store = users, items, folder, item_mapping, store
+
+    @classmethod
+    def load(cls, users, items, spec, resolve):
+        for key in cls.UNSUPPORTED:
+            if _get(spec, key):
+                raise Exception(f"side_information: `{key}` of the VisualAttribute loader is not supported by elliot_amd (it serves "
+                                f"the image-based models; VBPR reads `visual_features` only)")
+        folder = _get(spec, "visual_features")
+        folder = resolve(folder) if folder else folder
+        if not folder or not os.path.isdir(folder):
+            raise Exception(f"side_information: the VisualAttribute loader needs `visual_features`, a folder of <item id>.npy files "
+                            f"(got {folder!r}; dataloaders of elliot_amd: {sorted(LOADERS)})")
+        stems = sorted(f[:-4] for f in os.listdir(folder) if f.endswith(".npy") and f[:-4].lstrip("-").isdigit())
+        in_folder = set(int(s) for s in stems)
+        item_mapping = {item: val for val, item in enumerate(in_folder)}          # the reference's field: position in the folder's set
+        mine = items & in_folder                                                  # rated items left, the folder's right
+        return cls(users, mine, folder, item_mapping, cls._read(folder, sorted(mine)))
+
+    @classmethod
+    def _read(cls, folder, ids):
+        """{"ids": ascending public ids, "row": {id: row}, "matrix": fp32 [len(ids), D], "device": {}}; a file whose length is not
+        the common one is refused with its name."""
+        def one(item):
+            return np.asarray(np.load(os.path.join(folder, f"{item}.npy")), dtype=np.float32).reshape(-1)
+        with ThreadPoolExecutor(max_workers=max(1, min(cls.MAX_READERS, os.cpu_count() or 1))) as pool:
+            vectors = list(pool.map(one, ids))
+        lengths = Counter(len(v) for v in vectors)
+        D = lengths.most_common(1)[0][0] if lengths else 0
+        odd = [f"{item}.npy ({len(v)})" for item, v in zip(ids, vectors) if len(v) != D]
+        if odd:
+            raise Exception(f"side_information: visual feature files of another length than {D} in {folder}: {', '.join(odd[:8])}")
+        matrix = np.stack(vectors) if vectors else np.zeros((0, 0), np.float32)
+        return {"ids": list(ids), "row": {item: r for r, item in enumerate(ids)}, "matrix": matrix, "device": {}}
+
+    def for_fold(self):
+        """A loader of its own for one training fold: both sets rebuilt from lists; the matrix and its device copy are shared."""
+        return VisualAttribute(set(list(self.users)), set(list(self.items)), self.folder, self.item_mapping, self.store)
+
+    def get_mapped(self):
+        return self.users, self.items
+
+    def filter(self, users, items):
+        self.users, self.items = self.users & users, self.items & items       # the loader's own sets left
+
+    def feature_matrix(self, items, device=None):
+        """fp32 [len(items), D]: row k is the vector of public item items[k].  device=None: a NumPy array; else a torch tensor on
+        that device, gathered there from the one uploaded copy of the matrix."""
+        missing = [i for i in items if i not in self.items]
+        if missing:
+            raise Exception(f"side_information: no visual features for items {missing[:8]} (not among the loader's items)")
+        rows = np.fromiter((self.store["row"][i] for i in items), dtype=np.int64, count=len(items))
+        if device is None:
+            return self.store["matrix"][rows]
+        import torch
+        key = str(device)
+        if key not in self.store["device"]:
+            self.store["device"][key] = torch.from_numpy(self.store["matrix"]).to(device)
+        whole = self.store["device"][key]
+        if len(rows) == whole.shape[0] and np.array_equal(rows, np.arange(len(rows))):
+            return whole
+        return whole.index_select(0, torch.from_numpy(rows).to(device)).contiguous()
+
+    def namespace(self):
+        """What models read as `data.side_information.VisualAttributes`: the reference's field names plus `feature_matrix`."""
+        return SimpleNamespace(__name__=self.name, object=self, visual_feature_folder_path=self.folder, item_mapping=self.item_mapping,
+                               visual_features_shape=int(self.store["matrix"].shape[1]), feature_matrix=self.feature_matrix)
+
+
+LOADERS = {"ItemAttributes": ItemAttributes, "ChainedKG": ChainedKG, "VisualAttribute": VisualAttribute}
 
 
 def _settle(users, items, loaders):

@@ -2668,6 +2668,87 @@ class AmfDeviceState:
         return self._Pu, self._Pi
 
 
+class VbprDeviceState:
+    """VBPR_model's variables (visual_recommenders/VBPR/VBPR_model.py:40-53): a BprmfDeviceState with the dense accumulators for
+    Gu, Gi, Bi and ONE Adam step counter, plus Tu [U, Fd] and EB = [E | Bp] [D, Fd + 1] with their accumulators and slots, and
+    the item features `feat` [I, D] (a device tensor, shared, never written).  A step is el_vbpr_grads + el_vbpr_apply; scoring
+    goes through the image (P, Q, bq) = ([Gu | Tu], [Gi | feat E], Bi + feat Bp), rebuilt by image() on demand."""
+
+    def __init__(self, ctx, Gu, Gi, Bi, Tu, E, Bp, feat):
+        self.ctx = ctx
+        self.base = BprmfDeviceState(ctx, Gu, Gi, Bi, optimizer="adam", compact_user_grads=False)
+        b, dev = self.base, ctx.device
+        self.U, self.I, self.F = b.U, b.I, b.F
+
+        def own(x):
+            if isinstance(x, np.ndarray):
+                x = torch.from_numpy(np.ascontiguousarray(x))
+            return x.to(device=dev, dtype=torch.float32).contiguous().clone()
+
+        self.Tu = own(Tu)
+        self.Fd = int(self.Tu.shape[1])
+        if not isinstance(feat, torch.Tensor) or feat.device != dev or feat.dtype != torch.float32 or not feat.is_contiguous():
+            raise ValueError("VbprDeviceState: feat must be a contiguous float32 tensor on the context's device")
+        self.feat = feat
+        self.D = int(feat.shape[1])
+        E, Bp = own(E), own(Bp).reshape(-1, 1)
+        if tuple(feat.shape) != (self.I, self.D) or tuple(E.shape) != (self.D, self.Fd) or Bp.shape[0] != self.D \
+                or self.Tu.shape[0] != self.U:
+            raise ValueError("VbprDeviceState: shapes of Tu / E / Bp / feat do not fit")
+        self.EB = torch.cat([E, Bp], dim=1).contiguous()
+        z = torch.zeros_like
+        self.gTu, self.mTu, self.vTu = z(self.Tu), z(self.Tu), z(self.Tu)
+        self.gEB, self.mEB, self.vEB = z(self.EB), z(self.EB), z(self.EB)
+        self._c = _lib.VbprState(mf=b._c, Tu=self.Tu.data_ptr(), gTu=self.gTu.data_ptr(), mTu=self.mTu.data_ptr(),
+                                 vTu=self.vTu.data_ptr(), EB=self.EB.data_ptr(), gEB=self.gEB.data_ptr(), mEB=self.mEB.data_ptr(),
+                                 vEB=self.vEB.data_ptr(), Feat=self.feat.data_ptr(), Fd=self.Fd, D=self.D)
+        self._ws = self._image_ws = self._P = self._Q = self._bq = None
+        self.last_distinct_items = 0
+
+    loss = property(lambda self: self.base.loss)
+    step = property(lambda self: self.base.step)
+    E = property(lambda self: self.EB[:, :self.Fd])
+    Bp = property(lambda self: self.EB[:, self.Fd:])
+
+    def pop_loss(self):
+        return self.base.pop_loss()
+
+    def grads(self, u, i, j, l_w, l_b, l_e):
+        """Loss and tape.gradient of train_step (VBPR_model.py:72-92) into the accumulators; apply() consumes them."""
+        B = int(u.numel())
+        ws = workspace(self, "_ws", int(self.ctx.lib.el_vbpr_ws_bytes(self.ctx.handle, B, self.U, self.I, self.F, self.Fd, self.D)),
+                       self.ctx.device)
+        n = C.c_int64(0)
+        check(self.ctx.lib.el_vbpr_grads(self.ctx.handle, self.ctx.stream(), C.byref(self._c), _ptr(u, torch.int32, "u"),
+                                         _ptr(i, torch.int32, "i"), _ptr(j, torch.int32, "j"), B, float(l_w), float(l_b), float(l_e),
+                                         _ptr(self.base.loss, torch.float64), C.byref(n), _ptr(ws), ws.numel()), "el_vbpr_grads")
+        self.last_distinct_items = int(n.value)
+
+    def apply(self, lr):
+        self.base._advance()
+        check(self.ctx.lib.el_vbpr_apply(self.ctx.handle, self.ctx.stream(), C.byref(self._c), float(lr), int(self.step),
+                                         float(adam_lr_t(lr, self.step))), "el_vbpr_apply")
+
+    def train_step(self, u, i, j, lr, l_w, l_b, l_e):
+        self.grads(u, i, j, l_w, l_b, l_e)
+        self.apply(lr)
+
+    def image(self):
+        """(P, Q, bq) of the current weights: x(u, i) = bq[i] + P[u] . Q[i] (el_vbpr_item_image)."""
+        W = self.F + self.Fd
+        if self._Q is None:
+            dev = self.ctx.device
+            self._P = torch.empty((self.U, W), dtype=torch.float32, device=dev)
+            self._Q = torch.empty((self.I, W), dtype=torch.float32, device=dev)
+            self._bq = torch.empty(self.I, dtype=torch.float32, device=dev)
+        ws = workspace(self, "_image_ws", int(self.ctx.lib.el_vbpr_image_ws_bytes(self.ctx.handle, self.I, self.Fd, self.D)),
+                       self.ctx.device)
+        check(self.ctx.lib.el_vbpr_item_image(self.ctx.handle, self.ctx.stream(), C.byref(self._c), _ptr(self._Q, torch.float32),
+                                              _ptr(self._bq, torch.float32), _ptr(self._P, torch.float32), _ptr(ws), ws.numel()),
+              "el_vbpr_item_image")
+        return self._P, self._Q, self._bq
+
+
 # ------------------------------------------------------------------------------------------
 # graph propagation: LightGCN (graph_based/lightgcn) -- SURVEY 8f N3
 # ------------------------------------------------------------------------------------------

@@ -33,8 +33,10 @@ from .latent_factor_models.PureSVD.pure_svd import PureSVD
 from .algebric.slope_one.slope_one import SlopeOne
 from .latent_factor_models.BPRSlim.bprslim import BPRSlim
 from .adversarial.AMF.AMF import AMF
+from .visual_recommenders.VBPR.VBPR import VBPR
 
 __all__ = ["BaseRecommenderModel", "init_charger", "RecMixin", "BPRMF_batch", "BPRMF", "MultiVAE", "MultiDAE", "NeuMF", "GMF",
            "MF", "PMF", "FunkSVD", "LogisticMatrixFactorization", "LMF", "CML", "MF2020", "LightGCN", "NGCF", "ProxyRecommender",
            "ItemKNN", "UserKNN", "iALS", "WRMF", "EASER", "RP3beta", "Slim", "PureSVD",
-           "AttributeItemKNN", "AttributeUserKNN", "VSM", "KaHFM", "SlopeOne", "BPRSlim", "ItemAutoRec", "UserAutoRec", "AMF"]
+           "AttributeItemKNN", "AttributeUserKNN", "VSM", "KaHFM", "SlopeOne", "BPRSlim", "ItemAutoRec", "UserAutoRec", "AMF",
+           "VBPR"]

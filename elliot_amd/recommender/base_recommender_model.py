@@ -33,7 +33,7 @@ _META_FIELDS = (
 
 # the models whose recommend() is one call on their own tables or score blocks and that carry the matching rank()
 RANK_MODELS = frozenset(("BPRMF_batch", "LightGCN", "NGCF", "PureSVD", "BPRMF", "MF2020", "iALS", "WRMF", "MultiVAE", "MultiDAE",
-                         "EASER", "SlopeOne", "BPRSlim", "AMF"))
+                         "EASER", "SlopeOne", "BPRSlim", "AMF", "VBPR"))
 
 
 def param(key, short, default, read=None, show=None, attr=None):

@@ -3,7 +3,7 @@
 Honours the slice of Elliot's YAML schema (elliot/namespace/namespace_model.py:28-61) that the hello-world style
 experiments use: dataset, data_config {strategy: dataset|fixed, dataset_path | train_path/test_path/validation_path,
 side_information: [{dataloader: ItemAttributes, attribute_file} | {dataloader: ChainedKG, map, features, properties, additive,
-threshold}]}, align_side_with_train, prefiltering, binarize,
+threshold} | {dataloader: VisualAttribute, visual_features}]}, align_side_with_train, prefiltering, binarize,
 splitting {test_splitting, validation_splitting: every strategy of base_splitter.py}, negative_sampling {strategy: random|fixed}, top_k, evaluation {cutoffs, simple_metrics,
 relevance_threshold}, gpu, path_output_rec_*, models {<Model>: {meta: {...}, <hyper-params>}}.
 The full driver (HPO, result handlers, statistical tests: elliot/run.py:39-148) stays Elliot's: plug the models in

@@ -381,6 +381,50 @@ int el_amf_delta_clear(el_ctx* ctx, void* stream, const el_bprmf_state* st, cons
  * scratch tables then go through el_score_topk / el_score_rank.                                                           */
 int el_amf_perturbed_tables(el_ctx* ctx, void* stream, const el_bprmf_state* st, const el_amf_delta* d, float* Gu_out, float* Gi_out);
 
+/* ---- VBPR: BPR over item features (visual_recommenders/VBPR/VBPR_model.py; el_vbpr.hip) ------------------------------------
+ *   x(u, i) = Bi[i] + Gu[u] . Gi[i] + Tu[u] . (f_i E) + f_i . Bp,     f_i = row i of Feat [I, D]
+ * Entry points only: el_bprmf_state and the ABI version of the BPR step do not change.  `mf` holds Gu, Gi, Bi with the DENSE
+ * accumulators and Adam slots (no uslot / Gu_last / Gi_last).  E and Bp are one variable, EB = [E | Bp] [D, Fd + 1] row-major
+ * (column Fd is Bp), so that each of the step's two products carries the bias column along.                                 */
+typedef struct el_vbpr_state {
+    el_bprmf_state mf;
+    float* Tu;  float* gTu; float* mTu; float* vTu;   /* [U, Fd] visual user factors, accumulator (zero on entry and exit), Adam slots */
+    float* EB;  float* gEB; float* mEB; float* vEB;   /* [D, Fd + 1]                                                                  */
+    const float* Feat;                                 /* [I, D] item features, row = item id; never written                           */
+    int32_t Fd;
+    int64_t D;
+} el_vbpr_state;
+
+/* Scratch of el_vbpr_grads for a batch of B triplets (0 = bad arguments). */
+size_t el_vbpr_ws_bytes(el_ctx* ctx, int64_t B, int64_t U, int64_t I, int32_t F, int32_t Fd, int64_t D);
+
+/* Replaces: the loss and tape.gradient of VBPR_model.train_step (VBPR_model.py:70-92).  With s_b = sigma(-x_b) where
+ * clip_by_value(x_b, -80, 1e8) passes the gradient (inclusive at -80) and 0 elsewhere, x_b = x(u, i) - x(u, j):
+ *   L = sum softplus(-clip(x_b)) + l_w/2 sum(|Gu[u]|^2 + |Tu[u]|^2 + |Gi[i]|^2 + |Gi[j]|^2) + l_b/2 sum Bi[i]^2 + l_b/20 sum Bi[j]^2
+ *       + l_e/2 (|E|^2 + |Bp|^2)                                                     (the last term once per step, not per sample)
+ * The summed row gradients go to gGu / gTu / gGi / gBi, the dense gradient to gEB (all zero on entry); L is ADDED to loss_out
+ * (device double[1]; a sum of per-workgroup partials, as el_bprmf_deterministic documents).  Feat enters through the n DISTINCT
+ * items of the batch only: one product Feat_rows EB [n, Fd + 1] going forward, one product Feat_rows^T [A | a] going backward
+ * (el_gemm_f32), where [A | a] holds per distinct item the signed sums of s_b Tu[u_b] and s_b; no [B, D] array is formed.  Every
+ * row sum runs in sorted batch order without floating-point atomics: the same input gives the same bytes.  n is read back by the
+ * host (ONE stream synchronise per call: the call cannot be captured into a graph) and returned in *n_items_out when that is
+ * not NULL.  F, Fd >= 1, F + Fd <= 511, any D and B >= 1.  ws: el_vbpr_ws_bytes(...).                                          */
+int el_vbpr_grads(el_ctx* ctx, void* stream, const el_vbpr_state* st, const int32_t* u, const int32_t* i, const int32_t* j,
+                  int64_t B, float l_w, float l_b, float l_e, double* loss_out, int64_t* n_items_out, void* ws, size_t ws_bytes);
+
+/* optimizer.apply_gradients (VBPR_model.py:93): el_bprmf_apply(EL_OPT_ADAM_TF_DENSE) on (Gu, Gi, Bi) and the same Keras sparse
+ * apply (every row moves; epsilon outside the root, fp32 1 - beta) on Tu, whose gradients are IndexedSlices; E and Bp receive
+ * dense gradients and take TensorFlow's fused ApplyAdam (m += (g - m)(1 - b1), the step of the Mult-VAE weights) with the same
+ * lr_t and epsilon.  The accumulators come back zero.                                                                        */
+int el_vbpr_apply(el_ctx* ctx, void* stream, const el_vbpr_state* st, float lr, int32_t step, float lr_t);
+
+/* Replaces: the item side of predict_item_batch (VBPR_model.py:104-108) for every item at once:
+ *   Q [I, F + Fd] = [Gi | Feat E],  bq [I] = Bi + Feat Bp,  and, when P is not NULL, P [U, F + Fd] = [Gu | Tu]
+ * so that x(u, i) = bq[i] + P[u] . Q[i] and scoring is el_score_topk / el_score_rank on (P, Q, bq) with F + Fd factors.
+ * ws: el_vbpr_image_ws_bytes(ctx, I, Fd, D).                                                                                */
+size_t el_vbpr_image_ws_bytes(el_ctx* ctx, int64_t I, int32_t Fd, int64_t D);
+int el_vbpr_item_image(el_ctx* ctx, void* stream, const el_vbpr_state* st, float* Q, float* bq, float* P, void* ws, size_t ws_bytes);
+
 /* ---- BPR-MF, NumPy semantics (BPRMF; K5) ------------------------------------- */
 
 typedef struct el_bprsgd_state {
