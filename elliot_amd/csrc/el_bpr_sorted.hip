@@ -41,6 +41,18 @@ __global__ __launch_bounds__(256) void k_bpr_prep(const int32_t* __restrict__ u,
     valI[B + t] = (u32)t | 0x80000000u;
 }
 
+// a lane's floats of a row, non-temporal where the instantiation streams that row once (NT: a compile-time flag of the kernel)
+template <int VW, bool NT>
+__device__ __forceinline__ void ldv_s(const float* p, float* dst) {
+    if (NT) ldv_nt<VW>(p, dst);
+    else ldv<VW>(p, dst);
+}
+template <int VW, bool NT>
+__device__ __forceinline__ void stv_s(float* p, const float* src) {
+    if (NT) stv_nt<VW>(p, src);
+    else stv<VW>(p, src);
+}
+
 #define BPR_USTG 16   // positions per LDS stage, user segments (6 words each)
 #define BPR_ISTG 64   // item segments (4 words each)
 
@@ -141,9 +153,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SER && CPL
                             mn[x] = mrow[DEFER ? q : 0][x], vn[x] = vrow[DEFER ? q : 0][x];
                             el_adam_slots(mn[x], vn[x], g, f.b1, f.b2, omb1, omb2);
                         }
+                        // Cache policy of the deferred kernels, one rule: a row that no later instruction of this step, and with high
+                        // probability none of the next, reads again is loaded and stored non-temporally (ldv_nt / stv_nt); a row that
+                        // is re-used keeps the default policy.  Here: a user's m, v (and the theta gather below) are touched once per
+                        // step and one user in ten comes back in the next; the theta store stays default -- the item segments of
+                        // this step gather that row -- and so do the Gi rows, Bi, the lr ring and the stamps.
                         if (thmoved) stv<VW>(p.st.Gu + cur * F + e, gu[q]);  // the pre-update row: this step's move stays owed
-                        stv<VW>(p.st.mGu + cur * F + e, mn);
-                        stv<VW>(p.st.vGu + cur * F + e, vn);
+                        stv_nt<VW>(p.st.mGu + cur * F + e, mn);
+                        stv_nt<VW>(p.st.vGu + cur * F + e, vn);
                     }
                 }
                 if (sub == 0) f.last[cur] = ~f.t;
@@ -225,12 +242,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SER && CPL
                             for (int x = 0; x < VW; ++x) rm[PRE ? t : 0][q][x] = rv[PRE ? t : 0][q][x] = 0.f;
                         }
                         if (okv[t] && e < F) {
-                            ldv<VW>(pu + e, rgu[t][q]);
+                            ldv_s<VW, DEFER>(pu + e, rgu[t][q]);       // (DEFER: the user's row streams through once, see flush)
                             ldv<VW>(pi + e, rgi[t][q]);
                             ldv<VW>(pj + e, rgj[t][q]);
                             if (hd) {
-                                ldv<VW>(p.st.mGu + keyv[t] * F + e, rm[PRE ? t : 0][q]);
-                                ldv<VW>(p.st.vGu + keyv[t] * F + e, rv[PRE ? t : 0][q]);
+                                ldv_nt<VW>(p.st.mGu + keyv[t] * F + e, rm[PRE ? t : 0][q]);
+                                ldv_nt<VW>(p.st.vGu + keyv[t] * F + e, rv[PRE ? t : 0][q]);
                             }
                         }
                     }
@@ -272,8 +289,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SER && CPL
 #pragma unroll
                                     for (int x = 0; x < VW; ++x) mrow[DEFER ? q : 0][x] = vrow[DEFER ? q : 0][x] = 0.f;
                                     if (e < F) {
-                                        ldv<VW>(p.st.mGu + key * F + e, mrow[DEFER ? q : 0]);
-                                        ldv<VW>(p.st.vGu + key * F + e, vrow[DEFER ? q : 0]);
+                                        ldv_nt<VW>(p.st.mGu + key * F + e, mrow[DEFER ? q : 0]);
+                                        ldv_nt<VW>(p.st.vGu + key * F + e, vrow[DEFER ? q : 0]);
                                     }
                                 }
                             }
@@ -379,7 +396,6 @@ __global__ __launch_bounds__(256) void k_bpr_rowptr(const u32* __restrict__ keys
 template <int CPL, int RPG>
 __global__ __launch_bounds__(256) void k_bpr_user_adam(SegParams p, FusedParams f) {
     constexpr int VW = 4;
-    typedef float f4 __attribute__((ext_vector_type(4)));
     const int F = p.st.F, lpt = p.lpt;
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t grp = gid / lpt;
@@ -402,10 +418,8 @@ __global__ __launch_bounds__(256) void k_bpr_user_adam(SegParams p, FusedParams 
                 if (r < nrows && e < F) {
                     const int64_t o = (rowbase + r) * F + e;
                     ldv<VW>(p.st.Gu + o, th[r][q]);
-                    const f4 a = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p.st.mGu + o));
-                    const f4 b = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p.st.vGu + o));
-#pragma unroll
-                    for (int x = 0; x < VW; ++x) mm[r][q][x] = a[x], vv[r][q][x] = b[x];
+                    ldv_nt<VW>(p.st.mGu + o, mm[r][q]);
+                    ldv_nt<VW>(p.st.vGu + o, vv[r][q]);
                 }
             }
         }
@@ -510,7 +524,7 @@ __global__ __launch_bounds__(256) void k_bpr_user_adam(SegParams p, FusedParams 
             for (int q = 0; q < CPL; ++q) {
                 const int e = (sub + q * lpt) * VW;
                 if (e < F) {
-                    f4 a, m4, v4;
+                    float a[VW], m4[VW], v4[VW];
 #pragma unroll
                     for (int x = 0; x < VW; ++x) {
                         const float g = cnt[r] ? acc[r][q][x] + w * th[r][q][x] : 0.f;
@@ -519,9 +533,9 @@ __global__ __launch_bounds__(256) void k_bpr_user_adam(SegParams p, FusedParams 
                         a[x] = tx, m4[x] = mx, v4[x] = vx;
                     }
                     const int64_t o = (rowbase + r) * F + e;
-                    __builtin_nontemporal_store(a, reinterpret_cast<f4*>(f.Gu_new + o));
-                    __builtin_nontemporal_store(m4, reinterpret_cast<f4*>(p.st.mGu + o));
-                    __builtin_nontemporal_store(v4, reinterpret_cast<f4*>(p.st.vGu + o));
+                    stv_nt<VW>(f.Gu_new + o, a);
+                    stv_nt<VW>(p.st.mGu + o, m4);
+                    stv_nt<VW>(p.st.vGu + o, v4);
                 }
             }
         }
@@ -539,9 +553,10 @@ __global__ __launch_bounds__(256) void k_bpr_user_adam(SegParams p, FusedParams 
 // One waiting row brought forward ns steps by a whole wave: elements e = (lane + 64 q) VW, all 64 lanes on the same gap (the item
 // catch-up kernel: one wave per sorted position, the wave on a segment head owns the row; the flush walks for rows wider than one
 // pass of the wave).  m = v = 0 (a row that never had a gradient) is a fixed point of the gradient-free step: nothing to do.
+// NTMV: m and v loaded and stored non-temporally (k_bpr_catchup_items).
 // TRAIL (the user table, whose theta may trail m and v by one move: k_bpr_user_seg): `owed` = the move of step `last` is taken first,
 // ns may then be 0 -- theta alone is written.  Without TRAIL this is the code it was (the item rows: stamps never negative).
-template <int VW, bool SER, bool TRAIL = false>
+template <int VW, bool SER, bool TRAIL = false, bool NTMV = false>
 __device__ __forceinline__ void bpr_replay_row(float* __restrict__ tth, float* __restrict__ tm, float* __restrict__ tv, int F, int64_t row, int lane,
                                                int last, int ns, const float* __restrict__ hist, int hist_mask, bool owed = false) {
     auto lrs = [&](int s) { return hist[(last + 1 + s) & hist_mask]; };
@@ -556,8 +571,8 @@ __device__ __forceinline__ void bpr_replay_row(float* __restrict__ tth, float* _
         for (int x = 0; x < VW; ++x) th[x] = mm[x] = vv[x] = 0.f;
         if (e < F) {
             ldv<VW>(tth + row * F + e, th);
-            ldv<VW>(tm + row * F + e, mm);
-            ldv<VW>(tv + row * F + e, vv);
+            ldv_s<VW, NTMV>(tm + row * F + e, mm);
+            ldv_s<VW, NTMV>(tv + row * F + e, vv);
         }
         bool nz = false;
 #pragma unroll
@@ -574,8 +589,8 @@ __device__ __forceinline__ void bpr_replay_row(float* __restrict__ tth, float* _
         if (e < F) {
             stv<VW>(tth + row * F + e, th);
             if (!TRAIL || ns > 0) {
-                stv<VW>(tm + row * F + e, mm);
-                stv<VW>(tv + row * F + e, vv);
+                stv_s<VW, NTMV>(tm + row * F + e, mm);
+                stv_s<VW, NTMV>(tv + row * F + e, vv);
             }
         }
     }
@@ -723,7 +738,9 @@ __global__ __launch_bounds__(256) void k_bpr_catchup_items(el_bprmf_state st, co
     const int last = st.Gi_last[row];
     const int ns = (t - 1) - last;
     if (ns <= 0) return;
-    bpr_replay_row<VW, SER>(st.Gi, st.mGi, st.vGi, st.F, row, lane, last, ns, hist, hist_mask);
+    // (m, v of a caught-up item row: non-temporal, the rule at k_bpr_user_seg's flush -- the segment that follows fetches them once more,
+    //  then nothing does until the item's next batch; theta stays default: this step's user segments gather it)
+    bpr_replay_row<VW, SER, false, true>(st.Gi, st.mGi, st.vGi, st.F, row, lane, last, ns, hist, hist_mask);
     if (lane == 0) st.Gi_last[row] = t - 1;
 }
 
@@ -796,9 +813,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
                         tn[x] = rrow[IFUSE ? q : 0][x], mn[x] = mrow[IFUSE ? q : 0][x], vn[x] = vrow[IFUSE ? q : 0][x];
                         el_adam_elem(tn[x], mn[x], vn[x], gg, f.lr_t, f.b1, f.b2, omb1, omb2, f.eps);
                     }
-                    stv<VW>(p.st.Gi + cur * F + e, tn);
-                    stv<VW>(p.st.mGi + cur * F + e, mn);
-                    stv<VW>(p.st.vGi + cur * F + e, vn);
+                    stv<VW>(p.st.Gi + cur * F + e, tn);       // (default: the next step's user segments gather Gi)
+                    stv_nt<VW>(p.st.mGi + cur * F + e, mn);   // the row's m, v: this step's only touch (the rule at k_bpr_user_seg's flush)
+                    stv_nt<VW>(p.st.vGi + cur * F + e, vn);
                 }
             }
             if (sub == 0) {
@@ -895,8 +912,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
                         for (int x = 0; x < VW; ++x) hr[IFUSE ? t : 0][q][x] = hm[IFUSE ? t : 0][q][x] = hv[IFUSE ? t : 0][q][x] = 0.f;
                         if (headt && e < F) {
                             ldv<VW>(p.st.Gi + keyv[t] * F + e, hr[IFUSE ? t : 0][q]);
-                            ldv<VW>(p.st.mGi + keyv[t] * F + e, hm[IFUSE ? t : 0][q]);
-                            ldv<VW>(p.st.vGi + keyv[t] * F + e, hv[IFUSE ? t : 0][q]);
+                            ldv_nt<VW>(p.st.mGi + keyv[t] * F + e, hm[IFUSE ? t : 0][q]);
+                            ldv_nt<VW>(p.st.vGi + keyv[t] * F + e, hv[IFUSE ? t : 0][q]);
                         }
                     }
                 }

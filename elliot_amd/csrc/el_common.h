@@ -256,6 +256,31 @@ __device__ __forceinline__ void stv(float* p, const float* src) {
         p[0] = src[0];
     }
 }
+// The same lane's floats with the non-temporal hint (global_load / global_store ... nt): for a row that is streamed once and not
+// read again soon, so that it does not push re-used rows out of the L2 and the Infinity Cache.  Same arguments, same alignment.
+template <int VW>
+__device__ __forceinline__ void ldv_nt(const float* p, float* dst) {
+    if constexpr (VW == 1) {
+        dst[0] = __builtin_nontemporal_load(p);
+    } else {
+        typedef float fv __attribute__((ext_vector_type(VW)));
+        const fv t = __builtin_nontemporal_load(reinterpret_cast<const fv*>(p));
+#pragma unroll
+        for (int x = 0; x < VW; ++x) dst[x] = t[x];
+    }
+}
+template <int VW>
+__device__ __forceinline__ void stv_nt(float* p, const float* src) {
+    if constexpr (VW == 1) {
+        __builtin_nontemporal_store(src[0], p);
+    } else {
+        typedef float fv __attribute__((ext_vector_type(VW)));
+        fv t;
+#pragma unroll
+        for (int x = 0; x < VW; ++x) t[x] = src[x];
+        __builtin_nontemporal_store(t, reinterpret_cast<fv*>(p));
+    }
+}
 
 // ---- order-preserving float <-> uint maps (top-k keys) ---------------------------
 // key = ord(score) << 32 | ~item  : larger key == better (score desc, then index asc).
