@@ -46,6 +46,17 @@ def workspace(holder, attr, need, device):
     return ws
 
 
+def _own(x, device, dtype=torch.float32):
+    """A state's private copy of a parameter: a numpy array, host tensor or device tensor as a contiguous `dtype` tensor on `device`
+    that never aliases the caller's.  None stays None."""
+    if x is None:
+        return None
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    t = x.to(device=device, dtype=dtype).contiguous()
+    return t.clone() if t.untyped_storage().data_ptr() == x.untyped_storage().data_ptr() else t
+
+
 class Context:
     """One el_ctx per device (include/elliot_hip.h: el_ctx_create)."""
 
@@ -712,8 +723,7 @@ class AlsDeviceState:
             raise ValueError("gram must be 'fresh' (iALS) or 'stale' (WRMF)")
         self.ctx = ctx
         dev = ctx.device
-        own = lambda x: torch.from_numpy(np.array(x, dtype=np.float64, order="C")).to(dev)
-        self.X, self.Y = own(X), own(Y)
+        self.X, self.Y = _own(X, dev, torch.float64), _own(Y, dev, torch.float64)
         self.U, self.F = int(self.X.shape[0]), int(self.X.shape[1])
         self.I = int(self.Y.shape[0])
         if self.F > _lib.EL_ALS_MAX_F:
@@ -750,11 +760,9 @@ class AlsDeviceState:
 
     def recommend(self, mask, k, start, stop):
         """X Y^T (fp64) for users [start, stop) and the masked top-k (el_score_topk_f64 with b = 0): (idx, val) on the device."""
-        kind, csr = mask if mask is not None else (None, None)
         if self._zero_bias is None:
             self._zero_bias = torch.zeros(self.I, dtype=torch.float64, device=self.ctx.device)
-        return score_topk_f64(self.ctx, self.X, self.Y, self._zero_bias, start, stop, k, excl=csr if kind == "excl" else None,
-                              cand=csr if kind == "cand" else None)
+        return score_topk_f64(self.ctx, self.X, self.Y, self._zero_bias, start, stop, k, **mask_kwargs(mask))
 
     def rank(self, mask, targets, start, stop):
         """Positions of the entries of rows [start, stop) of `targets` in the order recommend() selects by (el_score_rank_f64)."""
@@ -792,9 +800,8 @@ class _DenseScoreState:
         """Top-k of users [start, stop) under the tagged mask ("excl" | "cand", DeviceCSR): (idx int32, val SCORE_DTYPE) [n, k]
         on the device; lists short of k are padded with (-1, -inf)."""
         ctx, dt = self.ctx, self.SCORE_DTYPE
-        kind, csr = mask if mask is not None else (None, None)
-        ep, ei = _csr_ptrs(csr if kind == "excl" else None)
-        cp, ci = _csr_ptrs(csr if kind == "cand" else None)
+        m = mask_kwargs(mask)
+        (ep, ei), (cp, ci) = _csr_ptrs(m["excl"]), _csr_ptrs(m["cand"])
         sfx = "" if dt == torch.float32 else "_f64"
         topk, pad = getattr(ctx.lib, "el_dense_topk" + sfx), getattr(ctx.lib, "el_topk_pad" + sfx)
         start, stop = int(start), int(stop)
@@ -1559,11 +1566,9 @@ class PureSvdDeviceState:
         padded with (-1, -inf) (el_topk_pad): (idx, val) [n, k] on the device."""
         if self.user_vec is None:
             raise _lib.ElliotHipError("PureSVD: recommend() before build() or set_weights()")
-        kind, csr = mask if mask is not None else (None, None)
         if self._zero_bias is None:
             self._zero_bias = torch.zeros(self.I, dtype=torch.float32, device=self.ctx.device)
-        idx, val = score_topk(self.ctx, self.user_vec, self.item_vec, self._zero_bias, start, stop, k,
-                              excl=csr if kind == "excl" else None, cand=csr if kind == "cand" else None)
+        idx, val = score_topk(self.ctx, self.user_vec, self.item_vec, self._zero_bias, start, stop, k, **mask_kwargs(mask))
         check(self.ctx.lib.el_topk_pad(self.ctx.handle, self.ctx.stream(), _ptr(idx, torch.int32), _ptr(val, torch.float32),
                                        int(idx.numel())), "el_topk_pad")
         return idx, val
@@ -2071,6 +2076,7 @@ def adam_lr_t(lr, step, beta1=0.9, beta2=0.999):
 # HBM placement of the four streams of the dense Adam pass
 # ------------------------------------------------------------------------------------------
 _LAYOUT_CANDIDATES_MIB = (0.0, 0.5, 1.0, 1.5, 2.0, 2.5, 3.0, 3.5, 4.0, 4.5, 5.0, 5.5)
+BIG_TABLE_BYTES = 64 << 20          # an embedding table from here on gets the tuned Adam block (and compact user gradients in BPR)
 
 
 def _strided_tables(rows, F, count, gap_bytes, device):
@@ -2092,7 +2098,7 @@ def tune_table_layout(ctx, rows, F, compact=False):
     cache = ctx.__dict__.setdefault("_layout_cache", {})
     if key in cache:
         return cache[key]
-    if os.environ.get("EL_TUNE_LAYOUT", "1") == "0" or rows * F * 4 < (64 << 20):
+    if os.environ.get("EL_TUNE_LAYOUT", "1") == "0" or rows * F * 4 < BIG_TABLE_BYTES:
         cache[key] = 0
         return 0
     dev = ctx.device
@@ -2153,6 +2159,16 @@ def tune_table_layout(ctx, rows, F, compact=False):
     return best
 
 
+def _tuned_adam_block(ctx, theta, count, compact=False):
+    """The arrays the dense Adam pass streams for one big table, from ONE allocation at the tuned distance (tune_table_layout):
+    `count` zeroed float32 tables of theta's shape, theta copied into the first.  Returns (tables, the block to keep alive, gap)."""
+    rows, F = int(theta.shape[0]), int(theta.shape[1])
+    gap = tune_table_layout(ctx, rows, F, compact=compact)
+    tabs, block = _strided_tables(rows, F, count, gap, ctx.device)
+    tabs[0].copy_(theta if isinstance(theta, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(theta)))
+    return tabs, block, gap
+
+
 class BprmfDeviceState:
     """Gu/Gi/Bi + gradient accumulators + Adam slots in HBM (BPRMF_batch_model.py:39-44)."""
 
@@ -2183,7 +2199,7 @@ class BprmfDeviceState:
         self.replay = replay
         self.opt = OPTIMIZERS[optimizer] if isinstance(optimizer, str) else int(optimizer)
         dev = ctx.device
-        big = int(Gu.shape[0]) * int(Gu.shape[1]) * 4 >= (64 << 20)
+        big = int(Gu.shape[0]) * int(Gu.shape[1]) * 4 >= BIG_TABLE_BYTES
         self.compact = bool(self.opt == EL_OPT_ADAM_TF_DENSE and int(Gu.shape[1]) % 4 == 0 and optimizer != "sgd_dense" and
                             (big if compact_user_grads is None else compact_user_grads))
 
@@ -2201,33 +2217,24 @@ class BprmfDeviceState:
         self.item_deferred = bool(self.item_fused and item_deferred is True)
         self._pending_items = False
 
-        def own(x, dt):
-            if isinstance(x, np.ndarray):
-                x = torch.from_numpy(np.ascontiguousarray(x))
-            return x.to(device=dev, dtype=dt).contiguous().clone()
-
-        self._Gi, self._Bi = own(Gi, torch.float32), own(Bi, torch.float32)
+        self._Gi, self._Bi = _own(Gi, dev), _own(Bi, dev)
         self.U, self.F = int(Gu.shape[0]), int(Gu.shape[1])
         self.I = self._Gi.shape[0]
         z = torch.zeros_like
         adam = self.opt in (EL_OPT_ADAM_TF_DENSE, EL_OPT_ADAM_LAZY)
         self.uslot = self.gGu_rows = None
-        if self.opt == EL_OPT_ADAM_TF_DENSE and self.U * self.F * 4 >= (64 << 20):
-            # the dense Adam pass streams these at once: one allocation, tuned distance (tune_table_layout)
-            gap = tune_table_layout(ctx, self.U, self.F, compact=self.compact)
+        if self.opt == EL_OPT_ADAM_TF_DENSE and self.U * self.F * 4 >= BIG_TABLE_BYTES:
+            self.gGu = None
             if self.compact and self.fused and not self.deferred:
                 # (deferred=None: the pair is allocated; if the first batch turns the deferred decay on, Gu_next just stays unused)
-                (self.Gu, self.mGu, self.vGu, self.Gu_next), self._user_block = _strided_tables(self.U, self.F, 4, gap, dev)
-                self.gGu = None
-            elif self.compact:
-                (self.Gu, self.mGu, self.vGu), self._user_block = _strided_tables(self.U, self.F, 3, gap, dev)
-                self.gGu = None
+                names = ("Gu", "mGu", "vGu", "Gu_next")
             else:
-                (self.Gu, self.gGu, self.mGu, self.vGu), self._user_block = _strided_tables(self.U, self.F, 4, gap, dev)
-            self.Gu.copy_(Gu if isinstance(Gu, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(Gu)))
-            self.layout_gap = gap
+                names = ("Gu", "mGu", "vGu") if self.compact else ("Gu", "gGu", "mGu", "vGu")
+            tabs, self._user_block, self.layout_gap = _tuned_adam_block(ctx, Gu, len(names), compact=self.compact)
+            for n, t in zip(names, tabs):
+                setattr(self, n, t)
         else:
-            self.Gu = own(Gu, torch.float32)
+            self.Gu = _own(Gu, dev)
             if self.fused and not self.deferred:
                 self.Gu_next = torch.empty_like(self.Gu)
             self.gGu = None if self.compact else z(self.Gu)
@@ -2265,7 +2272,7 @@ class BprmfDeviceState:
             tGu=self.tGu.data_ptr() if rows else None, tGi=self.tGi.data_ptr() if rows else None,
             tBi=self.tBi.data_ptr() if rows else None, U=self.U, I=self.I, F=self.F,
             Gu_next=self.Gu_next.data_ptr() if self.Gu_next is not None else None, replay_series=int(replay == "series"))
-        self.Gu_last = self.Gu_old = self.lr_hist = None
+        self.Gu_last = self.lr_hist = None
         self.Gi_last = None
         if self.deferred:
             self._enable_deferred()
@@ -2370,18 +2377,11 @@ class BprmfDeviceState:
             return
         self.sync()
         self.deferred = False
-        self._c.Gu_last = self._c.Gu_old = None
-        self._c.Gu_old_cap = 0
-        self.Gu_last = self.Gu_old = None                       # (the lr ring stays: the fused item side reads it too)
+        self._c.Gu_last = self.Gu_last = None                   # (the lr ring stays: the fused item side reads it too)
         if self.fused:                                          # the fused user-side step needs its second table from here on
             if self.Gu_next is None:
                 self.Gu_next = torch.empty_like(self._Gu)
             self._c.Gu_next = self.Gu_next.data_ptr()
-
-    def _ensure_old(self, B):
-        """(The deferred decay once kept a copy of the batch's pre-update user rows, Gu_old: the rows now trail their last Adam move
-        in Gu itself and the item side reads them there.  What is left is the choice of the form for this batch size.)"""
-        self._resolve_deferred(B)
 
     def _swap_user_tables(self, steps=1):
         """After `steps` fused train steps the current user table is the other one of the pair (include/elliot_hip.h, Gu_next)."""
@@ -2475,7 +2475,6 @@ class BprmfDeviceState:
                 raise ValueError("compact user-gradient rows need the sorted gradient path")
             if not self.fused:
                 self.ensure_rows(B)
-            self._ensure_old(B)
         if algo == _lib.EL_BPR_SORTED or (algo == _lib.EL_BPR_AUTO and B >= 2048) or self.compact:
             t = self.sort_workspace(B, "_ws")
             ws, ws_bytes = _ptr(t), t.numel()
@@ -2532,7 +2531,7 @@ class BprmfDeviceState:
             raise ValueError("train_step_presorted: the dense optimisers only (adam_tf_dense, sgd_dense)")
         if not self.fused:
             self.ensure_rows(B)
-        self._ensure_old(B)
+        self._resolve_deferred(B)
         self._advance()
         check(self.ctx.lib.el_bprmf_train_step_presorted(self.ctx.handle, self.ctx.stream(), C.byref(self._c), _ptr(u, torch.int32, "u"),
                                                          _ptr(i, torch.int32, "i"), _ptr(j, torch.int32, "j"), int(B), float(lr), float(l_w),
@@ -2554,7 +2553,7 @@ class BprmfDeviceState:
         # (kept alive on self: the library may copy the table with an asynchronous memcpy on the stream)
         if not self.fused:
             self.ensure_rows(B)
-        self._ensure_old(B)
+        self._resolve_deferred(B)
         need = int(self.ctx.lib.el_bprmf_ws_bytes(int(B), int(self.U), int(self.I), int(self.F))) if (B >= 2048 or self.compact) else 0
         ws = workspace(self, "_ws", need, self.ctx.device) if need else None
         lneed = int(self.ctx.lib.el_bprmf_train_loop_ws_bytes(int(events), int(B)))
@@ -2584,6 +2583,7 @@ class AmfDeviceState:
 
     def __init__(self, ctx, Gu, Gi, Bi, delta_Gu=None, delta_Gi=None):
         self.ctx = ctx
+        # (without compact user gradients the wrapped state has no per-row features: nothing stands aside for the library's calls)
         self.base = BprmfDeviceState(ctx, Gu, Gi, Bi, optimizer="adam", compact_user_grads=False)
         b, dev = self.base, ctx.device
         self.U, self.I, self.F = b.U, b.I, b.F
@@ -2608,13 +2608,7 @@ class AmfDeviceState:
     def _workspace(self, B):
         return workspace(self, "_ws", int(self.ctx.lib.el_amf_ws_bytes(int(B), self.U, self.I, self.F)), self.ctx.device)
 
-    def _stand_aside(self, on):
-        """The library reads every row as current: the per-row features of the wrapped state stand aside as for its grads() / apply()."""
-        if self.base.deferred or self.base.item_fused:
-            self.base._two_pass(on)
-
     def _call(self, fn, name, u, i, j, *rest):
-        self._stand_aside(True)
         ws = self._workspace(u.numel())
         head = (self.ctx.handle, self.ctx.stream(), C.byref(self.base._c), C.byref(self._d), _ptr(u, torch.int32, "u"),
                 _ptr(i, torch.int32, "i"), _ptr(j, torch.int32, "j"), int(u.numel()))
@@ -2639,7 +2633,6 @@ class AmfDeviceState:
         """build_perturbation (nb_iter = 0) / build_msap_perturbation (AMF_model.py:133-197): delta only, no optimiser."""
         self._call(self.ctx.lib.el_amf_perturb, "el_amf_perturb", u, i, j, float(l_w), float(l_b), float(eps), float(eps_iter),
                    int(nb_iter))
-        self._stand_aside(False)
         self.delta_is_zero = False
 
     def clear_delta(self):
@@ -2660,11 +2653,9 @@ class AmfDeviceState:
         """(Gu + dGu, Gi + dGi) in fp32 scratch tables -- what predict(adversarial=True) multiplies (AMF_model.py:110-111)."""
         if self._Pu is None:
             self._Pu, self._Pi = torch.empty_like(self.dGu), torch.empty_like(self.dGi)
-        self._stand_aside(True)
         check(self.ctx.lib.el_amf_perturbed_tables(self.ctx.handle, self.ctx.stream(), C.byref(self.base._c), C.byref(self._d),
                                                    _ptr(self._Pu, torch.float32), _ptr(self._Pi, torch.float32)),
               "el_amf_perturbed_tables")
-        self._stand_aside(False)
         return self._Pu, self._Pi
 
 
@@ -2680,18 +2671,13 @@ class VbprDeviceState:
         b, dev = self.base, ctx.device
         self.U, self.I, self.F = b.U, b.I, b.F
 
-        def own(x):
-            if isinstance(x, np.ndarray):
-                x = torch.from_numpy(np.ascontiguousarray(x))
-            return x.to(device=dev, dtype=torch.float32).contiguous().clone()
-
-        self.Tu = own(Tu)
+        self.Tu = _own(Tu, dev)
         self.Fd = int(self.Tu.shape[1])
         if not isinstance(feat, torch.Tensor) or feat.device != dev or feat.dtype != torch.float32 or not feat.is_contiguous():
             raise ValueError("VbprDeviceState: feat must be a contiguous float32 tensor on the context's device")
         self.feat = feat
         self.D = int(feat.shape[1])
-        E, Bp = own(E), own(Bp).reshape(-1, 1)
+        E, Bp = _own(E, dev), _own(Bp, dev).reshape(-1, 1)
         if tuple(feat.shape) != (self.I, self.D) or tuple(E.shape) != (self.D, self.Fd) or Bp.shape[0] != self.D \
                 or self.Tu.shape[0] != self.U:
             raise ValueError("VbprDeviceState: shapes of Tu / E / Bp / feat do not fit")
@@ -2917,8 +2903,7 @@ class NgcfDeviceState:
         self.bpr = BprmfDeviceState(ctx, Gu, Gi, np.zeros(int(Gi.shape[0]), np.float32), optimizer="adam_tf_dense", deferred=False,
                                     item_deferred=False)
         self.U, self.I, self.W = self.bpr.U, self.bpr.I, self.bpr.F
-        own = lambda x: (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))).to(device=dev, dtype=torch.float32).contiguous().clone()
-        self.layers = [{k: own(v) for k, v in l.items()} for l in layers]
+        self.layers = [{k: _own(v, dev) for k, v in l.items()} for l in layers]
         self.slots = [{k: (torch.zeros_like(v), torch.zeros_like(v)) for k, v in l.items()} for l in self.layers]
         sizes = [self.embed_k] + [int(l["W1"].shape[1]) for l in self.layers]
         if sum(sizes) != self.W or any(int(l["W1"].shape[0]) != sizes[n] for n, l in enumerate(self.layers)):
@@ -2999,12 +2984,7 @@ class BprSgdDeviceState:
         self.ctx = ctx
         dev = ctx.device
 
-        def own(x):
-            if isinstance(x, np.ndarray):
-                x = torch.from_numpy(np.ascontiguousarray(x))
-            return x.to(device=dev, dtype=torch.float64).contiguous().clone()
-
-        self.P, self.Q, self.b = own(P), own(Q), own(b)
+        self.P, self.Q, self.b = (_own(x, dev, torch.float64) for x in (P, Q, b))
         self.U, self.F = self.P.shape
         self.I = self.Q.shape[0]
         self._c = BprsgdState(P=self.P.data_ptr(), Q=self.Q.data_ptr(), b=self.b.data_ptr(), U=self.U, I=self.I,
@@ -3040,12 +3020,11 @@ class Mf2020DeviceState:
     def __init__(self, ctx, P, Q, bu=None, bi=None, gb=0.0, lr=0.05, reg=0.0):
         self.ctx = ctx
         dev = ctx.device
-        own = lambda x: (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))).to(device=dev, dtype=torch.float64).contiguous().clone()
-        self.P, self.Q = own(P), own(Q)
+        self.P, self.Q = _own(P, dev, torch.float64), _own(Q, dev, torch.float64)
         self.U, self.F = int(self.P.shape[0]), int(self.P.shape[1])
         self.I = int(self.Q.shape[0])
-        self.bu = own(bu) if bu is not None else torch.zeros(self.U, dtype=torch.float64, device=dev)
-        self.bi = own(bi) if bi is not None else torch.zeros(self.I, dtype=torch.float64, device=dev)
+        self.bu = _own(bu, dev, torch.float64) if bu is not None else torch.zeros(self.U, dtype=torch.float64, device=dev)
+        self.bi = _own(bi, dev, torch.float64) if bi is not None else torch.zeros(self.I, dtype=torch.float64, device=dev)
         self.gb = torch.full((1,), float(gb), dtype=torch.float64, device=dev)
         self.loss = torch.zeros(1, dtype=torch.float64, device=dev)
         self.lr, self.reg = float(lr), float(reg)
@@ -3112,20 +3091,18 @@ class VaeDeviceState:
     def __init__(self, ctx, weights, max_batch):
         self.ctx = ctx
         dev = ctx.device
-        f = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev) if isinstance(x, np.ndarray) \
-            else x.to(device=dev, dtype=torch.float32).contiguous().clone()
-        W1, W4 = f(weights["W1"]), f(weights["W4"])
+        f = {n: _own(x, dev) for n, x in weights.items()}
+        W1, W4 = f["W1"], f["W4"]
         self.I, self.H = W1.shape
         self.L = int(weights["Wm"].shape[1])
         self.Bmax = int(max_batch)
         self.dae = "Wv" not in weights          # MultiDAE: mean head only, tanh on it, no sampling / KL (multi_dae_model.py)
         if self.dae:
-            wmv, bmv = f(weights["Wm"]), f(weights["bm"])
+            wmv, bmv = f["Wm"], f["bm"]
         else:
-            wmv = torch.cat([f(weights["Wm"]), f(weights["Wv"])], dim=1).contiguous()
-            bmv = torch.cat([f(weights["bm"]), f(weights["bv"])]).contiguous()
-        t = {"W1": W1, "b1": f(weights["b1"]), "Wmv": wmv, "bmv": bmv,
-             "W3": f(weights["W3"]), "b3": f(weights["b3"]), "W4": W4, "b4": f(weights["b4"])}
+            wmv = torch.cat([f["Wm"], f["Wv"]], dim=1).contiguous()
+            bmv = torch.cat([f["bm"], f["bv"]]).contiguous()
+        t = {"W1": W1, "b1": f["b1"], "Wmv": wmv, "bmv": bmv, "W3": f["W3"], "b3": f["b3"], "W4": W4, "b4": f["b4"]}
         self.w = [t[n] for n in self.ORDER]
         self.g = [torch.zeros_like(x) for x in self.w]
         self.m = [torch.zeros_like(x) for x in self.w]
@@ -3214,15 +3191,13 @@ class AutoRecDeviceState:
     def __init__(self, ctx, weights, out_act, max_batch, nnz_max):
         self.ctx = ctx
         dev = ctx.device
-        f = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev) if isinstance(x, np.ndarray) \
-            else x.to(device=dev, dtype=torch.float32).contiguous().clone()
-        W1, W2 = f(weights["W1"]), f(weights["W2"])
+        W1, W2 = _own(weights["W1"], dev), _own(weights["W2"], dev)
         self.N, self.H = (int(x) for x in W1.shape)
         if tuple(W2.shape) != (self.H, self.N):
             raise ValueError(f"W2 must be [H, N] = {(self.H, self.N)}, got {tuple(W2.shape)}")
         self.out_act = ACTS[out_act]
         self.Bmax, self.nnz_max = int(max_batch), int(nnz_max)
-        self.w = [W1, f(weights["b1"]), W2.t().contiguous(), f(weights["b2"])]
+        self.w = [W1, _own(weights["b1"], dev), W2.t().contiguous(), _own(weights["b2"], dev)]
         self.g = [torch.zeros_like(x) for x in self.w]
         self.m = [torch.zeros_like(x) for x in self.w]
         self.v = [torch.zeros_like(x) for x in self.w]
@@ -3339,13 +3314,11 @@ class NmfDeviceState:
         self.replay = replay                                         # how waiting rows are brought forward (BprmfDeviceState: the same two modes)
         self.dropout, self.dropout_seed = float(dropout), int(dropout_seed)
         self.deferred = True if deferred is None else bool(deferred)
-        f = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev) if isinstance(x, np.ndarray) \
-            else x.to(device=dev, dtype=torch.float32).contiguous().clone()
         self.use_mf = "Umf" in weights
         self.use_mlp = "Umlp" in weights
         self.head_bias = "hb" in weights
         names = ["Umf", "Imf", "Umlp", "Imlp"]
-        self.tab = [f(weights[n]) if n in weights else None for n in names]
+        self.tab = [_own(weights.get(n), dev) for n in names]
         ref = self.tab[0] if self.use_mf else self.tab[2]
         self.U = ref.shape[0]
         self.I = (self.tab[1] if self.use_mf else self.tab[3]).shape[0]
@@ -3357,25 +3330,18 @@ class NmfDeviceState:
             tb = self.tab[t]
             if tb is None:
                 continue
-            if tb.numel() * 4 >= (64 << 20):
-                # Keras' dense Adam over an embedding table streams theta, g, m, v at once: one allocation, the distance between
-                # the four arrays tuned by timing the pass (tune_table_layout -- the BPR tables' 0.82 -> 0.61 ms effect; with one
-                # allocation per array the channel / bank phase of the seven streams is the allocator's luck)
-                gap = tune_table_layout(ctx, int(tb.shape[0]), int(tb.shape[1]))
-                (th, self.gtab[t], self.mtab[t], self.vtab[t]), blk = _strided_tables(int(tb.shape[0]), int(tb.shape[1]), 4, gap, dev)
-                th.copy_(tb)
-                self.tab[t] = th
+            if tb.numel() * 4 >= BIG_TABLE_BYTES:
+                (self.tab[t], self.gtab[t], self.mtab[t], self.vtab[t]), blk, _gap = _tuned_adam_block(ctx, tb, 4)
                 self._tab_blocks.append(blk)
                 del tb
             else:
                 self.gtab[t], self.mtab[t], self.vtab[t] = z(tb), z(tb), z(tb)
-        self.W = [f(w) for w in weights.get("W", [])]
-        self.b = [f(b) for b in weights.get("b", [])]
+        self.W = [_own(w, dev) for w in weights.get("W", [])]
+        self.b = [_own(b, dev) for b in weights.get("b", [])]
         self.units = [w.shape[1] for w in self.W]
         self.gW, self.mW, self.vW = [z(w) for w in self.W], [z(w) for w in self.W], [z(w) for w in self.W]
         self.gb, self.mb, self.vb = [z(b) for b in self.b], [z(b) for b in self.b], [z(b) for b in self.b]
-        self.hw = f(weights["hw"])
-        self.hb = f(weights["hb"]) if self.head_bias else None
+        self.hw, self.hb = _own(weights["hw"], dev), _own(weights.get("hb"), dev)
         self.ghw, self.mhw, self.vhw = z(self.hw), z(self.hw), z(self.hw)
         self.ghb, self.mhb, self.vhb = z(self.hb), z(self.hb), z(self.hb)
         B = int(max_batch)
@@ -3654,29 +3620,19 @@ class NmfDeviceState:
         max_list = _NMF_MAX_LIST if self.use_mlp else _PW_MAX_LIST
 
         def score(kk):
+            nonlocal items_unchanged
+            same, items_unchanged = items_unchanged, True          # a longer list of this call meets the image of its first pass
             if self.use_mlp:
-                return self.score_topk_logits(u_start, u_stop, kk, excl=excl, cand=cand, items_unchanged=items_unchanged)
-            img, brow = self._dot_tables(items_unchanged)
-            return score_topk(self.ctx, self.tab[0], img, brow, u_start, u_stop, kk, excl=excl, cand=cand, items_unchanged=items_unchanged)
+                return self.score_topk_logits(u_start, u_stop, kk, excl=excl, cand=cand, items_unchanged=same)
+            img, brow = self._dot_tables(same)
+            return score_topk(self.ctx, self.tab[0], img, brow, u_start, u_stop, kk, excl=excl, cand=cand, items_unchanged=same)
 
-        kk = min(self.I, k + getattr(self, "_margin", _PW_MARGIN))
-        while True:
-            idx, val = score(kk)
-            items_unchanged = True
+        def link(val, kk):
             check(self.ctx.lib.el_pwmf_link_values(self.ctx.handle, self.ctx.stream(), _ptr(val, torch.float32), int(val.shape[0]),
                                                    int(val.stride(0)), int(kk), _lib.EL_PW_MSE_SIGMOID, None, int(u_start)),
                   "el_pwmf_link_values")
-            if kk >= self.I:
-                break
-            open_rows = (val[:, k - 1] == val[:, kk - 1]) & (val[:, k - 1] > float("-inf"))
-            if not bool(open_rows.any()):
-                break
-            if kk >= max_list:
-                return self._pairs_topk(u_start, u_stop, k, excl, cand)
-            kk = min(self.I, max_list, k + 16 if kk < k + 16 else kk * 4)
-        self._margin = kk - k
-        idx, val = topk_rerank(self.ctx, idx, val)
-        return idx[:, :k].contiguous(), val[:, :k].contiguous()
+
+        return _linked_topk(self, k, score, link, max_list, lambda: self._pairs_topk(u_start, u_stop, k, excl, cand))
 
 
 # ------------------------------------------------------------------------------------------
@@ -3703,6 +3659,29 @@ def topk_rerank(ctx, idx, val):
     return idx, val
 
 
+def _linked_topk(state, k, score, link, max_list, dense):
+    """Top-k by a linked score from kernels that rank by the raw one.  score(kk) -> (idx, val) lists of length kk by raw score;
+    link(val, kk) maps the values in place; the list is taken `state._margin` entries longer than k, linked, and while some row's
+    k-th value still equals its last one taken longer (k + 16, then x4) up to `max_list`, past which dense() answers; then re-ranked
+    by (value desc, index asc) and cut.  The length that resolved this block stays in state._margin: small-score models (untrained:
+    everything near link(0)) collapse often, and the next blocks of the evaluation start there (the training calls reset it)."""
+    kk = min(state.I, k + getattr(state, "_margin", _PW_MARGIN))
+    while True:
+        idx, val = score(kk)
+        link(val, kk)
+        if kk >= state.I:
+            break
+        open_rows = (val[:, k - 1] == val[:, kk - 1]) & (val[:, k - 1] > float("-inf"))
+        if not bool(open_rows.any()):
+            break
+        if kk >= max_list:
+            return dense()
+        kk = min(state.I, max_list, k + 16 if kk < k + 16 else kk * 4)
+    state._margin = kk - k
+    idx, val = topk_rerank(state.ctx, idx, val)
+    return idx[:, :k].contiguous(), val[:, :k].contiguous()
+
+
 class PwmfDeviceState:
     """Variables + optimiser slots of one point-wise factor model in HBM (include/elliot_hip.h, el_pwmf_state).
 
@@ -3711,10 +3690,9 @@ class PwmfDeviceState:
 
     def __init__(self, ctx, Gu, Gi, Bu=None, Bi=None, kind="mse", optimizer="adam", alpha=0.0, l_w=0.0):
         self.ctx, dev = ctx, ctx.device
-        f = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
         if (Bu is None) != (Bi is None):
             raise ValueError("Bu and Bi go together")
-        self.Gu, self.Gi, self.Bu, self.Bi = f(Gu), f(Gi), f(Bu), f(Bi)
+        self.Gu, self.Gi, self.Bu, self.Bi = (_own(x, dev) for x in (Gu, Gi, Bu, Bi))
         if self.Bu is not None:
             self.Bu, self.Bi = self.Bu.reshape(-1).contiguous(), self.Bi.reshape(-1).contiguous()
         self.U, self.F = self.Gu.shape
@@ -3727,12 +3705,8 @@ class PwmfDeviceState:
         names = ("Gu", "Gi", "Bu", "Bi")
         for n in names:
             t = getattr(self, n)
-            if n == "Gu" and adam and self.U * self.F * 4 >= (64 << 20):
-                # the dense Adam pass streams theta, g, m, v of the user table at once: one allocation, tuned distance
-                gap = tune_table_layout(ctx, self.U, self.F)
-                (th, self.gGu, self.mGu, self.vGu), self._user_block = _strided_tables(self.U, self.F, 4, gap, dev)
-                th.copy_(self.Gu)
-                self.Gu = th
+            if n == "Gu" and adam and self.U * self.F * 4 >= BIG_TABLE_BYTES:
+                (self.Gu, self.gGu, self.mGu, self.vGu), self._user_block, _gap = _tuned_adam_block(ctx, self.Gu, 4)
                 continue
             setattr(self, "g" + n, z(t))
             setattr(self, "m" + n, slot(t))
@@ -3848,22 +3822,9 @@ class PwmfDeviceState:
         plain = self.kind != "mse_sigmoid" and self.Bu is None
         if plain:
             return score_topk(self.ctx, self.Gu, self.Gi, None, u_start, u_stop, k, excl=excl, cand=cand)
-        kk = min(self.I, k + getattr(self, "_margin", _PW_MARGIN))
-        while True:
-            idx, val = score_topk(self.ctx, self.Gu, self.Gi, self.Bi, u_start, u_stop, kk, excl=excl, cand=cand)
-            self._link(val, kk, u_start)
-            if kk >= self.I:
-                break
-            open_rows = (val[:, k - 1] == val[:, kk - 1]) & (val[:, k - 1] > float("-inf"))
-            if not bool(open_rows.any()):
-                break
-            if kk >= _PW_MAX_LIST:
-                return self._recommend_dense(u_start, u_stop, k, excl, cand)
-            kk = min(self.I, _PW_MAX_LIST, k + 16 if kk < k + 16 else kk * 4)
-        self._margin = kk - k          # small-score models (untrained: everything near link(0)) collapse often: the next blocks
-        #                                of this evaluation start with the list length that resolved this one (reset by train_step)
-        idx, val = topk_rerank(self.ctx, idx, val)
-        return idx[:, :k].contiguous(), val[:, :k].contiguous()
+        return _linked_topk(self, k, lambda kk: score_topk(self.ctx, self.Gu, self.Gi, self.Bi, u_start, u_stop, kk, excl=excl, cand=cand),
+                            lambda val, kk: self._link(val, kk, u_start), _PW_MAX_LIST,
+                            lambda: self._recommend_dense(u_start, u_stop, k, excl, cand))
 
     def _recommend_dense(self, u_start, u_stop, k, excl, cand):
         out_i, out_v = [], []

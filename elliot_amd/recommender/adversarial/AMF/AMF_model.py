@@ -9,11 +9,11 @@ Gi + Delta_Gi, call(adversarial=True) from the plain tables (:58-63).  It is por
 regulariser read the perturbed rows, the l_adv term reads the plain ones.  While the perturbation is all zero (before the first
 adversarial step, or with adversarial_epochs = 0) a plain step IS BPRMF_batch's, and takes its kernels.
 """
-import numpy as np
 import torch
 
 from .... import ops
-from ...latent_factor_models.BPRMF_batch.BPRMF_batch_model import BPRMF_batch_model, DeferredLoss
+from ...device_model import DeferredLoss
+from ...latent_factor_models.BPRMF_batch.BPRMF_batch_model import BPRMF_batch_model, initial_weights
 
 
 class AMF_model(BPRMF_batch_model):
@@ -23,18 +23,10 @@ class AMF_model(BPRMF_batch_model):
         self._factors, self._learning_rate, self._l_w, self._l_b = factors, learning_rate, l_w, l_b
         self._eps, self._l_adv = eps, l_adv
         self._num_users, self._num_items = num_users, num_items
-        if init_weights is not None:
-            Gu, Gi, Bi = init_weights
-        else:
-            # tf.initializers.GlorotUniform (:40-43) as BPRMF_batch_model draws it on the host; Bi = 0
-            rs = np.random.RandomState(random_seed)
-            lu, li = np.sqrt(6.0 / (num_users + factors)), np.sqrt(6.0 / (num_items + factors))
-            Gu = rs.uniform(-lu, lu, size=(num_users, factors)).astype(np.float32)
-            Gi = rs.uniform(-li, li, size=(num_items, factors)).astype(np.float32)
-            Bi = np.zeros(num_items, np.float32)
+        # tf.initializers.GlorotUniform (:40-43) as BPRMF_batch_model draws it on the host; Bi = 0
+        Gu, Gi, Bi = init_weights if init_weights is not None else initial_weights(random_seed, num_users, num_items, factors)
         self.amf = ops.AmfDeviceState(self.ctx, Gu, Gi, Bi)
         self.state = self.amf.base                               # what BPRMF_batch_model's scoring and checkpoints read
-        self._weights_version, self._scored_version = 0, -1
 
     # -- training ---------------------------------------------------------------------------------------
     def train_step(self, batch, user_adv_train=False):
@@ -42,7 +34,7 @@ class AMF_model(BPRMF_batch_model):
         if not user_adv_train and self.amf.delta_is_zero:
             return super().train_step(batch)                     # Delta = 0: the BPRMF_batch step, bit for bit
         u, i, j = (self._as_index(x) for x in batch)
-        self._weights_version += 1
+        self._touch()
         self.amf.train_step(u, i, j, self._learning_rate, self._l_w, self._l_b, self._l_adv, self._eps, bool(user_adv_train))
         return DeferredLoss(self.amf)
 
@@ -55,13 +47,13 @@ class AMF_model(BPRMF_batch_model):
     def build_perturbation(self, batch):
         """FGSM (:133-161): Delta = eps * normalize(grad) on the batch's rows, zero elsewhere."""
         u, i, j = (self._as_index(x) for x in batch)
-        self._weights_version += 1
+        self._touch()
         self.amf.perturb(u, i, j, self._l_w, self._l_b, self._eps)
 
     def build_msap_perturbation(self, batch, eps_iter, nb_iter):
         """MSAP (:163-197): nb_iter clipped steps of size eps_iter."""
         u, i, j = (self._as_index(x) for x in batch)
-        self._weights_version += 1
+        self._touch()
         if int(nb_iter) < 1:
             self.amf.clear_delta()                               # (the reference's loop body never runs: Delta stays zero)
             return
@@ -78,11 +70,9 @@ class AMF_model(BPRMF_batch_model):
     def recommend(self, mask, k, start, stop, item_offset=0, adversarial=False):
         if not adversarial:
             return super().recommend(mask, k, start, stop, item_offset)
-        kind, csr = mask if mask is not None else (None, None)
         self._scored_version = -1                                # the item image of the screened kernels is another table's now
         Gu, Gi, Bi = self._tables(True)
-        return ops.score_topk(self.ctx, Gu, Gi, Bi, start, stop, k, excl=csr if kind == "excl" else None,
-                              cand=csr if kind == "cand" else None, item_offset=item_offset)
+        return ops.score_topk(self.ctx, Gu, Gi, Bi, start, stop, k, **ops.mask_kwargs(mask), item_offset=item_offset)
 
     def rank(self, mask, targets, start, stop, adversarial=False):
         Gu, Gi, Bi = self._tables(adversarial)

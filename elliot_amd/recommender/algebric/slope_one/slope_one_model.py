@@ -8,15 +8,14 @@ freq, dev, user_mean and every prediction equal the reference's bit for bit.
 
 freq and dev START FROM ZERO.  The reference starts them from np.empty and relies on fresh pages being zero.
 """
-import pickle
-
 import numpy as np
 
 from .... import ops
+from ...device_model import DeviceModel
 from ...attribute_profiles import train_rows_in_dict_order
 
 
-class SlopeOneModel(object):
+class SlopeOneModel(DeviceModel):
     """freq, dev, user_mean and the scoring table on the device; recommend() is the RecMixin scoring hook."""
 
     def __init__(self, data, ctx):
@@ -42,11 +41,3 @@ class SlopeOneModel(object):
 
     def set_model_state(self, saving_dict):
         self.state.set_model(saving_dict["freq"], saving_dict["dev"], saving_dict["user_mean"])
-
-    def load_weights(self, path):
-        with open(path, "rb") as f:
-            self.set_model_state(pickle.load(f))
-
-    def save_weights(self, path):
-        with open(path, "wb") as f:
-            pickle.dump(self.get_model_state(), f)

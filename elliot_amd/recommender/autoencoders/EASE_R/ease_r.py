@@ -17,16 +17,15 @@ block of users (ops.EaseDeviceState).  Deviations, all documen
     allocated; too little is refused with a ValueError stating the bytes.
 save_weights / load_weights pickle B with l2_norm and neighborhood (the reference keeps no checkpoint of its own).
 """
-import pickle
-
 import numpy as np
 
 from .... import ops
+from ...device_model import DeviceModel
 from ...base_recommender_model import BaseRecommenderModel, init_charger
 from ...recommender_utils_mixin import RecMixin
 
 
-class EaseModel(object):
+class EaseModel(DeviceModel):
     """B (float32 [I, I]) and the train ratings on the device; recommend() is the RecMixin scoring hook."""
 
     def __init__(self, data, l2_norm, neighborhood, ctx):
@@ -52,14 +51,6 @@ class EaseModel(object):
         self._l2_norm = float(saving_dict["l2_norm"])
         self._neighborhood = int(saving_dict["neighborhood"])
         self.state.set_weights(saving_dict["B"])
-
-    def load_weights(self, path):
-        with open(path, "rb") as f:
-            self.set_model_state(pickle.load(f))
-
-    def save_weights(self, path):
-        with open(path, "wb") as f:
-            pickle.dump(self.get_model_state(), f)
 
 
 class EASER(RecMixin, BaseRecommenderModel):

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from .... import ops
-from ...latent_factor_models.BPRMF_batch.BPRMF_batch_model import DeferredLoss
+from ...device_model import DeferredLoss, DeviceModel
 
 
 def _glorot_normal(rs, fan_in, fan_out):
@@ -22,7 +22,7 @@ def _glorot_normal(rs, fan_in, fan_out):
     return (x * std).astype(np.float32)
 
 
-class VariationalAutoEncoder:
+class VariationalAutoEncoder(DeviceModel):
     def __init__(self, original_dim, intermediate_dim=600, latent_dim=200, learning_rate=0.001, dropout_rate=0,
                  regularization_lambda=0.01, random_seed=42, name="VariationalAutoEncoder", ctx=None, train_csr=None,
                  max_batch=512, init_weights=None, **kwargs):
@@ -69,17 +69,12 @@ class VariationalAutoEncoder:
     def get_top_k(self, preds, train_mask, k=100, offset=None):
         """:157-159.  `preds` = the block predict(start, stop) returned; the tagged CSR mask covers ALL users, so the rows of
         the block are addressed by `offset` (default: the start of the last predict call)."""
-        kind, csr = train_mask
         row0 = int(getattr(self, "_row0", 0) if offset is None else offset)
-        idx, val = ops.dense_topk(self.ctx, preds, row0, row0 + preds.shape[0], k,
-                                  excl=csr if kind == "excl" else None, cand=csr if kind == "cand" else None)
+        idx, val = ops.dense_topk(self.ctx, preds, row0, row0 + preds.shape[0], k, **ops.mask_kwargs(train_mask))
         return val, idx
 
     def recommend(self, mask, k, start, stop, item_offset=0):
-        preds = self.predict(start, stop)
-        kind, csr = mask if mask is not None else (None, None)
-        return ops.dense_topk(self.ctx, preds, start, stop, k, excl=csr if kind == "excl" else None,
-                              cand=csr if kind == "cand" else None)
+        return ops.dense_topk(self.ctx, self.predict(start, stop), start, stop, k, **ops.mask_kwargs(mask))
 
     def rank(self, mask, targets, start, stop):
         """Positions of the entries of rows [start, stop) of `targets` in the full rankings of predict(start, stop)
@@ -87,7 +82,7 @@ class VariationalAutoEncoder:
         preds = self.predict(start, stop)
         return ops.dense_rank(self.ctx, preds, start, stop, targets, **ops.mask_kwargs(mask))
 
-    def save_weights(self, path):
+    def save_weights(self, path):                 # the state's own dict, and a load rebuilds the state from it
         with open(path, "wb") as f:
             pickle.dump(self.state.weights(), f)
 

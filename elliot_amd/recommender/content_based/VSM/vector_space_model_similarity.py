@@ -5,17 +5,16 @@ sklearn's cosine_similarity(user_profiles, item_profiles) normalises the rows of
 el_knn_score_topk with A = the user profiles and B = the transposed item profiles (columns ascending): the same sums in the same
 order, masked and cut to the top-k per user, without the [U, I] block.
 """
-import pickle
-
 import numpy as np
 
 from .... import ops
+from ...device_model import DeviceModel
 from ... import attribute_profiles as ap
 
 SIMILARITIES = ("cosine",)
 
 
-class Similarity(object):
+class Similarity(DeviceModel):
 
     def __init__(self, data, user_profile_matrix, item_attribute_matrix, similarity, ctx):
         """The two matrices are functions without arguments, called by initialize() only."""
@@ -41,9 +40,7 @@ class Similarity(object):
         self._upload()
 
     def recommend(self, mask, k, start, stop):
-        kind, csr = mask if mask is not None else (None, None)
-        excl, cand = (csr if kind == "excl" else None), (csr if kind == "cand" else None)
-        return ops.knn_score_topk(self.ctx, self._Ad, self._Ad_vals, self._Bd, self._Bd_vals, start, stop, k, excl=excl, cand=cand)
+        return ops.knn_score_topk(self.ctx, self._Ad, self._Ad_vals, self._Bd, self._Bd_vals, start, stop, k, **ops.mask_kwargs(mask))
 
     def get_model_state(self):
         out = {"_similarity": self._similarity}
@@ -60,11 +57,3 @@ class Similarity(object):
         self._A, self._B = (sp.csr_matrix((saving_dict[f"{t}_data"], saving_dict[f"{t}_indices"], saving_dict[f"{t}_indptr"]),
                                           shape=tuple(saving_dict[f"{t}_shape"])) for t in ("_A", "_B"))
         self._upload()
-
-    def load_weights(self, path):
-        with open(path, "rb") as f:
-            self.set_model_state(pickle.load(f))
-
-    def save_weights(self, path):
-        with open(path, "wb") as f:
-            pickle.dump(self.get_model_state(), f)

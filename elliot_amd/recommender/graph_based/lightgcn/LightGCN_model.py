@@ -9,13 +9,11 @@ sparse product into row blocks: accepted and ignored.
 Deviation from the reference: `embed_k` (the plugin's `latent_dim`, shortcut `factors`) must be a multiple of 4 -- the propagation kernels move rows as
 16-byte vectors -- and the constructor refuses any other width with a ValueError; the reference accepts any width.
 """
-import pickle
-
 import numpy as np
 import torch
 
 from .... import ops
-from ...latent_factor_models.BPRMF_batch.BPRMF_batch_model import DeferredLoss
+from ...device_model import DeferredLoss, DeviceModel
 
 
 ADAM_MOMENTS = ("mGu", "vGu", "mGi", "vGi")
@@ -38,7 +36,7 @@ def restore_adam(b, d, complete):
             getattr(b, n).zero_()
 
 
-class LightGCNModel:
+class LightGCNModel(DeviceModel):
     def __init__(self, num_users, num_items, learning_rate, embed_k, l_w, n_layers, n_fold, adjacency, laplacian, random_seed,
                  name="LightGCN", ctx=None, init_weights=None, **kwargs):
         require_multiple_of_4("embed_k (latent_dim, factors)", embed_k)
@@ -54,37 +52,22 @@ class LightGCNModel:
         lap.sort_indices()
         self.graph = ops.GraphCSR(self.ctx, lap.indptr, lap.indices, lap.data.astype(np.float32), self.num_users, self.embed_k)
         self.state = ops.LightGcnDeviceState(self.ctx, Gu, Gi, self.graph, n_layers=self.n_layers)
-        self._weights_version, self._scored_version = 0, -1
-
-    def _as_index(self, x):
-        if isinstance(x, torch.Tensor):
-            return x.reshape(-1).to(device=self.ctx.device, dtype=torch.int32).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32)).to(self.ctx.device)
 
     def train_step(self, batch):
         u, i, j = (self._as_index(x) for x in batch)
-        self._weights_version += 1
+        self._touch()
         self.state.train_step(u, i, j, self.learning_rate, self.l_w)
         return DeferredLoss(self.state)
 
     def recommend(self, mask, k, start, stop, item_offset=0):
-        kind, csr = mask if mask is not None else (None, None)
         st = self.state
-        same = self._scored_version == self._weights_version
-        self._scored_version = self._weights_version
-        return ops.score_topk(self.ctx, st.Gu, st.Gi, None, start, stop, k, excl=csr if kind == "excl" else None,
-                              cand=csr if kind == "cand" else None, item_offset=item_offset, items_unchanged=same)
+        return ops.score_topk(self.ctx, st.Gu, st.Gi, None, start, stop, k, **ops.mask_kwargs(mask), item_offset=item_offset,
+                              items_unchanged=self._items_unchanged())
 
     def rank(self, mask, targets, start, stop):
         """Positions of the entries of rows [start, stop) of `targets` in the order recommend() selects by (el_score_rank)."""
         st = self.state
         return ops.score_rank(self.ctx, st.Gu, st.Gi, None, start, stop, targets, **ops.mask_kwargs(mask))
-
-    def get_top_k(self, predictions, train_mask, k=100):
-        kind, csr = train_mask
-        idx, val = ops.dense_topk(self.ctx, predictions, 0, predictions.shape[0], k, excl=csr if kind == "excl" else None,
-                                  cand=csr if kind == "cand" else None)
-        return val, idx
 
     def get_model_state(self):
         b = self.state.bpr
@@ -96,15 +79,7 @@ class LightGCNModel:
 
     def set_model_state(self, d):
         b = self.state.bpr
-        self._weights_version += 1
+        self._touch()
         b.Gu.copy_(torch.from_numpy(d["Gu"]))
         b.Gi.copy_(torch.from_numpy(d["Gi"]))
         restore_adam(b, d, all(n in d for n in ADAM_MOMENTS))
-
-    def save_weights(self, path):
-        with open(path, "wb") as f:
-            pickle.dump(self.get_model_state(), f)
-
-    def load_weights(self, path):
-        with open(path, "rb") as f:
-            self.set_model_state(pickle.load(f))

@@ -12,17 +12,15 @@ Deviation from the reference: `embed_k` (the plugin's `latent_dim`, shortcut `fa
 propagation kernels move rows as 16-byte vectors -- and the constructor refuses any other width with a ValueError; the reference accepts
 any width.
 """
-import pickle
-
 import numpy as np
 import torch
 
 from .... import ops
-from ...latent_factor_models.BPRMF_batch.BPRMF_batch_model import DeferredLoss
+from ...device_model import DeferredLoss, DeviceModel, glorot_uniform
 from ..lightgcn.LightGCN_model import ADAM_MOMENTS, require_multiple_of_4, restore_adam
 
 
-class NGCFModel:
+class NGCFModel(DeviceModel):
     def __init__(self, num_users, num_items, learning_rate, embed_k, l_w, weight_size, n_layers, node_dropout, message_dropout, n_fold,
                  adjacency, laplacian, random_seed, name="NGFC", ctx=None, init_weights=None, **kwargs):
         require_multiple_of_4("embed_k (latent_dim, factors)", embed_k)
@@ -41,9 +39,7 @@ class NGCFModel:
         else:
             Gu, Gi = np.zeros((self.num_users, W), np.float32), np.zeros((self.num_items, W), np.float32)     # :88-91 tf.zeros
         if layers is None:
-            def glorot(a, b):
-                lim = np.sqrt(6.0 / (a + b))
-                return rs.uniform(-lim, lim, size=(a, b)).astype(np.float32)
+            glorot = lambda a, b: glorot_uniform(rs, a, b)
             layers = []
             for k in range(int(n_layers)):
                 kin, kout = self.weight_size_list[k], self.weight_size_list[k + 1]
@@ -58,37 +54,22 @@ class NGCFModel:
         self.graph = ops.GraphCSR(self.ctx, lap.indptr, lap.indices, vals, self.num_users, max(self.weight_size_list))
         drop = [float(x) for x in message_dropout] if len(message_dropout) else [0.0] * int(n_layers)
         self.state = ops.NgcfDeviceState(self.ctx, Gu, Gi, self.graph, layers, self.embed_k, message_dropout=drop, dropout_seed=random_seed)
-        self._weights_version, self._scored_version = 0, -1
-
-    def _as_index(self, x):
-        if isinstance(x, torch.Tensor):
-            return x.reshape(-1).to(device=self.ctx.device, dtype=torch.int32).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32)).to(self.ctx.device)
 
     def train_step(self, batch):
         u, i, j = (self._as_index(x) for x in batch)
-        self._weights_version += 1
+        self._touch()
         self.state.train_step(u, i, j, self.learning_rate, self.l_w)
         return DeferredLoss(self.state)
 
     def recommend(self, mask, k, start, stop, item_offset=0):
-        kind, csr = mask if mask is not None else (None, None)
         st = self.state
-        same = self._scored_version == self._weights_version
-        self._scored_version = self._weights_version
-        return ops.score_topk(self.ctx, st.Gu, st.Gi, None, start, stop, k, excl=csr if kind == "excl" else None,
-                              cand=csr if kind == "cand" else None, item_offset=item_offset, items_unchanged=same)
+        return ops.score_topk(self.ctx, st.Gu, st.Gi, None, start, stop, k, **ops.mask_kwargs(mask), item_offset=item_offset,
+                              items_unchanged=self._items_unchanged())
 
     def rank(self, mask, targets, start, stop):
         """Positions of the entries of rows [start, stop) of `targets` in the order recommend() selects by (el_score_rank)."""
         st = self.state
         return ops.score_rank(self.ctx, st.Gu, st.Gi, None, start, stop, targets, **ops.mask_kwargs(mask))
-
-    def get_top_k(self, predictions, train_mask, k=100):
-        kind, csr = train_mask
-        idx, val = ops.dense_topk(self.ctx, predictions, 0, predictions.shape[0], k, excl=csr if kind == "excl" else None,
-                                  cand=csr if kind == "cand" else None)
-        return val, idx
 
     def get_model_state(self):
         st, b = self.state, self.state.bpr
@@ -102,7 +83,7 @@ class NGCFModel:
 
     def set_model_state(self, d):
         st, b = self.state, self.state.bpr
-        self._weights_version += 1
+        self._touch()
         b.Gu.copy_(torch.from_numpy(d["Gu"]))
         b.Gi.copy_(torch.from_numpy(d["Gi"]))
         for l, src in zip(st.layers, d.get("layers", [])):
@@ -117,11 +98,3 @@ class NGCFModel:
                     m.copy_(torch.from_numpy(src[k][0])), v.copy_(torch.from_numpy(src[k][1]))
                 else:
                     m.zero_(), v.zero_()
-
-    def save_weights(self, path):
-        with open(path, "wb") as f:
-            pickle.dump(self.get_model_state(), f)
-
-    def load_weights(self, path):
-        with open(path, "rb") as f:
-            self.set_model_state(pickle.load(f))

@@ -49,10 +49,9 @@ class KnnSimilarity(SparseWModel):
     def recommend(self, mask, k, start, stop):
         if self._preds is None:
             return super().recommend(mask, k, start, stop)
-        kind, csr = mask if mask is not None else (None, None)      # restored from a reference checkpoint: its dense block
-        excl, cand = (csr if kind == "excl" else None), (csr if kind == "cand" else None)
+        # restored from a reference checkpoint: its dense block
         block = torch.from_numpy(np.ascontiguousarray(self._preds[start:stop], dtype=np.float32)).to(self.ctx.device)
-        return ops.dense_topk(self.ctx, block, start, stop, k, excl=excl, cand=cand)
+        return ops.dense_topk(self.ctx, block, start, stop, k, **ops.mask_kwargs(mask))
 
     def hyper_state(self):
         return {"_similarity": self._similarity, "_num_neighbors": self._num_neighbors, "_implicit": self._implicit}

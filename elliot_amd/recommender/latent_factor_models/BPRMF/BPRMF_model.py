@@ -6,15 +6,14 @@ level share no user/item row), each level is one conflict-free launch of `el_bpr
 exactly the predecessor state it would see in the sequential loop.  `hogwild=True` applies the whole batch in
 one launch instead (not the reference's semantics).
 """
-import pickle
-
 import numpy as np
 import torch
 
 from .... import ops
+from ...device_model import DeviceModel
 
 
-class MFModel(object):
+class MFModel(DeviceModel):
     def __init__(self, F, data, lr, user_regularization, bias_regularization, positive_item_regularization,
                  negative_item_regularization, random_seed, *args, ctx=None, hogwild=False, init_weights=None):
         self.ctx = ctx or ops.get_context(0)
@@ -61,11 +60,8 @@ class MFModel(object):
 
     def recommend(self, mask, k, start, stop, item_offset=0):
         """get_user_predictions (:70-85) for users [start, stop): fp64 scores, masked top-k."""
-        kind, csr = mask if mask is not None else (None, None)
         st = self.state
-        return ops.score_topk_f64(self.ctx, st.P, st.Q, st.b, start, stop, k,
-                                  excl=csr if kind == "excl" else None, cand=csr if kind == "cand" else None,
-                                  item_offset=item_offset)
+        return ops.score_topk_f64(self.ctx, st.P, st.Q, st.b, start, stop, k, **ops.mask_kwargs(mask), item_offset=item_offset)
 
     def rank(self, mask, targets, start, stop):
         """Positions of the entries of rows [start, stop) of `targets` in the order recommend() selects by (el_score_rank_f64)."""
@@ -82,11 +78,3 @@ class MFModel(object):
         st.b.copy_(torch.from_numpy(np.asarray(d["_item_bias"], dtype=np.float64)))
         st.P.copy_(torch.from_numpy(np.asarray(d["_user_factors"], dtype=np.float64)))
         st.Q.copy_(torch.from_numpy(np.asarray(d["_item_factors"], dtype=np.float64)))
-
-    def load_weights(self, path):
-        with open(path, "rb") as f:
-            self.set_model_state(pickle.load(f))
-
-    def save_weights(self, path):
-        with open(path, "wb") as f:
-            pickle.dump(self.get_model_state(), f)

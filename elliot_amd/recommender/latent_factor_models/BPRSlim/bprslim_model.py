@@ -9,15 +9,14 @@ order in which a triplet's sum over the seen items is taken, and by nothing else
 
 S STARTS FROM ZERO.  The reference starts it from np.empty and relies on fresh pages being zero.
 """
-import pickle
-
 import numpy as np
 import torch
 
 from .... import ops
+from ...device_model import DeviceModel
 
 
-class BPRSlimModel(object):
+class BPRSlimModel(DeviceModel):
     """S and its scoring table on the device; recommend() is the RecMixin scoring hook."""
 
     def __init__(self, data, lr, lj_reg, li_reg, ctx):
@@ -46,11 +45,3 @@ class BPRSlimModel(object):
 
     def set_model_state(self, saving_dict):
         self.state.set_model(saving_dict["_s_dense"])
-
-    def load_weights(self, path):
-        with open(path, "rb") as f:
-            self.set_model_state(pickle.load(f))
-
-    def save_weights(self, path):
-        with open(path, "wb") as f:
-            pickle.dump(self.get_model_state(), f)

@@ -7,7 +7,8 @@ really updates there depends on trace timing; this model implements what the plu
 import numpy as np
 
 from .... import ops
-from ..pointwise_model import PointwiseFactorModel, glorot_uniform
+from ...device_model import glorot_uniform
+from ..pointwise_model import PointwiseFactorModel
 
 
 class LogisticMatrixFactorizationModel(PointwiseFactorModel):

@@ -4,15 +4,14 @@ Same constructor (F, data, lr, reg, random_seed), same initial draw (np.random.s
 :37-56), fp64 parameters in HBM; `train_step(batch)` runs the batch's samples in order (el_mf2020_train); scoring through
 `recommend(...)`: the fp64 score b_u + (g + b_i + p_u . q_i) of :115-116 and a masked top-k on the device.
 """
-import pickle
-
 import numpy as np
 import torch
 
 from .... import ops
+from ...device_model import DeviceModel
 
 
-class MFModel:
+class MFModel(DeviceModel):
     def __init__(self, F, data, lr, reg, random_seed, *args, ctx=None, init_weights=None):
         self.ctx = ctx or ops.get_context(0)
         self._factors, self._lr, self._reg = int(F), lr, reg
@@ -38,10 +37,8 @@ class MFModel:
     def recommend(self, mask, k, start, stop, item_offset=0):
         """prepare_predictions (:115-116) for users [start, stop) + the masked top-k (:62-78), fp64 scores."""
         st = self.state
-        kind, csr = mask if mask is not None else (None, None)
         bias = st.gb + st.bi
-        idx, val = ops.score_topk_f64(self.ctx, st.P, st.Q, bias, start, stop, k, excl=csr if kind == "excl" else None,
-                                      cand=csr if kind == "cand" else None, item_offset=item_offset)
+        idx, val = ops.score_topk_f64(self.ctx, st.P, st.Q, bias, start, stop, k, **ops.mask_kwargs(mask), item_offset=item_offset)
         return idx, val + st.bu[start:stop, None]          # (the user bias shifts a user's whole row: it does not change the order)
 
     def rank(self, mask, targets, start, stop):
@@ -62,11 +59,3 @@ class MFModel:
         st.bi.copy_(torch.from_numpy(np.asarray(d["_item_bias"])))
         st.P.copy_(torch.from_numpy(np.asarray(d["_user_factors"])))
         st.Q.copy_(torch.from_numpy(np.asarray(d["_item_factors"])))
-
-    def save_weights(self, path):
-        with open(path, "wb") as f:
-            pickle.dump(self.get_model_state(), f)
-
-    def load_weights(self, path):
-        with open(path, "rb") as f:
-            self.set_model_state(pickle.load(f))

@@ -5,14 +5,13 @@ item_vec = (diag(sigma) Vt)^T, a dense user_vec[u] @ item_vec.T and a masked arg
 ops.PureSvdDeviceState (el_spmm_csr_f64, el_psvd_orth, el_gram_f64, el_psvd_project, el_psvd_signs; el_score_topk +
 el_topk_pad per block of users).  The tables stay on the device between build and top-k.
 """
-import pickle
-
 import numpy as np
 
 from .... import ops
+from ...device_model import DeviceModel
 
 
-class PureSVDModel(object):
+class PureSVDModel(DeviceModel):
 
     def __init__(self, factors, data, random_seed, ctx):
         self._data = data
@@ -52,14 +51,3 @@ class PureSVDModel(object):
     def set_model_state(self, saving_dict):
         self.state.set_weights(np.asarray(saving_dict["user_vec"]), np.asarray(saving_dict["item_vec"]))
         self._host_tables = None
-
-    def save_weights(self, path):
-        """One pickle of the two host tables under the keys of get_model_state()."""
-        state = self.get_model_state()
-        with open(path, "wb") as out:
-            pickle.dump(state, out)
-
-    def load_weights(self, path):
-        with open(path, "rb") as src:
-            state = pickle.load(src)
-        self.set_model_state(state)

@@ -5,12 +5,11 @@ Deviations, all documented: rows are solved by Cholesky (agreement to ~1e-12, no
 never written (the reference stores the confidences into data.sp_i_train in place); the dense [U, I] pred_mat is not kept --
 scores are formed and selected per block by el_score_topk_f64, and a checkpoint holds pred_mat only when U * I <= 2^28.
 """
-import pickle
-
 import numpy as np
 import scipy.sparse as sp
 
 from ... import ops
+from ..device_model import DeviceModel
 
 PRED_MAT_MAX = 1 << 28
 
@@ -56,7 +55,7 @@ def check_factors(factors):
         raise ValueError(f"factors={factors} unsupported: the ALS kernels solve 1..{ops._lib.EL_ALS_MAX_F} factors")
 
 
-class AlsModel(object):
+class AlsModel(DeviceModel):
     """X, Y drawn as the reference draws them (np.random seeded with `seed`: X first, then Y, normal(scale=0.01)), trained by
     ops.AlsDeviceState with the Gram timing of the model (gram="fresh": iALS, "stale": WRMF)."""
     gram = "fresh"
@@ -109,14 +108,6 @@ class AlsModel(object):
             if m.shape != tuple(dst.shape):
                 raise ValueError(f"checkpoint {key} has shape {m.shape}, the model expects {tuple(dst.shape)}")
             dst.copy_(ops.torch.from_numpy(np.ascontiguousarray(m, dtype=np.float64)))
-
-    def load_weights(self, path):
-        with open(path, "rb") as f:
-            self.set_model_state(pickle.load(f))
-
-    def save_weights(self, path):
-        with open(path, "wb") as f:
-            pickle.dump(self.get_model_state(), f)
 
 
 class IalsModel(AlsModel):

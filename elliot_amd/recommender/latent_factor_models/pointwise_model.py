@@ -2,21 +2,22 @@
 reference plugins use -- train_step(batch), predict / get_recs on index grids, get_top_k, get/set_model_state -- on top of
 ops.PwmfDeviceState (el_pwmf_* kernels).  Reference: latent_factor_models/MF/matrix_factorization_model.py:18-101 and its
 three siblings; what differs between them is the table below (link, biases, optimiser, initialiser)."""
-import pickle
-
 import numpy as np
 import torch
 
 from ... import ops
-from .BPRMF_batch.BPRMF_batch_model import DeferredLoss
+from ..device_model import DeferredLoss, DeviceModel, glorot_uniform
 
 
-def glorot_uniform(rs, rows, cols):
-    lim = np.sqrt(6.0 / (rows + cols))          # tf.initializers.GlorotUniform: the distribution, not TF's bit stream
-    return rs.uniform(-lim, lim, size=(rows, cols)).astype(np.float32)
+def initial_weights(rs, U, I, F, with_biases=False):
+    """GlorotUniform tables, and biases drawn as [rows, 1] kernels: Gu, Gi, then Bu, Bi."""
+    w = {"Gu": glorot_uniform(rs, U, F), "Gi": glorot_uniform(rs, I, F)}
+    if with_biases:
+        w["Bu"], w["Bi"] = glorot_uniform(rs, U, 1)[:, 0].copy(), glorot_uniform(rs, I, 1)[:, 0].copy()
+    return w
 
 
-class PointwiseFactorModel:
+class PointwiseFactorModel(DeviceModel):
     kind = "mse"             # ops.PW_KINDS
     optimizer = "adam"       # ops.PW_OPTS
     with_biases = False
@@ -32,21 +33,13 @@ class PointwiseFactorModel:
         self._side = "both"
 
     def initial_weights(self, rs, U, I, F):
-        w = {"Gu": glorot_uniform(rs, U, F), "Gi": glorot_uniform(rs, I, F)}
-        if self.with_biases:
-            w["Bu"], w["Bi"] = glorot_uniform(rs, U, 1)[:, 0].copy(), glorot_uniform(rs, I, 1)[:, 0].copy()
-        return w
-
-    def _idx(self, x):
-        if isinstance(x, torch.Tensor):
-            return x.reshape(-1).to(device=self.ctx.device, dtype=torch.int32).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32)).to(self.ctx.device)
+        return initial_weights(rs, U, I, F, self.with_biases)
 
     def train_step(self, batch):
         user, item, label = batch
         y = label if isinstance(label, torch.Tensor) else torch.from_numpy(np.asarray(label, dtype=np.float32))
         y = y.reshape(-1).to(device=self.ctx.device, dtype=torch.float32).contiguous()
-        self.state.train_step(self._idx(user), self._idx(item), y, self._lr, side=self._side)
+        self.state.train_step(self._as_index(user), self._as_index(item), y, self._lr, side=self._side)
         return DeferredLoss(self.state)
 
     def train_epoch(self, sampler, events, batch_size):
@@ -58,31 +51,15 @@ class PointwiseFactorModel:
     def predict(self, inputs, training=False, **kwargs):
         user, item = inputs
         shape = tuple(user.shape) if isinstance(user, torch.Tensor) else tuple(np.shape(user))
-        return self.state.forward(self._idx(user), self._idx(item)).reshape(shape)
+        return self.state.forward(self._as_index(user), self._as_index(item)).reshape(shape)
 
     get_recs = predict
 
     def recommend(self, mask, k, start, stop, item_offset=0):
-        kind, csr = mask if mask is not None else (None, None)
-        return self.state.recommend(start, stop, k, excl=csr if kind == "excl" else None,
-                                    cand=csr if kind == "cand" else None)
-
-    def get_top_k(self, preds, train_mask, k=100):
-        kind, csr = train_mask
-        idx, val = ops.dense_topk(self.ctx, preds, 0, preds.shape[0], k, excl=csr if kind == "excl" else None,
-                                  cand=csr if kind == "cand" else None)
-        return val, idx
+        return self.state.recommend(start, stop, k, **ops.mask_kwargs(mask))
 
     def get_model_state(self):
         return self.state.weights()
 
     def set_model_state(self, saved):
         self.state.load(saved)
-
-    def save_weights(self, path):
-        with open(path, "wb") as f:
-            pickle.dump(self.get_model_state(), f)
-
-    def load_weights(self, path):
-        with open(path, "rb") as f:
-            self.set_model_state(pickle.load(f))

@@ -8,15 +8,10 @@ import numpy as np
 import torch
 
 from .... import ops
-from ...latent_factor_models.BPRMF_batch.BPRMF_batch_model import DeferredLoss
+from ...device_model import DeferredLoss, DeviceModel, glorot_uniform
 
 
-def _glorot_uniform(rs, rows, cols):
-    lim = np.sqrt(6.0 / (rows + cols))          # tf.initializers.GlorotUniform (distribution only)
-    return rs.uniform(-lim, lim, size=(rows, cols)).astype(np.float32)
-
-
-class _PointwiseModel:
+class _PointwiseModel(DeviceModel):
     """Shared device plumbing: train_step on (user, item, label), pair scoring, full-catalogue top-k."""
 
     def _setup(self, ctx, weights, max_batch, lr, num_users, num_items, dropout=0.0, seed=42):
@@ -24,19 +19,13 @@ class _PointwiseModel:
         self.num_users, self.num_items, self._lr = num_users, num_items, lr
         self._dropout, self._seed = float(dropout or 0.0), seed
         self.state = ops.NmfDeviceState(self.ctx, weights, max_batch, dropout=self._dropout, dropout_seed=seed)
-        self._weights_version, self._scored_version = 0, -1          # recommend() keeps the item-side image between blocks
-
-    def _idx(self, x):
-        if isinstance(x, torch.Tensor):
-            return x.reshape(-1).to(device=self.ctx.device, dtype=torch.int32).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32)).to(self.ctx.device)
 
     def train_step(self, batch):
         user, pos, label = batch
         y = label if isinstance(label, torch.Tensor) else torch.from_numpy(np.asarray(label, dtype=np.float32))
         y = y.reshape(-1).to(device=self.ctx.device, dtype=torch.float32).contiguous()
-        u, i = self._idx(user), self._idx(pos)
-        self._weights_version += 1
+        u, i = self._as_index(user), self._as_index(pos)
+        self._touch()
         # the reference takes ONE optimiser step per batch (neural_matrix_factorization_model.py:96-106): a batch beyond the
         # activation buffers grows them (or fails loudly when HBM cannot hold them) -- it is never split into several steps
         self.state.ensure_batch(u.numel())
@@ -47,7 +36,7 @@ class _PointwiseModel:
         """(user grid, item grid) -> probabilities, same shape (model :120-144; GMF :81-89)."""
         user, item = inputs
         shape = tuple(np.shape(user)) if not isinstance(user, torch.Tensor) else tuple(user.shape)
-        u, i = self._idx(user), self._idx(item)
+        u, i = self._as_index(user), self._as_index(item)
         out = torch.empty(u.numel(), dtype=torch.float32, device=self.ctx.device)
         B = self.state.Bmax
         for s in range(0, u.numel(), B):
@@ -60,26 +49,16 @@ class _PointwiseModel:
         neural_matrix_factorization_model.py:119-144); here NeuMF goes through el_nmf_score_topk (layer 1 separable, layers 2-3
         and the head on fp32 MFMA tiles per pair, selection fused -- no [Ub, I] block) and GMF through the fused dot-product
         top-k kernels on the item image Imf * h (ops.NmfDeviceState.recommend)."""
-        kind, csr = mask if mask is not None else (None, None)
-        same = self._scored_version == self._weights_version          # block after block of one evaluation
-        self._scored_version = self._weights_version
-        return self.state.recommend(start, stop, k, excl=csr if kind == "excl" else None, cand=csr if kind == "cand" else None,
-                                    items_unchanged=same)
+        return self.state.recommend(start, stop, k, **ops.mask_kwargs(mask), items_unchanged=self._items_unchanged())
 
-    def get_top_k(self, preds, train_mask, k=100):
-        kind, csr = train_mask
-        idx, val = ops.dense_topk(self.ctx, preds, 0, preds.shape[0], k, excl=csr if kind == "excl" else None,
-                                  cand=csr if kind == "cand" else None)
-        return val, idx
-
-    def save_weights(self, path):
+    def save_weights(self, path):                 # the state's own dict, and a load rebuilds the state from it
         with open(path, "wb") as f:
             pickle.dump(self.state.weights(), f)
 
     def load_weights(self, path):
         with open(path, "rb") as f:
             self.state = ops.NmfDeviceState(self.ctx, pickle.load(f), self.state.Bmax, dropout=self._dropout, dropout_seed=self._seed)
-        self._weights_version += 1
+        self._touch()
 
 
 class NeuralMatrixFactorizationModel(_PointwiseModel):
@@ -92,18 +71,18 @@ class NeuralMatrixFactorizationModel(_PointwiseModel):
             rs = np.random.RandomState(random_seed)
             w = {}
             if is_mf_train:
-                w["Umf"], w["Imf"] = _glorot_uniform(rs, num_users, embed_mf_size), _glorot_uniform(rs, num_items, embed_mf_size)
+                w["Umf"], w["Imf"] = glorot_uniform(rs, num_users, embed_mf_size), glorot_uniform(rs, num_items, embed_mf_size)
             last = 0
             if is_mlp_train:
-                w["Umlp"] = _glorot_uniform(rs, num_users, embed_mlp_size)
-                w["Imlp"] = _glorot_uniform(rs, num_items, embed_mlp_size)
+                w["Umlp"] = glorot_uniform(rs, num_users, embed_mlp_size)
+                w["Imlp"] = glorot_uniform(rs, num_items, embed_mlp_size)
                 w["W"], w["b"], kin = [], [], 2 * embed_mlp_size
                 for units in mlp_hidden_size:
-                    w["W"].append(_glorot_uniform(rs, kin, units))
+                    w["W"].append(glorot_uniform(rs, kin, units))
                     w["b"].append(np.zeros(units, np.float32))
                     kin = units
                 last = mlp_hidden_size[-1]
-            w["hw"] = _glorot_uniform(rs, (embed_mf_size if is_mf_train else 0) + last, 1)[:, 0].copy()
+            w["hw"] = glorot_uniform(rs, (embed_mf_size if is_mf_train else 0) + last, 1)[:, 0].copy()
             w["hb"] = np.zeros(1, np.float32)
             init_weights = w
         self._setup(ctx, init_weights, max_batch, learning_rate, num_users, num_items, dropout=dropout, seed=random_seed)
@@ -118,7 +97,7 @@ class GeneralizedMatrixFactorizationModel(_PointwiseModel):
             raise NotImplementedError("GMF is_edge_weight_train=False is not reproduced (reference branch is ill-defined)")
         if init_weights is None:
             rs = np.random.RandomState(random_seed)
-            init_weights = {"Umf": _glorot_uniform(rs, num_users, embed_mf_size),
-                            "Imf": _glorot_uniform(rs, num_items, embed_mf_size),
-                            "hw": _glorot_uniform(rs, embed_mf_size, 1)[:, 0].copy()}
+            init_weights = {"Umf": glorot_uniform(rs, num_users, embed_mf_size),
+                            "Imf": glorot_uniform(rs, num_items, embed_mf_size),
+                            "hw": glorot_uniform(rs, embed_mf_size, 1)[:, 0].copy()}
         self._setup(ctx, init_weights, max_batch, learning_rate, num_users, num_items)

@@ -8,19 +8,17 @@ elliot/recommender/neural/UserAutoRec/userautorec_model.py:54-123 and .../ItemAu
 (el_autorec_train_step), which is all the loss reads.  `l_w` is accepted and ignored exactly like the reference: its
 kernel_regularizers are never added to the loss (train_step uses the squared error alone, :93-107 / :90-104).
 """
-import pickle
-
 import numpy as np
 import torch
 
 from ... import ops
 from ..autoencoders.vae.multi_vae_model import _glorot_normal
-from ..latent_factor_models.BPRMF_batch.BPRMF_batch_model import DeferredLoss
+from ..device_model import DeferredLoss, DeviceModel
 
 WEIGHT_ORDER = ("W1", "b1", "W2", "b2")          # keras.Model.get_weights(): encoder kernel, bias, decoder kernel, bias
 
 
-class AutoRecModel:
+class AutoRecModel(DeviceModel):
     out_act = None                               # "sigmoid" in the item variant
 
     def __init__(self, data, num_users, num_items, lr, hidden_neuron, l_w, random_seed=42, name="AutoRec", ctx=None,
@@ -55,11 +53,9 @@ class AutoRecModel:
         return self.state.predict_rows(self.train_csr, rows.to(device=self.ctx.device, dtype=torch.int32).contiguous())
 
     def _topk(self, preds, mask, k, start, stop):
-        kind, csr = mask if mask is not None else (None, None)
-        return ops.dense_topk(self.ctx, preds, start, stop, k, excl=csr if kind == "excl" else None,
-                              cand=csr if kind == "cand" else None)
+        return ops.dense_topk(self.ctx, preds, start, stop, k, **ops.mask_kwargs(mask))
 
-    def get_top_k(self, preds, train_mask, k=100, offset=0):
+    def get_top_k(self, preds, train_mask, k=100, offset=0):                 # the block's first row is `offset`, not user 0
         idx, val = self._topk(preds, train_mask, k, int(offset), int(offset) + preds.shape[0])
         return val, idx
 
@@ -70,11 +66,3 @@ class AutoRecModel:
 
     def set_model_state(self, saved):
         self._new_state(dict(zip(WEIGHT_ORDER, saved["weights"])))
-
-    def save_weights(self, path):
-        with open(path, "wb") as f:
-            pickle.dump(self.get_model_state(), f)
-
-    def load_weights(self, path):
-        with open(path, "rb") as f:
-            self.set_model_state(pickle.load(f))

@@ -4,15 +4,14 @@ checkpoint is W as a host CSR (`_W_data`, `_W_indices`, `_W_indptr`) beside the 
 
 A subclass gives initialize() (which builds _W / _W_vals), hyper_state() and set_hyper_state().
 """
-import pickle
-
 import numpy as np
 import scipy.sparse as sp
 
 from .. import ops
+from .device_model import DeviceModel
 
 
-class SparseWModel(object):
+class SparseWModel(DeviceModel):
 
     def __init__(self, data, ctx):
         self._data = data
@@ -34,9 +33,7 @@ class SparseWModel(object):
 
     def recommend(self, mask, k, start, stop):
         """Top-k of users [start, stop) under the tagged mask ("excl" | "cand", DeviceCSR): (idx, val) [n, k] on the device."""
-        kind, csr = mask if mask is not None else (None, None)
-        excl, cand = (csr if kind == "excl" else None), (csr if kind == "cand" else None)
-        return ops.knn_score_topk(self.ctx, *self._operands(), start, stop, k, excl=excl, cand=cand)
+        return ops.knn_score_topk(self.ctx, *self._operands(), start, stop, k, **ops.mask_kwargs(mask))
 
     def w_csr(self):
         """W as a host scipy CSR."""
@@ -54,11 +51,3 @@ class SparseWModel(object):
         ip = np.asarray(saving_dict["_W_indptr"], np.int64)
         self._W = ops.DeviceCSR(ip, saving_dict["_W_indices"], ip.shape[0] - 1, self.ctx.device)
         self._W_vals = ops.device_values(saving_dict["_W_data"], self.ctx.device)
-
-    def load_weights(self, path):
-        with open(path, "rb") as f:
-            self.set_model_state(pickle.load(f))
-
-    def save_weights(self, path):
-        with open(path, "wb") as f:
-            pickle.dump(self.get_model_state(), f)

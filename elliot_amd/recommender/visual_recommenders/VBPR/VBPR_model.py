@@ -9,13 +9,11 @@ Scoring restates predict_item_batch (:104-108) for all items at once: the image 
 the weights changed since the last scoring, then el_score_topk / el_score_rank run on it.  `predict` (:98-101) reads an attribute
 `self.F` that nothing sets; it cannot run in the reference and is not ported.
 """
-import pickle
-
 import numpy as np
 import torch
 
 from .... import ops
-from ...latent_factor_models.BPRMF_batch.BPRMF_batch_model import DeferredLoss
+from ...device_model import DeferredLoss, DeviceModel, glorot_uniform
 
 NAMES = ("Bi", "Gu", "Gi", "Tu", "E", "Bp")            # the reference's six variables: the keys of a checkpoint
 
@@ -25,18 +23,14 @@ def initial_weights(seed, num_users, num_items, factors, factors_d, num_image_fe
     (:40-51): Bi = 0, then Gu, Gi, Bp, Tu, E.  TF's seeded bit stream cannot be reproduced without TF -- the distribution is
     (SURVEY A.5)."""
     rs = np.random.RandomState(seed)
-
-    def glorot(rows, cols):
-        lim = np.sqrt(6.0 / (rows + cols))
-        return rs.uniform(-lim, lim, size=(rows, cols)).astype(np.float32)
     w = {"Bi": np.zeros(num_items, np.float32)}
-    w["Gu"], w["Gi"] = glorot(num_users, factors), glorot(num_items, factors)
-    w["Bp"] = glorot(num_image_feature, 1)
-    w["Tu"], w["E"] = glorot(num_users, factors_d), glorot(num_image_feature, factors_d)
+    w["Gu"], w["Gi"] = glorot_uniform(rs, num_users, factors), glorot_uniform(rs, num_items, factors)
+    w["Bp"] = glorot_uniform(rs, num_image_feature, 1)
+    w["Tu"], w["E"] = glorot_uniform(rs, num_users, factors_d), glorot_uniform(rs, num_image_feature, factors_d)
     return w
 
 
-class VBPRModel:
+class VBPRModel(DeviceModel):
     def __init__(self, factors=200, factors_d=20, learning_rate=0.001, l_w=0, l_b=0, l_e=0, num_image_feature=2048, num_users=100,
                  num_items=100, random_seed=42, name="VBPRMF", ctx=None, features=None, init_weights=None, **kwargs):
         self.ctx = ctx or ops.get_context(0)
@@ -50,18 +44,13 @@ class VBPRModel:
         Bi, Gu, Gi, Tu, E, Bp = (init_weights[n] for n in NAMES)
         self.vb = ops.VbprDeviceState(self.ctx, Gu, Gi, Bi, Tu, E, Bp, features)
         self.state = self.vb.base                                 # (Gu, Gi, Bi, their slots and the step counter)
-        self._weights_version, self._image_version, self._scored_version = 0, -1, -1
+        self._image_version = -1
 
     # -- training ---------------------------------------------------------------------------------------
-    def _as_index(self, x):
-        if isinstance(x, torch.Tensor):
-            return x.reshape(-1).to(device=self.ctx.device, dtype=torch.int32).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32)).to(self.ctx.device)
-
     def train_step(self, batch):
         """train_step (:70-95).  batch = (user, pos, neg), shapes [B] or [B, 1]; the feature rows are looked up on the device."""
         u, i, j = (self._as_index(x) for x in batch)
-        self._weights_version += 1
+        self._touch()
         self.vb.train_step(u, i, j, self._learning_rate, self._l_w, self._l_b, self._l_e)
         return DeferredLoss(self.vb)
 
@@ -73,15 +62,11 @@ class VBPRModel:
             self._image_version = self._weights_version
             self._scored_version = -1
             self.vb.image()
-        same = self._scored_version == self._weights_version
-        self._scored_version = self._weights_version
-        return self.vb._P, self.vb._Q, self.vb._bq, same
+        return self.vb._P, self.vb._Q, self.vb._bq, self._items_unchanged()
 
     def recommend(self, mask, k, start, stop, item_offset=0):
-        kind, csr = mask if mask is not None else (None, None)
         P, Q, bq, same = self._image()
-        return ops.score_topk(self.ctx, P, Q, bq, start, stop, k, excl=csr if kind == "excl" else None,
-                              cand=csr if kind == "cand" else None, item_offset=item_offset, items_unchanged=same)
+        return ops.score_topk(self.ctx, P, Q, bq, start, stop, k, **ops.mask_kwargs(mask), item_offset=item_offset, items_unchanged=same)
 
     def rank(self, mask, targets, start, stop):
         P, Q, bq, _ = self._image()
@@ -101,18 +86,10 @@ class VBPRModel:
         return d
 
     def set_model_state(self, d):
-        self._weights_version += 1
+        self._touch()
         for n, (th, m, v) in self._tensors().items():
             th.copy_(torch.from_numpy(np.ascontiguousarray(d[n])).reshape(th.shape))
             for slot, t in (("m" + n, m), ("v" + n, v)):
                 if slot in d:
                     t.copy_(torch.from_numpy(np.ascontiguousarray(d[slot])).reshape(t.shape))
         self.state.step = int(d.get("_step", 0))
-
-    def save_weights(self, path):
-        with open(path, "wb") as f:
-            pickle.dump(self.get_model_state(), f)
-
-    def load_weights(self, path):
-        with open(path, "rb") as f:
-            self.set_model_state(pickle.load(f))
