@@ -61,6 +61,14 @@ class VbprState(C.Structure):
                 ("EB", _f32p), ("gEB", _f32p), ("mEB", _f32p), ("vEB", _f32p), ("Feat", _f32p), ("Fd", C.c_int32), ("D", C.c_int64)]
 
 
+class FmState(C.Structure):
+    _fields_ = [("U", C.c_int64), ("I", C.c_int64), ("nF", C.c_int64), ("F", C.c_int32),
+                ("E", _f32p), ("w", _f32p), ("g0", _f32p), ("gE", _f32p), ("gw", _f32p), ("gg0", _f64p),
+                ("mE", _f32p), ("vE", _f32p), ("mw", _f32p), ("vw", _f32p), ("g0d", _f64p), ("mg0", _f64p), ("vg0", _f64p),
+                ("a_indptr", _i64p), ("a_indices", _i32p), ("t_indptr", _i64p), ("t_indices", _i32p), ("t_longest", C.c_int64),
+                ("slot", _i32p)]
+
+
 class BprsgdState(C.Structure):
     _fields_ = [
         ("P", _f64p), ("Q", _f64p), ("b", _f64p),
@@ -212,6 +220,14 @@ PROTOTYPES = {
     "el_vbpr_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(VbprState), C.c_float, C.c_int32, C.c_float]),
     "el_vbpr_image_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64]),
     "el_vbpr_item_image": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(VbprState), _f32p, _f32p, _f32p, C.c_void_p, C.c_size_t]),
+    "el_fm_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
+    "el_fm_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FmState), _i32p, _i32p, _f32p, C.c_int64, _f64p, C.c_void_p, C.c_size_t]),
+    "el_fm_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FmState), C.c_int32, C.c_float]),
+    "el_fm_train_step": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FmState), _i32p, _i32p, _f32p, C.c_int64, C.c_int32, C.c_float, _f64p,
+                                   C.c_void_p, C.c_size_t]),
+    "el_fm_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FmState), _i32p, _i32p, C.c_int64, _f32p]),
+    "el_fm_item_image": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FmState), _f32p, _f32p]),
+    "el_fm_labels": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _f32p, _i32p, _i32p, _f32p, C.c_int64, _f32p]),
     "el_spmm_csr_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GraphCsr), _f32p, _f32p, C.c_int32, _f32p, _f32p]),
     "el_lightgcn_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "el_lightgcn_propagate": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GraphCsr), _f32p, _f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t]),

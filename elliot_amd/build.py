@@ -17,6 +17,8 @@ FLAGS = [
     "-ffp-contract=off",     # every fma in the kernels is explicit (top-k bit-exactness)
     "-Wno-unused-result",
 ]
+# per-source additions: el_fm.hip keeps its row sums on scalar fp32 instructions (no packed-fp32 forms)
+EXTRA_FLAGS = {"el_fm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def sources():
@@ -30,6 +32,7 @@ def _stamp():
         with open(f, "rb") as fh:
             h.update(fh.read())
     h.update(" ".join(FLAGS).encode())
+    h.update(repr(sorted(EXTRA_FLAGS.items())).encode())
     return h.hexdigest()
 
 
@@ -45,7 +48,7 @@ def build(force=False, verbose=True):
     for src in sources():
         obj = src[:-4] + ".o"
         objs.append(obj)
-        cmd = [hipcc] + [f for f in FLAGS if f != "-shared"] + ["-c", src, "-o", obj]
+        cmd = [hipcc] + [f for f in FLAGS if f != "-shared"] + EXTRA_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
         if verbose:
             print("[elliot_amd.build]", " ".join(cmd), flush=True)
         procs.append((src, subprocess.Popen(cmd)))

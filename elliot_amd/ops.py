@@ -2735,6 +2735,142 @@ class VbprDeviceState:
         return self._P, self._Q, self._bq
 
 
+def fm_attribute_index(item_features, n_features):
+    """The attribute matrix of FM as the two index structures of el_fm_state, built once per data set on the host:
+    item_features[i] = the feature ids of item i (a set: repeats count once).  Returns (a_indptr int64 [I + 1], a_indices int32,
+    t_indptr int64 [nF + 1], t_indices int32): item -> features with ids ascending in a row, and its exact transpose, feature ->
+    items with ids ascending in a list."""
+    rows = [np.unique(np.asarray(list(f), dtype=np.int64)) for f in item_features]
+    a_indptr = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum([len(r) for r in rows], out=a_indptr[1:])
+    a_indices = (np.concatenate(rows) if rows and a_indptr[-1] else np.zeros(0, np.int64))
+    if a_indices.size and (a_indices.min() < 0 or a_indices.max() >= n_features):
+        raise ValueError("fm_attribute_index: feature id out of range")
+    item_of = np.repeat(np.arange(len(rows), dtype=np.int64), np.diff(a_indptr))
+    order = np.argsort(a_indices, kind="stable")                 # (stable: items stay ascending inside a feature)
+    t_indptr = np.zeros(int(n_features) + 1, np.int64)
+    np.cumsum(np.bincount(a_indices, minlength=int(n_features)), out=t_indptr[1:])
+    return a_indptr, a_indices.astype(np.int32), t_indptr, item_of[order].astype(np.int32)
+
+
+class FmDeviceState:
+    """FactorizationMachineModel's variables (latent_factor_models/FM/factorization_machine_model.py): ONE table E [N, F] and one
+    bias vector w [N] over N = U + I + nF rows in the reference's field order, the global bias g0, their dense accumulators and
+    Adam slots, the attribute matrix as CSR and CSC, and the step's slot map (include/elliot_hip.h, el_fm_state).  item_features:
+    per item the feature ids in [0, nF) -- None or nF = 0 is the model without attributes (g0 + w_u + w_i + e_u . e_i)."""
+
+    def __init__(self, ctx, U, I, E, w=None, g0=0.0, item_features=None, n_features=0):
+        self.ctx, dev = ctx, ctx.device
+        self.U, self.I, self.nF = int(U), int(I), int(n_features) if item_features is not None else 0
+        self.N = self.U + self.I + self.nF
+        self.E = _own(E, dev)
+        if self.E.ndim != 2 or self.E.shape[0] != self.N:
+            raise ValueError(f"FmDeviceState: E must be [{self.N}, F]")
+        self.F = int(self.E.shape[1])
+        self.w = torch.zeros(self.N, dtype=torch.float32, device=dev) if w is None else _own(w, dev).reshape(-1).contiguous()
+        self.g0 = torch.full((1,), float(g0), dtype=torch.float32, device=dev)
+        z = torch.zeros_like
+        for n in ("E", "w", "g0"):
+            for pre in ("g", "m", "v"):
+                setattr(self, pre + n, z(getattr(self, n)))
+        # (the global bias: gradient, variable and slots are doubles; g0 is the float image the kernels read)
+        self.g0d = self.g0.double()
+        self.gg0, self.mg0, self.vg0 = (torch.zeros(1, dtype=torch.float64, device=dev) for _ in range(3))
+        self.index = fm_attribute_index(item_features if self.nF else [()] * self.I, self.nF)
+        if len(self.index[0]) != self.I + 1:
+            raise ValueError("FmDeviceState: item_features must list every item")
+        self.a_indptr, self.a_indices, self.t_indptr, self.t_indices = (
+            torch.from_numpy(a if a.size else np.zeros(1, a.dtype)).to(dev) for a in self.index)
+        self.slot = torch.full((self.I,), -1, dtype=torch.int32, device=dev)
+        self.loss = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.step = 0
+        p = lambda t: t.data_ptr()
+        self._c = _lib.FmState(U=self.U, I=self.I, nF=self.nF, F=self.F,
+                               **{pre + n: p(getattr(self, pre + n)) for pre in ("", "g", "m", "v") for n in ("E", "w", "g0")},
+                               g0d=p(self.g0d), a_indptr=p(self.a_indptr), a_indices=p(self.a_indices), t_indptr=p(self.t_indptr),
+                               t_indices=p(self.t_indices), t_longest=int(np.diff(self.index[2]).max()) if self.nF else 0,
+                               slot=p(self.slot))
+        self._Q = self._bq = None
+
+    def _step_ws(self, B):
+        need = int(self.ctx.lib.el_fm_ws_bytes(self.ctx.handle, int(B), self.U, self.I, self.F))
+        return _ptr(workspace(self, "_ws", need, self.ctx.device)), need
+
+    def grads(self, u, i, y):
+        """Loss and tape.gradient of train_step (:62-69) into the accumulators; apply() consumes them."""
+        ws, need = self._step_ws(u.numel())
+        check(self.ctx.lib.el_fm_grads(self.ctx.handle, self.ctx.stream(), C.byref(self._c), _ptr(u, torch.int32, "u"),
+                                       _ptr(i, torch.int32, "i"), _ptr(y, torch.float32, "y"), int(u.numel()),
+                                       _ptr(self.loss, torch.float64), ws, need), "el_fm_grads")
+
+    def apply(self, lr):
+        self.step += 1
+        check(self.ctx.lib.el_fm_apply(self.ctx.handle, self.ctx.stream(), C.byref(self._c), int(self.step),
+                                       float(adam_lr_t(lr, self.step))), "el_fm_apply")
+
+    def train_step(self, u, i, y, lr):
+        self.step += 1
+        ws, need = self._step_ws(u.numel())
+        check(self.ctx.lib.el_fm_train_step(self.ctx.handle, self.ctx.stream(), C.byref(self._c), _ptr(u, torch.int32, "u"),
+                                            _ptr(i, torch.int32, "i"), _ptr(y, torch.float32, "y"), int(u.numel()), int(self.step),
+                                            float(adam_lr_t(lr, self.step)), _ptr(self.loss, torch.float64), ws, need),
+              "el_fm_train_step")
+
+    def forward(self, u, i, out=None):
+        """y^ of an explicit pair list (the model's predict)."""
+        if out is None:
+            out = torch.empty(u.numel(), dtype=torch.float32, device=self.ctx.device)
+        check(self.ctx.lib.el_fm_forward(self.ctx.handle, self.ctx.stream(), C.byref(self._c), _ptr(u, torch.int32, "u"),
+                                         _ptr(i, torch.int32, "i"), int(u.numel()), _ptr(out, torch.float32)), "el_fm_forward")
+        return out
+
+    def image(self):
+        """(Q, bq) of the current weights: y^(u, i) = w[u] + bq[i] + E[u] . Q[i] (el_fm_item_image)."""
+        if self._Q is None:
+            self._Q = torch.empty((self.I, self.F), dtype=torch.float32, device=self.ctx.device)
+            self._bq = torch.empty(self.I, dtype=torch.float32, device=self.ctx.device)
+        check(self.ctx.lib.el_fm_item_image(self.ctx.handle, self.ctx.stream(), C.byref(self._c), _ptr(self._Q, torch.float32),
+                                            _ptr(self._bq, torch.float32)), "el_fm_item_image")
+        return self._Q, self._bq
+
+    def recommend(self, Q, bq, u_start, u_stop, k, excl=None, cand=None, items_unchanged=False):
+        """Top-k of users [u_start, u_stop) on an image: the fused kernel ranks by bq[i] + E[u] . Q[i]; the user's own bias is added
+        to the k values afterwards (it moves no rank)."""
+        idx, val = score_topk(self.ctx, self.E[:self.U], Q, bq, u_start, u_stop, k, excl=excl, cand=cand, items_unchanged=items_unchanged)
+        check(self.ctx.lib.el_pwmf_link_values(self.ctx.handle, self.ctx.stream(), _ptr(val, torch.float32), int(val.shape[0]),
+                                               int(val.stride(0)), int(k), _lib.EL_PW_MSE, _ptr(self.w, torch.float32), int(u_start)),
+              "el_pwmf_link_values")
+        return idx, val
+
+    def pop_loss(self):
+        v = float(self.loss.item())
+        self.loss.zero_()
+        return v
+
+
+def fm_labels(ctx, ratings, u, i, coin):
+    """Labels of pointwise_pos_neg_ratings_sampler from the device sampler's coin: the rating of (u, i) where coin > 0, else 0
+    (el_fm_labels).  ratings = (DeviceCSR with ascending columns, float32 values on the device)."""
+    csr, values = ratings
+    y = torch.empty(u.numel(), dtype=torch.float32, device=ctx.device)
+    check(ctx.lib.el_fm_labels(ctx.handle, ctx.stream(), *_csr_ptrs(csr), _ptr(values, torch.float32), _ptr(u, torch.int32, "u"),
+                               _ptr(i, torch.int32, "i"), _ptr(coin, torch.float32), int(u.numel()), _ptr(y, torch.float32)), "el_fm_labels")
+    return y
+
+
+def fm_ratings_csr(ctx, m):
+    """A scipy rating matrix as (DeviceCSR, values) for fm_labels: the column indices of a row are checked to be ascending and
+    sorted at upload when they are not."""
+    import scipy.sparse as sp
+    m = m.tocsr()
+    m = sp.csr_matrix((m.data, m.indices, m.indptr), shape=m.shape)      # (a fresh view: the order is looked at, not remembered)
+    if not m.has_sorted_indices:
+        m = m.copy()
+        m.sort_indices()
+    values = torch.from_numpy(np.ascontiguousarray(m.data if m.nnz else np.zeros(1), dtype=np.float32)).to(ctx.device)
+    return DeviceCSR(m.indptr, m.indices, m.shape[1], ctx.device), values
+
+
 # ------------------------------------------------------------------------------------------
 # graph propagation: LightGCN (graph_based/lightgcn) -- SURVEY 8f N3
 # ------------------------------------------------------------------------------------------

@@ -425,6 +425,67 @@ int el_vbpr_apply(el_ctx* ctx, void* stream, const el_vbpr_state* st, float lr, 
 size_t el_vbpr_image_ws_bytes(el_ctx* ctx, int64_t I, int32_t Fd, int64_t D);
 int el_vbpr_item_image(el_ctx* ctx, void* stream, const el_vbpr_state* st, float* Q, float* bq, float* P, void* ws, size_t ws_bytes);
 
+/* ---- FM: factorization machine over users, items and item attributes (latent_factor_models/FM; el_fm.hip) -------
+ * One table E [N, F] and one bias vector w [N], N = U + I + nF, rows in the reference's field order (user u = row u, item i = row
+ * U + i, feature f = row U + I + f), one global scalar g0.  With X = {u, U + i} + A(i), A(i) the feature rows of item i (a set):
+ *   y^(u, i) = g0 + sum_X w_x + 1/2 (|sum_X e_x|^2 - sum_X |e_x|^2)         (factorization_machine_model.py:130, :178-180)
+ * Entry points only: EL_ABI_VERSION does not change.  The attribute matrix is given twice, item-major (CSR, feature ids ascending in
+ * a row) and feature-major (CSC, item ids ascending in a list); nF = 0 with both NULL is the model without attributes.            */
+typedef struct el_fm_state {
+    int64_t U, I, nF;
+    int32_t F;                                          /* 1 .. 512 */
+    float* E;   float* w;   float* g0;                  /* [N, F], [N], [1] */
+    float* gE;  float* gw;  double* gg0;                /* accumulators ([N, F], [N], double [1]): zero on entry of el_fm_grads, zero after el_fm_apply */
+    float* mE;  float* vE;  float* mw;  float* vw;      /* Adam slots of E and w */
+    double* g0d;  double* mg0;  double* vg0;            /* [1] each: the global bias as the optimiser keeps it, and its slots; g0 is the float
+                                                           image of g0d that the kernels read, rewritten by every apply (start: g0d = g0) */
+    const int64_t* a_indptr;  const int32_t* a_indices; /* item -> features: [I + 1], [nnz] (feature ids 0 .. nF - 1) */
+    const int64_t* t_indptr;  const int32_t* t_indices; /* feature -> items: [nF + 1], [nnz] */
+    int64_t t_longest;                                  /* the longest feature -> items list (a shorter value leaves long lists unsummed) */
+    int32_t* slot;                                      /* [I] scratch map item -> row of the step's image; -1 everywhere between calls */
+} el_fm_state;
+
+/* Scratch of el_fm_grads / el_fm_train_step for a batch of B samples (0 = bad arguments). */
+size_t el_fm_ws_bytes(el_ctx* ctx, int64_t B, int64_t U, int64_t I, int32_t F);
+
+/* Replaces: the loss and tape.gradient of FactorizationMachineModel.train_step (:62-72) on B samples (u, i, y):
+ *   L = 1/B sum (y_b - y^_b)^2;   with c_b = 2 (y^_b - y_b) / B and z_b = sum_X e_x:
+ *   gE[x] = sum_{b: x in X_b} c_b (z_b - e_x),   gw[x] = sum_{b: x in X_b} c_b,   gg0 = sum c_b
+ * (the l2 regulariser handed to the embedding never reaches the tape loss: train_step does not add self.losses -- the finding of
+ * MF / PMF / FunkSVD above).  The sums factor through the batch's DISTINCT items: per item one row s_i = e_{U+i} + sum_A e_f, per
+ * sample one dot product, two sorted-segment passes (users, items), and one pass over the feature-major lists that adds the item
+ * sums of the batch's items in list order -- nnz(attributes) slot reads per step whatever B.  No floating-point atomics, a fixed
+ * order in every sum: the same input gives the same bytes, the loss included (per-workgroup double partials added in index order).
+ * L is ADDED to loss_out (device double[1]); rows without an active sample are not written.  u in [0, U), i in [0, I): ids are not
+ * checked (as el_pwmf_*).  Any B >= 1, F in 1 .. 512, nF >= 0, empty A(i) allowed.  ws: el_fm_ws_bytes(...).                   */
+int el_fm_grads(el_ctx* ctx, void* stream, const el_fm_state* st, const int32_t* u, const int32_t* i, const float* y, int64_t B,
+                double* loss_out, void* ws, size_t ws_bytes);
+
+/* optimizer.apply_gradients (:70): the variables are read inside tf.map_fn bodies, so their gradients reach Adam as DENSE tensors:
+ * TensorFlow's fused ApplyAdam (m += (g - m)(1 - b1); the step of the Mult-VAE weights and of VBPR's E) on E, w and g0 -- every
+ * row moves every step.  g0 is one scalar that every sample moves: its gradient stays the double it was reduced in and its step (same
+ * formula, same float constants) runs in double on g0d, mg0, vg0; g0 = (float)g0d.  lr_t = lr sqrt(1 - b2^step) / (1 - b1^step).  The accumulators come back zero.  (Read from TF 2.3's
+ * while_v2 gradient, not run: parity unpinned vs TF.)                                                                         */
+int el_fm_apply(el_ctx* ctx, void* stream, const el_fm_state* st, int32_t step, float lr_t);
+
+/* el_fm_grads + el_fm_apply. */
+int el_fm_train_step(el_ctx* ctx, void* stream, const el_fm_state* st, const int32_t* u, const int32_t* i, const float* y, int64_t B,
+                     int32_t step, float lr_t, double* loss_out, void* ws, size_t ws_bytes);
+
+/* Replaces: predict / call (:56-59, :75-83) on an explicit pair list: out[p] = y^(u[p], i[p]); the item's sums are formed on the
+ * fly, no scratch.                                                                                                            */
+int el_fm_forward(el_ctx* ctx, void* stream, const el_fm_state* st, const int32_t* u, const int32_t* i, int64_t n, float* out);
+
+/* Replaces: get_user_full_array + get_recs (factorization_machine.py:143-164) for every item at once:
+ *   Q [I, F] = s_i,  bq [I] = g0 + l_i + 1/2 (|s_i|^2 - q_i)   so that   y^(u, i) = w[u] + bq[i] + E[u] . Q[i]
+ * and scoring is el_score_topk on (E[:U], Q, bq) followed by el_pwmf_link_values(EL_PW_MSE, Bu = w[:U]).  Needs no scratch.     */
+int el_fm_item_image(el_ctx* ctx, void* stream, const el_fm_state* st, float* Q, float* bq);
+
+/* Replaces: the labels of pointwise_pos_neg_ratings_sampler: y[b] = the rating of (u[b], i[b]) in the CSR (column indices ascending
+ * in a row; binary search) where coin[b] > 0, else 0.  y may be coin.                                                          */
+int el_fm_labels(el_ctx* ctx, void* stream, const int64_t* indptr, const int32_t* indices, const float* values, const int32_t* u,
+                 const int32_t* i, const float* coin, int64_t n, float* y);
+
 /* ---- BPR-MF, NumPy semantics (BPRMF; K5) ------------------------------------- */
 
 typedef struct el_bprsgd_state {
