@@ -69,6 +69,20 @@ class FmState(C.Structure):
                 ("slot", _i32p)]
 
 
+def _quad(n):
+    return [(pre + n, _f32p) for pre in ("", "g", "m", "v")]
+
+
+class FismState(C.Structure):
+    _fields_ = [("U", C.c_int64), ("I", C.c_int64), ("nnz", C.c_int64), ("F", C.c_int32), ("alpha", C.c_float), ("beta", C.c_float),
+                ("lambda_", C.c_float), ("gamma", C.c_float), ("loss_kind", C.c_int32), ("pad_len", C.c_int64),
+                *_quad("Gi"), *_quad("Gj"), *_quad("Bu"), *_quad("Bi"), ("coef", _f32p), ("h_indptr", _i64p), ("h_indices", _i32p),
+                ("t_indptr", _i64p), ("t_indices", _i32p), ("slot", _i32p)]
+
+
+EL_FISM_LOSS_REFERENCE, EL_FISM_LOSS_BCE = 0, 1
+
+
 class BprsgdState(C.Structure):
     _fields_ = [
         ("P", _f64p), ("Q", _f64p), ("b", _f64p),
@@ -228,6 +242,14 @@ PROTOTYPES = {
     "el_fm_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FmState), _i32p, _i32p, C.c_int64, _f32p]),
     "el_fm_item_image": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FmState), _f32p, _f32p]),
     "el_fm_labels": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, _f32p, _i32p, _i32p, _f32p, C.c_int64, _f32p]),
+    "el_fism_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
+    "el_fism_image_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32]),
+    "el_fism_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FismState), _i32p, _i32p, _f32p, C.c_int64, _f64p, C.c_void_p, C.c_size_t]),
+    "el_fism_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FismState), C.c_int32, C.c_float]),
+    "el_fism_train_step": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FismState), _i32p, _i32p, _f32p, C.c_int64, C.c_int32, C.c_float, _f64p,
+                                     C.c_void_p, C.c_size_t]),
+    "el_fism_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FismState), _i32p, _i32p, C.c_int64, _f32p]),
+    "el_fism_user_image": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FismState), _f32p, C.c_void_p, C.c_size_t]),
     "el_spmm_csr_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GraphCsr), _f32p, _f32p, C.c_int32, _f32p, _f32p]),
     "el_lightgcn_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "el_lightgcn_propagate": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GraphCsr), _f32p, _f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t]),
@@ -305,6 +327,8 @@ PROTOTYPES = {
                                            C.c_uint64, C.c_int64, _i32p, _i32p, _f32p]),
     "el_pointwise_sample": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64,
                                       C.c_int64, _i32p, _i32p, _f32p]),
+    "el_pointwise_sample_ratio": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, _i32p, C.c_int64, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64,
+                                            C.c_int64, _i32p, _i32p, _f32p]),
     "el_nmf_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(NmfState), _i32p, _i32p, C.c_int64, _f32p]),
     "el_nmf_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(NmfState), _i32p, _i32p, _f32p, C.c_int64, C.c_int64, _f64p]),
     "el_nmf_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(NmfState), C.c_int32, C.c_float]),

@@ -30,6 +30,7 @@ struct el_options {
     double screen_stride = 0;        // screened top-k: catalogue stride of the first pass (0: by catalogue size)
     double screen_ka = 0;            // ... and the list length it keeps
     double screen_prof = 0;          // ... per-pass clock counters (profiling builds of the passes)
+    double fism_piece = 256;         // FISM: list positions per lane group of the cut sum (a power of two, 8 .. 4096)
 };
 
 struct el_ctx {

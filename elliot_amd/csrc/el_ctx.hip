@@ -27,7 +27,7 @@ static const el_opt_entry g_el_opts[] = {
     {"gemm_split", &el_options::gemm_split}, {"gemm_xcd", &el_options::gemm_xcd}, {"nmf_side", &el_options::nmf_side}, {"nmf_head4", &el_options::nmf_head4},
     {"vae_side", &el_options::vae_side}, {"nmf_screen_maxfrac", &el_options::nmf_screen_maxfrac},
     {"screen_stride", &el_options::screen_stride}, {"screen_ka", &el_options::screen_ka},
-    {"screen_prof", &el_options::screen_prof},
+    {"screen_prof", &el_options::screen_prof}, {"fism_piece", &el_options::fism_piece},
 };
 
 // EL_<NAME> in the environment gives an option its initial value (the one place the library reads the environment)

@@ -58,11 +58,12 @@ struct PwPhilox {
 };
 
 // u ~ U[0,U); coin; positive: i ~ U(pos(u)), label 1; negative: i ~ U[0,I) \ pos(u), label 0
-// (pointwise_pos_neg_sampler.py:33-46)
-template <bool META>
+// (pointwise_pos_neg_sampler.py:33-46).  RATIO: the coin is a uniform draw in [0, neg_ratio], positive iff 0
+// (pointwise_pos_neg_ratio_ratings_sampler.py: [0] * neg_ratio + [1])
+template <bool META, bool RATIO = false>
 __global__ __launch_bounds__(256) void k_pw_sample(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
                                                    int64_t U, int64_t I, u64 seed, u64 first, int64_t n, int32_t* out_u,
-                                                   int32_t* out_i, float* out_y, const SamplerRec* __restrict__ meta) {
+                                                   int32_t* out_i, float* out_y, const SamplerRec* __restrict__ meta, u32 neg_ratio = 1u) {
     int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
     PwPhilox ps;
@@ -80,7 +81,7 @@ __global__ __launch_bounds__(256) void k_pw_sample(const int64_t* __restrict__ i
         }
         int64_t lui = r1 - r0;
         if (lui <= 0 || lui >= I) continue;
-        u32 coin = ps.next() >> 31;                       // random.getrandbits(1)
+        u32 coin = RATIO ? (ps.bounded(neg_ratio + 1u) == 0u ? 1u : 0u) : ps.next() >> 31;     // random.getrandbits(1)
         int32_t it = -1;
         if (coin) {
             it = indices[r0 + ps.bounded((u32)lui)];
@@ -122,6 +123,20 @@ extern "C" int el_pointwise_sample_meta(el_ctx* ctx, void* stream, const int64_t
     if (n <= 0) return 0;
     EL_LAUNCH("k_pw_sample", k_pw_sample<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pos_indptr,
               pos_indices, U, I, (u64)seed, (u64)first_sample, n, out_u, out_i, out_label, (const SamplerRec*)meta);
+    EL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int el_pointwise_sample_ratio(el_ctx* ctx, void* stream, const int64_t* pos_indptr, const int32_t* pos_indices, int64_t U,
+                                         int64_t I, int32_t neg_ratio, uint64_t seed, uint64_t first_sample, int64_t n, int32_t* out_u,
+                                         int32_t* out_i, float* out_label) {
+    if (int rc = el_bind(ctx)) return rc;
+    EL_REQUIRE(pos_indptr && pos_indices && out_u && out_i && out_label, "el_pointwise_sample_ratio: null pointer");
+    EL_REQUIRE(U >= 1 && U < 0xffffffffLL && I >= 2 && I < 0x7fffffffLL, "el_pointwise_sample_ratio: U/I out of range");
+    EL_REQUIRE(neg_ratio >= 1, "el_pointwise_sample_ratio: neg_ratio must be an integer >= 1");
+    if (n <= 0) return 0;
+    EL_LAUNCH("k_pw_sample_ratio", (k_pw_sample<false, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pos_indptr,
+              pos_indices, U, I, (u64)seed, (u64)first_sample, n, out_u, out_i, out_label, (const SamplerRec*)nullptr, (u32)neg_ratio);
     EL_CHECK_LAUNCH();
     return 0;
 }

@@ -56,7 +56,12 @@ def replay_stream(indexed_ratings, events, state=None):
 
 
 class Sampler(_BprSampler):
-    def __init__(self, indexed_ratings, ctx=None, seed=42, n_items=None, replay=False):
+    def __init__(self, indexed_ratings, ctx=None, seed=42, n_items=None, replay=False, neg_ratio=None):
+        """neg_ratio (an integer >= 1): the ratio form of pointwise_pos_neg_ratio_ratings_sampler -- a sample is positive with
+        probability 1 / (neg_ratio + 1) instead of 1 / 2 (philox stream only)."""
+        if neg_ratio is not None and (replay or int(neg_ratio) != neg_ratio or neg_ratio < 1):
+            raise ValueError("neg_ratio must be an integer >= 1 and goes with the philox stream")
+        self._neg_ratio = None if neg_ratio is None else int(neg_ratio)
         if replay and sp.issparse(indexed_ratings):
             raise ValueError("replay=True needs the reference's i_train_dict (its set order defines the stream)")
         super().__init__(indexed_ratings, ctx=ctx, seed=seed, n_items=n_items, replay=False)
@@ -77,6 +82,9 @@ class Sampler(_BprSampler):
                 yield (torch.from_numpy(u.astype(np.int32)).to(d), torch.from_numpy(i.astype(np.int32)).to(d),
                        torch.from_numpy(b.astype(np.float32)).to(d))
                 continue
-            u, i, y = ops.pointwise_sample(self.ctx, self.pos, n, seed=self.seed, first_sample=self._drawn)
+            if self._neg_ratio is not None:
+                u, i, y = ops.pointwise_sample_ratio(self.ctx, self.pos, n, self._neg_ratio, seed=self.seed, first_sample=self._drawn)
+            else:
+                u, i, y = ops.pointwise_sample(self.ctx, self.pos, n, seed=self.seed, first_sample=self._drawn)
             self._drawn += n
             yield u, i, y

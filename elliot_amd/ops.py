@@ -2871,6 +2871,131 @@ def fm_ratings_csr(ctx, m):
     return DeviceCSR(m.indptr, m.indices, m.shape[1], ctx.device), values
 
 
+def fism_history_index(h_indptr, h_indices, n_items):
+    """The train matrix as the two index structures of el_fism_state, built once per data set on the host: the histories as given
+    (user -> items, stored order kept: it is the summation order) and their exact transpose, item -> users with ids ascending in a
+    list.  Returns (h_indptr int64 [U + 1], h_indices int32, t_indptr int64 [I + 1], t_indices int32)."""
+    h_indptr, h_indices = np.asarray(h_indptr, np.int64), np.asarray(h_indices, np.int64)
+    if h_indices.size and (h_indices.min() < 0 or h_indices.max() >= n_items):
+        raise ValueError("fism_history_index: item id out of range")
+    user_of = np.repeat(np.arange(len(h_indptr) - 1, dtype=np.int64), np.diff(h_indptr))
+    order = np.argsort(h_indices, kind="stable")                 # (stable: users stay ascending inside an item)
+    t_indptr = np.zeros(int(n_items) + 1, np.int64)
+    np.cumsum(np.bincount(h_indices, minlength=int(n_items)), out=t_indptr[1:])
+    return h_indptr, h_indices.astype(np.int32), t_indptr, user_of[order].astype(np.int32)
+
+
+FISM_LOSSES = {"reference": _lib.EL_FISM_LOSS_REFERENCE, "bce": _lib.EL_FISM_LOSS_BCE}
+
+
+class FismDeviceState:
+    """FISM_model's variables (latent_factor_models/FISM/FISM_model.py): Gi, Gj [I, F], Bu [U], Bi [I] with their dense accumulators
+    and Adam slots, coef = n_u^-alpha (float32, computed here once; 0 for a user without history), the train matrix user-major and
+    item-major, and the step's slot map (include/elliot_hip.h, el_fism_state).  history = (indptr, indices) of the users' train items
+    in the order they are summed.  padding "reference": pad_len = the longest history (the reference's unmasked padded slots, in
+    the regulariser and in scoring); "none": pad_len = 0.  loss "reference" | "bce"."""
+
+    NAMES = ("Gi", "Gj", "Bu", "Bi")
+
+    def __init__(self, ctx, Gi, Gj, Bu, Bi, history, alpha=0.5, beta=0.001, lambda_=0.001, gamma=0.001, padding="reference",
+                 loss="reference"):
+        self.ctx, dev = ctx, ctx.device
+        self.Gi, self.Gj = _own(Gi, dev), _own(Gj, dev)
+        self.Bu, self.Bi = _own(Bu, dev).reshape(-1).contiguous(), _own(Bi, dev).reshape(-1).contiguous()
+        self.I, self.F = (int(x) for x in self.Gi.shape)
+        self.U = int(self.Bu.numel())
+        if tuple(self.Gj.shape) != (self.I, self.F) or self.Bi.numel() != self.I or len(history[0]) != self.U + 1:
+            raise ValueError("FismDeviceState: Gi, Gj [I, F], Bi [I], Bu [U] and a history of U users")
+        self.index = fism_history_index(history[0], history[1], self.I)
+        lens = np.diff(self.index[0])
+        self.nnz, self.longest = int(self.index[0][-1]), int(lens.max()) if lens.size else 0
+        if padding not in ("reference", "none") or loss not in FISM_LOSSES:
+            raise ValueError("FismDeviceState: padding is 'reference' or 'none', loss is 'reference' or 'bce'")
+        self.pad_len = self.longest if padding == "reference" else 0
+        with np.errstate(divide="ignore"):
+            coef = np.where(lens > 0, np.power(lens.astype(np.float32), np.float32(-float(alpha))), np.float32(0)).astype(np.float32)
+        self.coef = torch.from_numpy(coef).to(dev)
+        self.h_indptr, self.h_indices, self.t_indptr, self.t_indices = (
+            torch.from_numpy(a if a.size else np.zeros(1, a.dtype)).to(dev) for a in self.index)
+        for n in self.NAMES:
+            for pre in ("g", "m", "v"):
+                setattr(self, pre + n, torch.zeros_like(getattr(self, n)))
+        self.slot = torch.full((self.U,), -1, dtype=torch.int32, device=dev)
+        self.loss = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.step, self._margin = 0, _PW_MARGIN
+        p = lambda t: t.data_ptr()
+        self._c = _lib.FismState(U=self.U, I=self.I, nnz=self.nnz, F=self.F, alpha=float(alpha), beta=float(beta), lambda_=float(lambda_),
+                                 gamma=float(gamma), loss_kind=FISM_LOSSES[loss], pad_len=self.pad_len,
+                                 **{pre + n: p(getattr(self, pre + n)) for pre in ("", "g", "m", "v") for n in self.NAMES},
+                                 coef=p(self.coef), h_indptr=p(self.h_indptr), h_indices=p(self.h_indices), t_indptr=p(self.t_indptr),
+                                 t_indices=p(self.t_indices), slot=p(self.slot))
+        self._P = None
+
+    def _step_ws(self, B):
+        need = int(self.ctx.lib.el_fism_ws_bytes(self.ctx.handle, int(B), self.U, self.I, self.nnz, self.F))
+        return _ptr(workspace(self, "_ws", need, self.ctx.device)), need
+
+    def _batch(self, u, i, y):
+        return _ptr(u, torch.int32, "u"), _ptr(i, torch.int32, "i"), _ptr(y, torch.float32, "y"), int(u.numel())
+
+    def grads(self, u, i, y):
+        """Loss and tape.gradient of train_step (:78-89) into the accumulators; apply() consumes them."""
+        ws, need = self._step_ws(u.numel())
+        check(self.ctx.lib.el_fism_grads(self.ctx.handle, self.ctx.stream(), C.byref(self._c), *self._batch(u, i, y),
+                                         _ptr(self.loss, torch.float64), ws, need), "el_fism_grads")
+
+    def apply(self, lr):
+        self.step += 1
+        check(self.ctx.lib.el_fism_apply(self.ctx.handle, self.ctx.stream(), C.byref(self._c), int(self.step),
+                                         float(adam_lr_t(lr, self.step))), "el_fism_apply")
+
+    def train_step(self, u, i, y, lr):
+        self.step += 1
+        self._margin = _PW_MARGIN
+        ws, need = self._step_ws(u.numel())
+        check(self.ctx.lib.el_fism_train_step(self.ctx.handle, self.ctx.stream(), C.byref(self._c), *self._batch(u, i, y), int(self.step),
+                                              float(adam_lr_t(lr, self.step)), _ptr(self.loss, torch.float64), ws, need),
+              "el_fism_train_step")
+
+    def forward(self, u, i, out=None):
+        """The model's score of an explicit pair list, as batch_predict computes it (el_fism_forward)."""
+        if out is None:
+            out = torch.empty(u.numel(), dtype=torch.float32, device=self.ctx.device)
+        check(self.ctx.lib.el_fism_forward(self.ctx.handle, self.ctx.stream(), C.byref(self._c), _ptr(u, torch.int32, "u"),
+                                           _ptr(i, torch.int32, "i"), int(u.numel()), _ptr(out, torch.float32)), "el_fism_forward")
+        return out
+
+    def image(self):
+        """P [U, F] of the current weights: x(u, i) = P[u] . Gj[i] + Bu[u] + Bi[i] (el_fism_user_image)."""
+        if self._P is None:
+            self._P = torch.empty((self.U, self.F), dtype=torch.float32, device=self.ctx.device)
+        need = int(self.ctx.lib.el_fism_image_ws_bytes(self.ctx.handle, self.U, self.nnz, self.F))
+        ws = _ptr(workspace(self, "_image_ws", need, self.ctx.device))
+        check(self.ctx.lib.el_fism_user_image(self.ctx.handle, self.ctx.stream(), C.byref(self._c), _ptr(self._P, torch.float32), ws, need),
+              "el_fism_user_image")
+        return self._P
+
+    def _link(self, vals, k, u_start):
+        check(self.ctx.lib.el_pwmf_link_values(self.ctx.handle, self.ctx.stream(), _ptr(vals, torch.float32), int(vals.shape[0]),
+                                               int(vals.stride(0)), int(k), _lib.EL_PW_MSE_SIGMOID, _ptr(self.Bu, torch.float32),
+                                               int(u_start)), "el_pwmf_link_values")
+
+    def recommend(self, P, u_start, u_stop, k, excl=None, cand=None):
+        """Top-k of users [u_start, u_stop) on an image: the fused kernel ranks by Bi[i] + P[u] . Gj[i]; the list is linked through
+        sigma(. + Bu[u]) and re-ranked as the point-wise models' lists are (_linked_topk)."""
+        def dense():
+            preds = gemm(self.ctx, P[u_start:u_stop], self.Gj, transB=True, bias=self.Bi)
+            self._link(preds, self.I, u_start)
+            return dense_topk(self.ctx, preds, u_start, u_stop, k, excl=excl, cand=cand)
+        return _linked_topk(self, k, lambda kk: score_topk(self.ctx, P, self.Gj, self.Bi, u_start, u_stop, kk, excl=excl, cand=cand),
+                            lambda val, kk: self._link(val, kk, u_start), _PW_MAX_LIST, dense)
+
+    def pop_loss(self):
+        v = float(self.loss.item())
+        self.loss.zero_()
+        return v
+
+
 # ------------------------------------------------------------------------------------------
 # graph propagation: LightGCN (graph_based/lightgcn) -- SURVEY 8f N3
 # ------------------------------------------------------------------------------------------
@@ -3428,6 +3553,18 @@ def pointwise_sample(ctx, pos, n, seed, first_sample=0, use_meta=True, out=None)
                                            C.c_void_p(meta.data_ptr()) if meta is not None else None, int(pos.n_rows),
                                            int(pos.n_cols), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_sample), int(n), _ptr(u),
                                            _ptr(i), _ptr(y)), "el_pointwise_sample_meta")
+    return u, i, y
+
+
+def pointwise_sample_ratio(ctx, pos, n, neg_ratio, seed, first_sample=0):
+    """pointwise_pos_neg_ratio_ratings_sampler's draw on the device: a sample is positive with probability 1 / (neg_ratio + 1)
+    (el_pointwise_sample_ratio).  Returns (u int32[n], i int32[n], coin float32[n]: 1 positive, 0 negative)."""
+    u = torch.empty(n, dtype=torch.int32, device=ctx.device)
+    i = torch.empty(n, dtype=torch.int32, device=ctx.device)
+    y = torch.empty(n, dtype=torch.float32, device=ctx.device)
+    check(ctx.lib.el_pointwise_sample_ratio(ctx.handle, ctx.stream(), *_csr_ptrs(pos), int(pos.n_rows), int(pos.n_cols), int(neg_ratio),
+                                            int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_sample), int(n), _ptr(u), _ptr(i), _ptr(y)),
+          "el_pointwise_sample_ratio")
     return u, i, y
 
 

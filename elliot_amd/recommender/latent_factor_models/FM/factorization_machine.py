@@ -14,23 +14,10 @@ The sampler is the device philox sampler of the point-wise plugins (its coin is 
 one replayed for MF.  The training loop is RecMixin.train(); lists come from the item image and the fused top-k instead of one
 [I, U + I + nF] block per user (:143-164).
 """
-from .... import ops
 from ...base_recommender_model import BaseRecommenderModel, init_charger, param
 from ...recommender_utils_mixin import RecMixin
-from ..pointwise_plugin import PointwisePluginMixin
+from ..pointwise_plugin import PointwisePluginMixin, RatingLabels as _RatingLabels
 from .factorization_machine_model import FactorizationMachineModel
-
-
-class _RatingLabels:
-    """The point-wise sampler with the FM sampler's labels: (u, i, coin) -> (u, i, rating of a positive | 0)."""
-
-    def __init__(self, sampler, ctx, ratings):
-        self._sampler, self._ctx = sampler, ctx
-        self._ratings = ops.fm_ratings_csr(ctx, ratings)
-
-    def step(self, events, batch_size):
-        for u, i, coin in self._sampler.step(events, batch_size):
-            yield u, i, ops.fm_labels(self._ctx, self._ratings, u, i, coin)
 
 
 class FM(PointwisePluginMixin, RecMixin, BaseRecommenderModel):

@@ -486,6 +486,71 @@ int el_fm_item_image(el_ctx* ctx, void* stream, const el_fm_state* st, float* Q,
 int el_fm_labels(el_ctx* ctx, void* stream, const int64_t* indptr, const int32_t* indices, const float* values, const int32_t* u,
                  const int32_t* i, const float* coin, int64_t n, float* y);
 
+/* ---- FISM: factored item similarity (latent_factor_models/FISM; el_fism.hip) -------------------------------------
+ * No user table: with H(u) the user's train items in CSR order, n_u = |H(u)| and coef[u] = n_u^-alpha (computed by the caller in
+ * float32; 0 for a user without history),
+ *   p_u = sum_{k in H(u)} Gi[k],   x(u, i) = coef[u] (p_u . Gj[i]) + Bu[u] + Bi[i],   out = 1 / (1 + exp(-x))      (FISM_model.py:61-76)
+ * The target item is not taken out of the history.  Entry points only: EL_ABI_VERSION does not change.  The train matrix is given
+ * twice: user-major (h_*: the histories, stored order = summation order) and item-major (t_*: per item its users, ids ascending).
+ * Ported as written: loss_kind REFERENCE is Keras BinaryCrossentropy called as (y_true = out, y_pred = label), in double;
+ * pad_len = L (the longest history) keeps the reference's unmasked padded slots (item id 0) in the regulariser and in scoring.      */
+enum {
+    EL_FISM_LOSS_REFERENCE = 0, /* mean_b -(out_b log(yh_b + 1e-7) + (1 - out_b) log(1 - yh_b + 1e-7)), yh = clip(label, 1e-7, 1 - 1e-7) */
+    EL_FISM_LOSS_BCE = 1        /* the cross-entropy that was meant: y_true = (label > 0), y_pred = out, same clipping and epsilon       */
+};
+
+typedef struct el_fism_state {
+    int64_t U, I, nnz;                                  /* nnz = h_indptr[U] = t_indptr[I] */
+    int32_t F;                                          /* 1 .. 512 */
+    float alpha;                                        /* informational: the kernels read coef */
+    float beta, lambda, gamma;                          /* regularisers of Gi / Gj, Bu, Bi */
+    int32_t loss_kind;                                  /* EL_FISM_LOSS_* */
+    int64_t pad_len;                                    /* L: the reference's padded history width; 0: no padded slots anywhere */
+    float* Gi;  float* gGi;  float* mGi;  float* vGi;   /* [I, F] history side: variable, accumulator (zero on entry of el_fism_grads, zero after el_fism_apply), Adam slots */
+    float* Gj;  float* gGj;  float* mGj;  float* vGj;   /* [I, F] target side */
+    float* Bu;  float* gBu;  float* mBu;  float* vBu;   /* [U] */
+    float* Bi;  float* gBi;  float* mBi;  float* vBi;   /* [I] */
+    const float* coef;                                  /* [U] */
+    const int64_t* h_indptr;  const int32_t* h_indices; /* user -> items: [U + 1], [nnz] */
+    const int64_t* t_indptr;  const int32_t* t_indices; /* item -> users: [I + 1], [nnz] */
+    int32_t* slot;                                      /* [U] scratch map user -> row of the step's image; -1 on entry and on exit */
+} el_fism_state;
+
+/* Scratch of el_fism_grads / el_fism_train_step for a batch of B samples, and of el_fism_user_image (0 = bad arguments).  Both
+ * depend on the context's option fism_piece (el_ctx_set_option: list positions per lane group, a power of two in 8 .. 4096,
+ * default 256).                                                                                                              */
+size_t el_fism_ws_bytes(el_ctx* ctx, int64_t B, int64_t U, int64_t I, int64_t nnz, int32_t F);
+size_t el_fism_image_ws_bytes(el_ctx* ctx, int64_t U, int64_t nnz, int32_t F);
+
+/* Replaces: the loss and tape.gradient of FISM_model.train_step (:78-92) on B samples (u, i, label).  With c_b = dL/dx_b (the loss
+ * gradient in double, cast to float before the sigmoid's derivative), per distinct user T_u = sum c_b Gj[i_b], cnt_u, R_u = coef_u T_u:
+ *   gBu[u] = sum c_b + lambda cnt_u Bu[u]     gBi[i] = sum c_b + gamma m_i Bi[i]     gGj[i] = sum c_b coef_u p_u + beta m_i Gj[i]
+ *   gGi[k] = sum_{u in batch, k in H(u)} R_u + beta Gi[k] sum cnt_u     (+ beta Gi[0] sum_b (pad_len - n_{u_b}) for k = 0)
+ * The regulariser is a SUM over the samples (a repeated user or item counts once per occurrence).  L is ADDED to loss_out (device
+ * double[1]).  gGi is written for every item (exactly 0 where no batch user holds it), the other accumulators for the rows the
+ * batch names.  p_u and the gGi sums are ordered sums of gathered rows over CSR lists cut into pieces of fism_piece positions; no
+ * floating-point atomics, a fixed order in every sum: the same input gives the same bytes.  The fan-out reads every nonzero's user
+ * id once per step whatever B.  u in [0, U) with n_u >= 1, i in [0, I): not checked.  Any B >= 1.  ws: el_fism_ws_bytes(...).   */
+int el_fism_grads(el_ctx* ctx, void* stream, const el_fism_state* st, const int32_t* u, const int32_t* i, const float* label, int64_t B,
+                  double* loss_out, void* ws, size_t ws_bytes);
+
+/* optimizer.apply_gradients (:90): every variable is read through embedding_lookup, so Adam sees IndexedSlices: Keras' sparse apply,
+ * every row's m and v decay and move every step (EL_PW_ADAM's kernel, one launch per variable).  The accumulators come back zero.
+ * (Read from TF 2.3, not run: parity unpinned vs TF.)                                                                         */
+int el_fism_apply(el_ctx* ctx, void* stream, const el_fism_state* st, int32_t step, float lr_t);
+
+/* el_fism_grads + el_fism_apply. */
+int el_fism_train_step(el_ctx* ctx, void* stream, const el_fism_state* st, const int32_t* u, const int32_t* i, const float* label,
+                       int64_t B, int32_t step, float lr_t, double* loss_out, void* ws, size_t ws_bytes);
+
+/* The model's score of explicit pairs as batch_predict (:119-144) computes it:
+ *   out[p] = sigma(coef_u ((p_u + (pad_len - n_u) Gi[0]) . Gj[i]) + Bu[u] + Bi[i]);  p_u is formed on the fly, no scratch.     */
+int el_fism_forward(el_ctx* ctx, void* stream, const el_fism_state* st, const int32_t* u, const int32_t* i, int64_t n, float* out);
+
+/* P [U, F] = coef_u (p_u + (pad_len - n_u) Gi[0]) for ALL users, so that scoring is el_score_topk on (P, Gj, Bi) followed by
+ * el_pwmf_link_values(EL_PW_MSE_SIGMOID, Bu) and the re-rank.  ws: el_fism_image_ws_bytes(...).                                */
+int el_fism_user_image(el_ctx* ctx, void* stream, const el_fism_state* st, float* P, void* ws, size_t ws_bytes);
+
 /* ---- BPR-MF, NumPy semantics (BPRMF; K5) ------------------------------------- */
 
 typedef struct el_bprsgd_state {
@@ -1226,6 +1291,13 @@ int el_pointwise_sample(el_ctx* ctx, void* stream, const int64_t* pos_indptr, co
 int el_pointwise_sample_meta(el_ctx* ctx, void* stream, const int64_t* pos_indptr, const int32_t* pos_indices, const void* meta,
                              int64_t U, int64_t I, uint64_t seed, uint64_t first_sample, int64_t n,
                              int32_t* out_u, int32_t* out_i, float* out_label);
+
+/* The ratio form (pointwise_pos_neg_ratio_ratings_sampler.py: a draw from [0] * neg_ratio + [1]): the same Philox stream with the
+ * fair coin replaced by a uniform draw in [0, neg_ratio], positive iff 0 -- a sample is positive with probability
+ * 1 / (neg_ratio + 1).  neg_ratio >= 1.  out_label is 1 / 0; el_fm_labels turns it into the rating.                            */
+int el_pointwise_sample_ratio(el_ctx* ctx, void* stream, const int64_t* pos_indptr, const int32_t* pos_indices, int64_t U, int64_t I,
+                              int32_t neg_ratio, uint64_t seed, uint64_t first_sample, int64_t n,
+                              int32_t* out_u, int32_t* out_i, float* out_label);
 
 /* Replaces: NeuralMatrixFactorizationModel.get_recs / GeneralizedMatrixFactorizationModel.get_recs on an
  * explicit pair list (neural_matrix_factorization_model.py:120-144): out_prob[b] = sigmoid(...) of (u[b], i[b]). */
