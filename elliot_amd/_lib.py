@@ -82,6 +82,15 @@ class FismState(C.Structure):
 
 EL_FISM_LOSS_REFERENCE, EL_FISM_LOSS_BCE = 0, 1
 
+NAIS_NAMES = ("Gi", "Gj", "Bu", "Bi", "W1", "b1", "W2", "b2", "W3", "b3")
+
+
+class NaisState(C.Structure):
+    _fields_ = [("U", C.c_int64), ("I", C.c_int64), ("nnz", C.c_int64), ("F", C.c_int32), ("Ws", C.c_int32), ("alpha", C.c_float),
+                ("beta_smooth", C.c_float), ("l_b", C.c_float), ("loss_kind", C.c_int32), ("pad_len", C.c_int64),
+                *[f for n in NAIS_NAMES for f in _quad(n)], ("coef", _f32p),
+                ("h_indptr", _i64p), ("h_indices", _i32p), ("t_indptr", _i64p), ("t_indices", _i32p), ("slot", _i32p)]
+
 
 class BprsgdState(C.Structure):
     _fields_ = [
@@ -250,6 +259,15 @@ PROTOTYPES = {
                                      C.c_void_p, C.c_size_t]),
     "el_fism_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FismState), _i32p, _i32p, C.c_int64, _f32p]),
     "el_fism_user_image": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FismState), _f32p, C.c_void_p, C.c_size_t]),
+    "el_nais_ws_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(NaisState), C.c_int64]),
+    "el_nais_scores_ws_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(NaisState)]),
+    "el_nais_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(NaisState), _i32p, _i32p, _f32p, C.c_int64, _f64p, C.c_void_p, C.c_size_t]),
+    "el_nais_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(NaisState), C.c_int32, C.c_float]),
+    "el_nais_train_step": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(NaisState), _i32p, _i32p, _f32p, C.c_int64, C.c_int32, C.c_float, _f64p,
+                                     C.c_void_p, C.c_size_t]),
+    "el_nais_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(NaisState), _i32p, _i32p, C.c_int64, _f32p, C.c_void_p, C.c_size_t]),
+    "el_nais_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(NaisState), C.c_int64, C.c_int64, _f32p, C.c_int64, C.c_void_p,
+                                 C.c_size_t]),
     "el_spmm_csr_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GraphCsr), _f32p, _f32p, C.c_int32, _f32p, _f32p]),
     "el_lightgcn_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "el_lightgcn_propagate": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GraphCsr), _f32p, _f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t]),

@@ -40,6 +40,8 @@ namespace {
 #define FI_STG 64            // list / segment positions whose indices a lane group stages in LDS at once
 #define FI_COMB_LONG 16      // a list of more pieces than this is combined by a workgroup
 
+#include "el_fism_keys.h"
+
 // a lane's elements of one row (zero where the lane holds none or !ok): the split of fm_ld_row
 template <int VW, int CPL>
 __device__ __forceinline__ void fi_ld_row(const float* row, int F, int sub, int lpt, bool ok, float (&r)[CPL][VW]) {
@@ -88,13 +90,6 @@ struct FismCut {
     double* part_s;           // [pcap]
     int32_t* part_c;          // [pcap]
 };
-
-// pieces of a list of len positions as the scanned count: low word pieces, high word the same where there is more than one
-__device__ __forceinline__ u64 fi_plen(int64_t len, int piece) {
-    const u64 np = len <= piece ? 1ull : (u64)((len + piece - 1) / piece);
-    return np | (np > 1 ? np << 32 : 0ull);
-}
-__device__ __forceinline__ int64_t fi_lo(u64 v) { return (int64_t)(u32)v; }
 
 // forward source: the history's own rows, unfiltered; the float beside the row is sum |row|^2
 struct FismSrcHist {
@@ -338,41 +333,7 @@ struct FismFinFan {
     }
 };
 
-// ---- keys, slots ----------------------------------------------------------------------------------------------------------------
-// users as u, items as U + i; the counters of the two combine passes and the piece counts of the slots start at zero
-__global__ __launch_bounds__(256) void k_fism_keys(const int32_t* __restrict__ u, const int32_t* __restrict__ i, int64_t B, u32 U,
-                                                   u32* __restrict__ key, u32* __restrict__ val, int32_t* split_u, int32_t* split_i,
-                                                   u64* __restrict__ plen, int64_t n_max) {
-    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (b == 0) split_u[0] = 0, split_i[0] = 0;
-    for (int64_t t = b; t <= n_max; t += (int64_t)gridDim.x * 256) plen[t] = 0ull;
-    if (b >= B) return;
-    key[b] = (u32)u[b], val[b] = (u32)b;
-    key[B + b] = U + (u32)i[b], val[B + b] = (u32)b;
-}
-
-__global__ __launch_bounds__(256) void k_fism_heads(const u32* __restrict__ keys, int64_t n, int32_t* __restrict__ hd) {
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= n) return;
-    hd[p] = (p == 0 || keys[p - 1] != keys[p]) ? 1 : 0;
-}
-
-// the head of every user segment: the user's slot (hs = the exclusive scan of hd), the slot's user and its pieces
-__global__ __launch_bounds__(256) void k_fism_users(const u32* __restrict__ keys, const int32_t* __restrict__ hd, const int32_t* __restrict__ hs,
-                                                    int64_t B, int64_t U, int64_t n_max, const int64_t* __restrict__ h_indptr, int piece,
-                                                    int32_t* __restrict__ rows, int32_t* __restrict__ slot, u64* __restrict__ plen,
-                                                    int32_t* __restrict__ n_out) {
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= B) return;
-    if (p == B - 1) *n_out = hs[p] + hd[p];
-    if (!hd[p]) return;
-    const int64_t user = (int64_t)keys[p], sl = hs[p];
-    if (user >= U || sl >= n_max) return;                        // (an id past the table writes nothing outside the map)
-    rows[sl] = (int32_t)user;
-    slot[user] = (int32_t)sl;
-    plen[sl] = fi_plen(h_indptr[user + 1] - h_indptr[user], piece);
-}
-
+// ---- keys, slots: k_fism_keys, k_fism_heads, k_fism_users (el_fism_keys.h) ------------------------------------------------------
 // the piece counts of ALL nl lists of a CSR (the fan-out, the image); entry nl closes the scan
 __global__ __launch_bounds__(256) void k_fism_plen(const int64_t* __restrict__ indptr, int64_t nl, int piece, u64* __restrict__ plen) {
     const int64_t l = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -488,24 +449,7 @@ __global__ __launch_bounds__(256) void k_fism_predict(FismTabs t, const int32_t*
 }
 
 // ---- the two sorted-segment passes ------------------------------------------------------------------------------------------------
-// samples of one row: the positions of its key in the sorted keys of its side
-__device__ __forceinline__ int fi_count(const u32* __restrict__ keys, int64_t n, u32 key) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (keys[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    const int64_t first = lo;
-    hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (keys[mid] <= key) lo = mid + 1;
-        else hi = mid;
-    }
-    return (int)(lo - first);
-}
-
+// (fi_count, the samples of one row: el_fism_keys.h)
 // finish of a complete user row (T_u, sum c_b): R_u = coef_u T_u and cnt_u to the user's slot, gBu
 struct FismFinUser {
     const u32* keys;

@@ -2996,6 +2996,98 @@ class FismDeviceState:
         return v
 
 
+class NaisDeviceState:
+    """NAIS_model's ten variables (neural/NAIS/nais_model.py, `algorithm: concat`) with their dense accumulators and Adam slots, coef =
+    n_u^-alpha, the train matrix user-major and item-major (fism_history_index) and the step's slot map (include/elliot_hip.h,
+    el_nais_state).  weights: a dict Gi, Gj [I, F], Bu [U], Bi [I], W1 [2F, 2F], b1 [2F], W2 [2F, Ws], b2 [Ws], W3 [Ws] or [Ws, 1],
+    b3 [1].  padding / loss as FismDeviceState."""
+
+    NAMES = _lib.NAIS_NAMES
+
+    def __init__(self, ctx, weights, history, alpha=0.0, beta=0.5, l_b=1e-7, padding="reference", loss="reference"):
+        self.ctx, dev = ctx, ctx.device
+        for n in self.NAMES:
+            t = _own(weights[n], dev)
+            setattr(self, n, t if n in ("Gi", "Gj", "W1", "W2") else t.reshape(-1).contiguous())
+        self.I, self.F = (int(x) for x in self.Gi.shape)
+        self.U, self.Ws = int(self.Bu.numel()), int(self.W3.numel())
+        F2 = 2 * self.F
+        shapes = {"Gj": (self.I, self.F), "Bi": (self.I,), "W1": (F2, F2), "b1": (F2,), "W2": (F2, self.Ws), "b2": (self.Ws,), "b3": (1,)}
+        if any(tuple(getattr(self, n).shape) != s for n, s in shapes.items()) or len(history[0]) != self.U + 1:
+            raise ValueError("NaisDeviceState: Gi, Gj [I, F], Bu [U], Bi [I], W1 [2F, 2F], b1 [2F], W2 [2F, Ws], b2 [Ws], W3 [Ws], b3 [1]")
+        if padding not in ("reference", "none") or loss not in FISM_LOSSES:
+            raise ValueError("NaisDeviceState: padding is 'reference' or 'none', loss is 'reference' or 'bce'")
+        self.index = fism_history_index(history[0], history[1], self.I)
+        lens = np.diff(self.index[0])
+        self.nnz, self.longest = int(self.index[0][-1]), int(lens.max()) if lens.size else 0
+        self.pad_len = self.longest if padding == "reference" else 0
+        with np.errstate(divide="ignore"):
+            coef = np.where(lens > 0, np.power(lens.astype(np.float32), np.float32(-float(alpha))), np.float32(0)).astype(np.float32)
+        self.coef = torch.from_numpy(coef).to(dev)
+        self.h_indptr, self.h_indices, self.t_indptr, self.t_indices = (
+            torch.from_numpy(a if a.size else np.zeros(1, a.dtype)).to(dev) for a in self.index)
+        for n in self.NAMES:
+            for pre in ("g", "m", "v"):
+                setattr(self, pre + n, torch.zeros_like(getattr(self, n)))
+        self.slot = torch.full((self.U,), -1, dtype=torch.int32, device=dev)
+        self.loss = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.step = 0
+        p = lambda t: t.data_ptr()
+        self._c = _lib.NaisState(U=self.U, I=self.I, nnz=self.nnz, F=self.F, Ws=self.Ws, alpha=float(alpha), beta_smooth=float(beta),
+                                 l_b=float(l_b), loss_kind=FISM_LOSSES[loss], pad_len=self.pad_len,
+                                 **{pre + n: p(getattr(self, pre + n)) for pre in ("", "g", "m", "v") for n in self.NAMES},
+                                 coef=p(self.coef), h_indptr=p(self.h_indptr), h_indices=p(self.h_indices), t_indptr=p(self.t_indptr),
+                                 t_indices=p(self.t_indices), slot=p(self.slot))
+
+    def _call(self, name, *args):
+        fn = getattr(self.ctx.lib, name)
+        check(fn(self.ctx.handle, self.ctx.stream(), C.byref(self._c), *args), name)
+
+    def _step_ws(self, B):
+        need = int(self.ctx.lib.el_nais_ws_bytes(self.ctx.handle, C.byref(self._c), int(B)))
+        return _ptr(workspace(self, "_ws", need, self.ctx.device)), need
+
+    def _score_ws(self):
+        need = int(self.ctx.lib.el_nais_scores_ws_bytes(self.ctx.handle, C.byref(self._c)))
+        return _ptr(workspace(self, "_sws", need, self.ctx.device)), need
+
+    def _batch(self, u, i, y):
+        return _ptr(u, torch.int32, "u"), _ptr(i, torch.int32, "i"), _ptr(y, torch.float32, "y"), int(u.numel())
+
+    def grads(self, u, i, y):
+        """Loss and tape.gradient of train_step (:152-163) into the ten accumulators; apply() consumes them."""
+        self._call("el_nais_grads", *self._batch(u, i, y), _ptr(self.loss, torch.float64), *self._step_ws(u.numel()))
+
+    def apply(self, lr):
+        self.step += 1
+        self._call("el_nais_apply", int(self.step), float(adam_lr_t(lr, self.step)))
+
+    def train_step(self, u, i, y, lr):
+        self.step += 1
+        self._call("el_nais_train_step", *self._batch(u, i, y), int(self.step), float(adam_lr_t(lr, self.step)),
+                   _ptr(self.loss, torch.float64), *self._step_ws(u.numel()))
+
+    def forward(self, u, i, out=None):
+        """The model's score of an explicit pair list, as batch_predict computes it (el_nais_forward)."""
+        if out is None:
+            out = torch.empty(u.numel(), dtype=torch.float32, device=self.ctx.device)
+        self._call("el_nais_forward", _ptr(u, torch.int32, "u"), _ptr(i, torch.int32, "i"), int(u.numel()), _ptr(out, torch.float32),
+                   *self._score_ws())
+        return out
+
+    def scores(self, u_start, u_stop, out=None):
+        """batch_predict (:194-219) of users [u_start, u_stop) against ALL items: a dense [users, I] block (el_nais_scores)."""
+        if out is None:
+            out = torch.empty((int(u_stop) - int(u_start), self.I), dtype=torch.float32, device=self.ctx.device)
+        self._call("el_nais_scores", int(u_start), int(u_stop), _ptr(out, torch.float32), int(out.stride(0)), *self._score_ws())
+        return out
+
+    def recommend(self, u_start, u_stop, k, excl=None, cand=None):
+        return dense_topk(self.ctx, self.scores(u_start, u_stop), u_start, u_stop, k, excl=excl, cand=cand)
+
+    pop_loss = FismDeviceState.pop_loss
+
+
 # ------------------------------------------------------------------------------------------
 # graph propagation: LightGCN (graph_based/lightgcn) -- SURVEY 8f N3
 # ------------------------------------------------------------------------------------------

@@ -551,6 +551,68 @@ int el_fism_forward(el_ctx* ctx, void* stream, const el_fism_state* st, const in
  * el_pwmf_link_values(EL_PW_MSE_SIGMOID, Bu) and the re-rank.  ws: el_fism_image_ws_bytes(...).                                */
 int el_fism_user_image(el_ctx* ctx, void* stream, const el_fism_state* st, float* P, void* ws, size_t ws_bytes);
 
+/* ---- NAIS: neural attentive item similarity, `algorithm: concat` (neural/NAIS; el_nais.hip) -----------------------
+ * FISM's tables, sampler, loss and regulariser; every history row is weighted by a small MLP that sees the history item and the
+ * target.  With H(u) = (h_1 .. h_n) in CSR order, t = Gj[j], W1 [2F, 2F] (rows [0, F): the history half W1a, rows [F, 2F): the
+ * target half W1b), b1 [2F], W2 [2F, Ws], b2 [Ws], W3 [Ws], b3 [1]:
+ *   s_k = Gi[h_k] . t     v_k = [Gi[h_k], t] W1 + b1     a_k = (relu(v_k) W2 + b2) W3 + b3     x_k = exp(a_k)   (no max subtracted)
+ *   S = sum x_k,  N = sum x_k s_k,   out = sigma(coef[u] N / S^beta_smooth + Bu[u] + Bi[j])                (nais_model.py:79-150)
+ * Factored here as v_k = A[h_k] + Bt[j] with A = Gi W1a, Bt = Gj W1b + b1 (one product each per call) and a_k = relu(v_k) . w + c
+ * with w = W2 W3, c = b2 . W3 + b3.  Training masks the padded slots out of the attention; scoring does not: with pad_len = L the
+ * L - n slots of item id 0 add (L - n) x_0 to S and (L - n) x_0 s_0 to N.  The regulariser is FISM's with beta = 1 and
+ * lambda = gamma = l_b (a sum over samples, the padded slots inside with pad_len = L).  Entry points only: EL_ABI_VERSION stays.  */
+typedef struct el_nais_state {
+    int64_t U, I, nnz;                                  /* nnz = h_indptr[U] = t_indptr[I] */
+    int32_t F;                                          /* 1 .. 256 */
+    int32_t Ws;                                         /* >= 1: width of the second layer */
+    float alpha;                                        /* informational: the kernels read coef */
+    float beta_smooth;                                  /* exponent of the softmax denominator */
+    float l_b;                                          /* regulariser of Bu and Bi (Gi and Gj carry coefficient 1) */
+    int32_t loss_kind;                                  /* EL_FISM_LOSS_* */
+    int64_t pad_len;                                    /* L: the reference's padded history width; 0: no padded slots anywhere */
+    float* Gi;  float* gGi;  float* mGi;  float* vGi;   /* [I, F] variable, accumulator (written by el_nais_grads, zero after el_nais_apply), Adam slots */
+    float* Gj;  float* gGj;  float* mGj;  float* vGj;   /* [I, F]; gGj, gBu, gBi zero on entry of el_nais_grads */
+    float* Bu;  float* gBu;  float* mBu;  float* vBu;   /* [U] */
+    float* Bi;  float* gBi;  float* mBi;  float* vBi;   /* [I] */
+    float* W1;  float* gW1;  float* mW1;  float* vW1;   /* [2F, 2F] */
+    float* b1;  float* gb1;  float* mb1;  float* vb1;   /* [2F] */
+    float* W2;  float* gW2;  float* mW2;  float* vW2;   /* [2F, Ws] */
+    float* b2;  float* gb2;  float* mb2;  float* vb2;   /* [Ws] */
+    float* W3;  float* gW3;  float* mW3;  float* vW3;   /* [Ws] */
+    float* b3;  float* gb3;  float* mb3;  float* vb3;   /* [1] */
+    const float* coef;                                  /* [U] n_u^-alpha, computed by the caller */
+    const int64_t* h_indptr;  const int32_t* h_indices; /* user -> items: [U + 1], [nnz] */
+    const int64_t* t_indptr;  const int32_t* t_indices; /* item -> users: [I + 1], [nnz], ids ascending in a list */
+    int32_t* slot;                                      /* [U] scratch map; -1 on entry and on exit */
+} el_nais_state;
+
+/* Scratch of el_nais_grads / el_nais_train_step for B samples (0 = bad arguments).  Depends on the option fism_piece, not on the
+ * history lengths: B + max(B, nnz / piece) partial rows of 5F + 1 doubles sample-major (the pieces of the batch's histories are
+ * packed by a scan; their length is fism_piece, doubled per batch until they fit) and I + nnz / piece rows of 3F + 1 item-major. */
+size_t el_nais_ws_bytes(el_ctx* ctx, const el_nais_state* st, int64_t B);
+
+/* Replaces: the loss and tape.gradient of NAIS_model.train_step (:152-166) on B samples (u, j, label): all ten accumulators.  With
+ * r_b = dL/dx_b coef_u S^-beta:  ds_k = r x_k,  da_k = r x_k (s_k - beta N / S),  dv_k = da_k w * [v_k > 0]; the pairs are recomputed
+ * in the sample-major backward walk (gGj, gBt, gw, gc) and in the item-major fan-out (gGi, gA): nothing per pair is stored.  No
+ * floating-point atomics, a fixed order in every sum: the same input gives the same bytes.  L is ADDED to loss_out (device
+ * double[1]).  u in [0, U) with n_u >= 1, j in [0, I): not checked.                                                          */
+int el_nais_grads(el_ctx* ctx, void* stream, const el_nais_state* st, const int32_t* u, const int32_t* j, const float* label, int64_t B,
+                  double* loss_out, void* ws, size_t ws_bytes);
+/* Keras Adam on all ten variables (every row moves: k_adam_dense); the accumulators come back zero. */
+int el_nais_apply(el_ctx* ctx, void* stream, const el_nais_state* st, int32_t step, float lr_t);
+int el_nais_train_step(el_ctx* ctx, void* stream, const el_nais_state* st, const int32_t* u, const int32_t* j, const float* label,
+                       int64_t B, int32_t step, float lr_t, double* loss_out, void* ws, size_t ws_bytes);
+
+/* Scratch of el_nais_forward and el_nais_scores: A and Bt [I, 2F], w, c and the products' own scratch. */
+size_t el_nais_scores_ws_bytes(el_ctx* ctx, const el_nais_state* st);
+/* The model's score of explicit pairs as batch_predict (:194-219) computes it (padded slots included with pad_len = L). */
+int el_nais_forward(el_ctx* ctx, void* stream, const el_nais_state* st, const int32_t* u, const int32_t* j, int64_t n, float* out,
+                    void* ws, size_t ws_bytes);
+/* out[u - u_start, j] for users [u_start, u_stop) and ALL items (ld >= I), for el_dense_topk.  One workgroup takes 64 history
+ * positions of one user against 64 targets; S and N are carried per target across the position tiles in ascending order.       */
+int el_nais_scores(el_ctx* ctx, void* stream, const el_nais_state* st, int64_t u_start, int64_t u_stop, float* out, int64_t ld,
+                   void* ws, size_t ws_bytes);
+
 /* ---- BPR-MF, NumPy semantics (BPRMF; K5) ------------------------------------- */
 
 typedef struct el_bprsgd_state {
