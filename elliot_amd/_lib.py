@@ -91,6 +91,20 @@ class NaisState(C.Structure):
                 *[f for n in NAIS_NAMES for f in _quad(n)], ("coef", _f32p),
                 ("h_indptr", _i64p), ("h_indices", _i32p), ("t_indptr", _i64p), ("t_indices", _i32p), ("slot", _i32p)]
 
+EL_DMF_DOT, EL_DMF_COS_BATCH, EL_DMF_COS_ROW = 0, 1, 2
+EL_DMF_WS_STEP, EL_DMF_WS_TOWERS, EL_DMF_WS_SCORES, EL_DMF_WS_FORWARD = 0, 1, 2, 3
+DMF_ARRAYS = ("W", "b", "gW", "gb", "mW", "vW", "mb", "vb")
+
+
+class DmfTower(C.Structure):
+    _fields_ = [("n_layers", C.c_int32), ("width", C.c_int32 * 4), ("reserved", C.c_int32), *[(n, _f32p * 4) for n in DMF_ARRAYS]]
+
+
+class DmfState(C.Structure):
+    _fields_ = [("U", C.c_int64), ("I", C.c_int64), ("nnz", C.c_int64), ("sim", C.c_int32), ("max_rating", C.c_float), ("tw", DmfTower * 2),
+                ("r_indptr", _i64p), ("r_indices", _i32p), ("r_values", _f32p), ("t_indptr", _i64p), ("t_indices", _i32p), ("t_values", _f32p),
+                ("slot_u", _i32p), ("slot_i", _i32p)]
+
 
 class BprsgdState(C.Structure):
     _fields_ = [
@@ -268,6 +282,16 @@ PROTOTYPES = {
     "el_nais_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(NaisState), _i32p, _i32p, C.c_int64, _f32p, C.c_void_p, C.c_size_t]),
     "el_nais_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(NaisState), C.c_int64, C.c_int64, _f32p, C.c_int64, C.c_void_p,
                                  C.c_size_t]),
+    "el_dmf_ws_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(DmfState), C.c_int64, C.c_int32]),
+    "el_dmf_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DmfState), _i32p, _i32p, _f32p, C.c_int64, _f64p, C.c_void_p, C.c_size_t]),
+    "el_dmf_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DmfState), C.c_int32, C.c_float]),
+    "el_dmf_train_step": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DmfState), _i32p, _i32p, _f32p, C.c_int64, C.c_int32, C.c_float, _f64p,
+                                    C.c_void_p, C.c_size_t]),
+    "el_dmf_towers": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DmfState), _f32p, _f32p, C.c_void_p, C.c_size_t]),
+    "el_dmf_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DmfState), _f32p, _f32p, _i32p, _i32p, C.c_int64, _f32p, C.c_void_p,
+                                 C.c_size_t]),
+    "el_dmf_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DmfState), _f32p, _f32p, C.c_int64, C.c_int64, _f32p, C.c_int32, _f32p,
+                                C.c_int64, C.c_void_p, C.c_size_t]),
     "el_spmm_csr_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GraphCsr), _f32p, _f32p, C.c_int32, _f32p, _f32p]),
     "el_lightgcn_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "el_lightgcn_propagate": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GraphCsr), _f32p, _f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t]),

@@ -17,9 +17,9 @@ FLAGS = [
     "-ffp-contract=off",     # every fma in the kernels is explicit (top-k bit-exactness)
     "-Wno-unused-result",
 ]
-# per-source additions: el_fm.hip, el_fism.hip and el_nais.hip keep their row sums on scalar fp32 instructions (no packed-fp32 forms)
+# per-source additions: el_fm.hip, el_fism.hip, el_nais.hip and el_dmf.hip keep their row sums on scalar fp32 instructions (no packed-fp32 forms)
 _NO_PACKED = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"el_fm.hip": _NO_PACKED, "el_fism.hip": _NO_PACKED, "el_nais.hip": _NO_PACKED}
+EXTRA_FLAGS = {"el_fm.hip": _NO_PACKED, "el_fism.hip": _NO_PACKED, "el_nais.hip": _NO_PACKED, "el_dmf.hip": _NO_PACKED}
 
 
 def sources():

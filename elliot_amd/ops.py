@@ -3088,6 +3088,130 @@ class NaisDeviceState:
     pop_loss = FismDeviceState.pop_loss
 
 
+DMF_SIMS = {("dot", "reference"): _lib.EL_DMF_DOT, ("dot", "row"): _lib.EL_DMF_DOT, ("cosine", "reference"): _lib.EL_DMF_COS_BATCH,
+            ("cosine", "row"): _lib.EL_DMF_COS_ROW}
+
+
+class DmfDeviceState:
+    """DeepMatrixFactorizationModel's variables (neural/DMF/deep_matrix_factorization_model.py) with their Adam slots, the rating matrix
+    as CSR with values user-major and item-major, and the step's two slot maps (include/elliot_hip.h, el_dmf_state).  weights: a dict
+    "user" / "item" -> [(kernel [in, out], bias [out]), ...], the first kernel [I, H1] / [U, H1].  ratings = (indptr, indices, values)
+    of sp_i_train_ratings.  cosine_axis: "reference" (the batch axis, as written) | "row" (the feature axis); ignored for dot."""
+
+    SIDES = ("user", "item")
+
+    def __init__(self, ctx, weights, ratings, similarity="cosine", cosine_axis="reference", max_rating=1.0):
+        self.ctx, dev = ctx, ctx.device
+        if (similarity, cosine_axis) not in DMF_SIMS:
+            raise ValueError("DmfDeviceState: similarity is 'dot' or 'cosine', cosine_axis is 'reference' or 'row'")
+        indptr, indices, values = (np.asarray(a) for a in ratings)
+        self.U, self.I = int(weights["item"][0][0].shape[0]), int(weights["user"][0][0].shape[0])
+        if len(indptr) != self.U + 1:
+            raise ValueError("DmfDeviceState: the first kernels are [I, H1] (user tower) and [U, H1] (item tower)")
+        index = fism_history_index(indptr, indices, self.I)
+        order = np.argsort(np.asarray(indices, np.int64), kind="stable")
+        host = (*index[:2], np.asarray(values, np.float32), *index[2:], np.asarray(values, np.float32)[order])
+        self.nnz = int(index[0][-1])
+        self.csr = [torch.from_numpy(np.ascontiguousarray(a) if a.size else np.zeros(1, a.dtype)).to(dev) for a in host]
+        self.names, self.gW0 = [], [None, None]
+        self._c = _lib.DmfState(U=self.U, I=self.I, nnz=self.nnz, sim=DMF_SIMS[(similarity, cosine_axis)], max_rating=float(max_rating))
+        for t, side in enumerate(self.SIDES):
+            tw = self._c.tw[t]
+            tw.n_layers = len(weights[side])
+            for l, (W, b) in enumerate(weights[side][:4]):
+                for n, x in (("W", W), ("b", np.asarray(b).reshape(-1))):
+                    name = f"{side[0]}{n}{l}"
+                    setattr(self, name, _own(x, dev))
+                    self.names.append(name)
+                    for pre in ("g", "m", "v"):
+                        if pre + n + str(l) != "gW0":                                # (gW of a first layer exists only for grads())
+                            setattr(self, f"{side[0]}{pre}{n}{l}", torch.zeros_like(getattr(self, name)))
+                            getattr(tw, pre + n)[l] = getattr(self, f"{side[0]}{pre}{n}{l}").data_ptr()
+                    getattr(tw, n)[l] = getattr(self, name).data_ptr()
+                tw.width[l] = int(W.shape[1])
+        self.D = int(weights["user"][-1][0].shape[1])
+        for f, t in zip(("r_indptr", "r_indices", "r_values", "t_indptr", "t_indices", "t_values"), self.csr):
+            setattr(self._c, f, t.data_ptr())
+        self.slot_u = torch.full((self.U,), -1, dtype=torch.int32, device=dev)
+        self.slot_i = torch.full((self.I,), -1, dtype=torch.int32, device=dev)
+        self._c.slot_u, self._c.slot_i = self.slot_u.data_ptr(), self.slot_i.data_ptr()
+        self.loss = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.step, self._towers, self._qt = 0, None, {}
+
+    def _call(self, name, *args):
+        check(getattr(self.ctx.lib, name)(self.ctx.handle, self.ctx.stream(), C.byref(self._c), *args), name)
+
+    def _ws(self, n, what):
+        need = int(self.ctx.lib.el_dmf_ws_bytes(self.ctx.handle, C.byref(self._c), int(n), int(what)))
+        if need == 0:
+            raise _lib.ElliotHipError("el_dmf_ws_bytes: " + self.ctx.lib.el_last_error().decode())
+        return _ptr(workspace(self, "_ws%d" % what, need, self.ctx.device)), need
+
+    def _batch(self, u, i, y):
+        return _ptr(u, torch.int32, "u"), _ptr(i, torch.int32, "i"), _ptr(y, torch.float32, "y"), int(u.numel())
+
+    def touch(self):
+        self._towers, self._qt = None, {}
+
+    def grads(self, u, i, y):
+        """Loss and tape.gradient of train_step (:94-102) into the gradient buffers, the two first kernels' included (ugW0, igW0)."""
+        for t, side in enumerate(self.SIDES):
+            if self.gW0[t] is None:
+                self.gW0[t] = torch.zeros_like(getattr(self, side[0] + "W0"))
+                setattr(self, side[0] + "gW0", self.gW0[t])
+                self._c.tw[t].gW[0] = self.gW0[t].data_ptr()
+        self._call("el_dmf_grads", *self._batch(u, i, y), _ptr(self.loss, torch.float64), *self._ws(u.numel(), _lib.EL_DMF_WS_STEP))
+
+    def apply(self, lr):
+        self.step += 1
+        self.touch()
+        self._call("el_dmf_apply", int(self.step), float(adam_lr_t(lr, self.step)))
+
+    def train_step(self, u, i, y, lr):
+        self.step += 1
+        self.touch()
+        self._call("el_dmf_train_step", *self._batch(u, i, y), int(self.step), float(adam_lr_t(lr, self.step)),
+                   _ptr(self.loss, torch.float64), *self._ws(u.numel(), _lib.EL_DMF_WS_STEP))
+
+    def towers(self):
+        """(P [U, D], Q [I, D]) of the current variables: computed once per change of the variables (el_dmf_towers)."""
+        if self._towers is None:
+            P = torch.empty((self.U, self.D), dtype=torch.float32, device=self.ctx.device)
+            Q = torch.empty((self.I, self.D), dtype=torch.float32, device=self.ctx.device)
+            self._call("el_dmf_towers", _ptr(P), _ptr(Q), *self._ws(0, _lib.EL_DMF_WS_TOWERS))
+            self._towers = (P, Q)
+        return self._towers
+
+    def forward(self, u, i, out=None):
+        """y of `call` on the pairs taken as one batch (el_dmf_forward)."""
+        if out is None:
+            out = torch.empty(u.numel(), dtype=torch.float32, device=self.ctx.device)
+        P, Q = self.towers()
+        self._call("el_dmf_forward", _ptr(P), _ptr(Q), _ptr(u, torch.int32, "u"), _ptr(i, torch.int32, "i"), int(u.numel()),
+                   _ptr(out, torch.float32), *self._ws(u.numel(), _lib.EL_DMF_WS_FORWARD))
+        return out
+
+    def scores(self, u_start, u_stop, out=None):
+        """get_recs (:119-132) of the chunk of users [u_start, u_stop) against ALL items (el_dmf_scores).  The scaled item table is
+        kept per chunk length: an evaluation computes it at most twice."""
+        n = int(u_stop) - int(u_start)
+        if out is None:
+            out = torch.empty((n, self.I), dtype=torch.float32, device=self.ctx.device)
+        P, Q = self.towers()
+        key = n if self._c.sim == _lib.EL_DMF_COS_BATCH else 0
+        ready = key in self._qt
+        if not ready and self._c.sim != _lib.EL_DMF_DOT:
+            self._qt[key] = torch.empty_like(Q)
+        self._call("el_dmf_scores", _ptr(P), _ptr(Q), int(u_start), int(u_stop), _ptr(self._qt.get(key)), int(ready), _ptr(out, torch.float32),
+                   int(out.stride(0)), *self._ws(n, _lib.EL_DMF_WS_SCORES))
+        return out
+
+    def recommend(self, u_start, u_stop, k, excl=None, cand=None):
+        return dense_topk(self.ctx, self.scores(u_start, u_stop), u_start, u_stop, k, excl=excl, cand=cand)
+
+    pop_loss = FismDeviceState.pop_loss
+
+
 # ------------------------------------------------------------------------------------------
 # graph propagation: LightGCN (graph_based/lightgcn) -- SURVEY 8f N3
 # ------------------------------------------------------------------------------------------

@@ -37,9 +37,10 @@ from .visual_recommenders.VBPR.VBPR import VBPR
 from .latent_factor_models.FM.factorization_machine import FM
 from .latent_factor_models.FISM.FISM import FISM
 from .neural.NAIS.nais import NAIS
+from .neural.DMF.deep_matrix_factorization import DMF
 
 __all__ = ["BaseRecommenderModel", "init_charger", "RecMixin", "BPRMF_batch", "BPRMF", "MultiVAE", "MultiDAE", "NeuMF", "GMF",
            "MF", "PMF", "FunkSVD", "LogisticMatrixFactorization", "LMF", "CML", "MF2020", "LightGCN", "NGCF", "ProxyRecommender",
            "ItemKNN", "UserKNN", "iALS", "WRMF", "EASER", "RP3beta", "Slim", "PureSVD",
            "AttributeItemKNN", "AttributeUserKNN", "VSM", "KaHFM", "SlopeOne", "BPRSlim", "ItemAutoRec", "UserAutoRec", "AMF",
-           "VBPR", "FM", "FISM", "NAIS"]
+           "VBPR", "FM", "FISM", "NAIS", "DMF"]

@@ -613,6 +613,76 @@ int el_nais_forward(el_ctx* ctx, void* stream, const el_nais_state* st, const in
 int el_nais_scores(el_ctx* ctx, void* stream, const el_nais_state* st, int64_t u_start, int64_t u_stop, float* out, int64_t ld,
                    void* ws, size_t ws_bytes);
 
+/* ---- DMF: deep matrix factorization (neural/DMF; el_dmf.hip) ---------------------------------------------------------
+ * No embedding table: p = MLP_u(R[u, :]), q = MLP_i(R[:, i]) with R the train matrix WITH its rating values; every layer but the last
+ * is Dense(relu), the last is linear, both towers end in the same width D.  y is the dot product of p and q, or their cosine:
+ *   EL_DMF_COS_BATCH  as the reference writes it, tf.nn.l2_normalize(., 0): every column d is divided by the root of its sum of
+ *                     squares over the B samples of the batch (duplicates counted), floored at 1e-12 under the root
+ *   EL_DMF_COS_ROW    the paper's cosine: each p_b and q_b divided by its own norm
+ * Loss: Keras BinaryCrossentropy()(label / max_rating, y) -- y clipped to [1e-7, 1 - 1e-7] (no gradient outside), mean over B.  One
+ * Keras Adam with TF's dense ApplyAdam arithmetic on every kernel and bias.  Entry points only: EL_ABI_VERSION stays.              */
+#define EL_DMF_DOT 0
+#define EL_DMF_COS_BATCH 1
+#define EL_DMF_COS_ROW 2
+#define EL_DMF_WS_STEP 0      /* el_dmf_ws_bytes: el_dmf_grads / el_dmf_train_step on n samples */
+#define EL_DMF_WS_TOWERS 1    /* el_dmf_towers (n is not read) */
+#define EL_DMF_WS_SCORES 2    /* el_dmf_scores on a chunk of n users */
+#define EL_DMF_WS_FORWARD 3   /* el_dmf_forward on n pairs */
+
+typedef struct el_dmf_tower {
+    int32_t n_layers;                                   /* 1 .. 4 */
+    int32_t width[4];                                   /* output width of layer l, 1 .. 256 */
+    int32_t reserved;
+    float* W[4];   float* b[4];                         /* Keras layout: kernel [in, out], bias [out]; W[0] is [I, width[0]] (user tower) or [U, width[0]] */
+    float* gW[4];  float* gb[4];                        /* gradients, overwritten by every step; gW[0] is read and written by el_dmf_grads / el_dmf_apply only (may be NULL otherwise) */
+    float* mW[4];  float* vW[4];  float* mb[4];  float* vb[4];
+} el_dmf_tower;
+
+typedef struct el_dmf_state {
+    int64_t U, I, nnz;
+    int32_t sim;                                        /* EL_DMF_DOT | EL_DMF_COS_BATCH | EL_DMF_COS_ROW */
+    float max_rating;                                   /* labels are divided by it */
+    el_dmf_tower tw[2];                                 /* 0: the user tower over the rows of R, 1: the item tower over the rows of R^T */
+    const int64_t* r_indptr;  const int32_t* r_indices;  const float* r_values;   /* R   user -> (item, rating): [U + 1], [nnz], [nnz] */
+    const int64_t* t_indptr;  const int32_t* t_indices;  const float* t_values;   /* R^T item -> (user, rating): [I + 1], [nnz], [nnz] */
+    int32_t* slot_u;  int32_t* slot_i;                  /* [U], [I] scratch maps; -1 on entry and on exit */
+} el_dmf_state;
+
+/* Scratch of the call named by `what` (EL_DMF_WS_*) for n samples / users / pairs; 0 = bad arguments (el_last_error says which: a
+ * tower deeper than 4 layers, a width outside 1 .. 256, towers that end in different widths).  Depends on the option fism_piece. */
+size_t el_dmf_ws_bytes(el_ctx* ctx, const el_dmf_state* st, int64_t n, int32_t what);
+
+/* Replaces: the loss and tape.gradient of DeepMatrixFactorizationModel.train_step (:94-105) on B samples (u, i, label).  All tower
+ * work runs once per DISTINCT user and item of the batch.  First layer: the rating-weighted ordered row sum over the row's CSR list,
+ * cut into pieces of fism_piece positions (a double per lane, pieces combined in piece order).  Inner layers: el_gemm_f32; the last
+ * layer's forward on the distinct rows is summed in double and kept there (y and 1 / y see unrounded tower outputs).  dp / dq
+ * per distinct row: the ordered sum over the row's samples in batch order.  gW[0] [N, width[0]] of either tower: the ordered sum over
+ * the TRANSPOSED list of row j of rating * dz1[slot]; gb and the inner gW complete in their buffers.  No floating-point atomics: the
+ * same input gives the same bytes.  L is ADDED to loss_out (device double[1]).  u in [0, U), i in [0, I): not checked.           */
+int el_dmf_grads(el_ctx* ctx, void* stream, const el_dmf_state* st, const int32_t* u, const int32_t* i, const float* label, int64_t B,
+                 double* loss_out, void* ws, size_t ws_bytes);
+/* Dense Adam on every variable from the gradient buffers (gW[0] included).  lr_t: the bias-corrected step size of `step`. */
+int el_dmf_apply(el_ctx* ctx, void* stream, const el_dmf_state* st, int32_t step, float lr_t);
+/* The same step with the first-layer weight gradient never stored: the lane group that completes row j of gW[0] reads W[0][j], m, v,
+ * moves them and writes them, once; a row the batch does not reach takes its move with g = 0.  Equal to grads + apply bit for bit. */
+int el_dmf_train_step(el_ctx* ctx, void* stream, const el_dmf_state* st, const int32_t* u, const int32_t* i, const float* label,
+                      int64_t B, int32_t step, float lr_t, double* loss_out, void* ws, size_t ws_bytes);
+
+/* P [U, D] and Q [I, D]: the towers of every user and every item, every layer on el_gemm_f32, float32 tables.  (A step keeps its own
+ * last-layer outputs in double; el_dmf_forward and el_dmf_scores read these float32 tables, so `predict` and the scores see tower
+ * outputs rounded to float32 where the loss of a step does not.)                                                                  */
+int el_dmf_towers(el_ctx* ctx, void* stream, const el_dmf_state* st, float* P, float* Q, void* ws, size_t ws_bytes);
+/* out[b] = y of `call` (:84-91) on the n pairs taken as ONE batch (EL_DMF_COS_BATCH normalises over these n pairs), unclipped. */
+int el_dmf_forward(el_ctx* ctx, void* stream, const el_dmf_state* st, const float* P, const float* Q, const int32_t* u, const int32_t* i,
+                   int64_t n, float* out, void* ws, size_t ws_bytes);
+/* Replaces get_recs (:119-132) for the chunk of users [u_start, u_stop) against ALL items: out[u - u_start, i] (ld >= I) =
+ * Pt[u] . Qt[i], for el_dense_topk.  EL_DMF_COS_BATCH: Pt[u, d] = P[u, d] rsqrt(max(sum over the chunk's users of P[., d]^2, 1e-12)),
+ * Qt[i, d] = Q[i, d] rsqrt(max(Uc Q[i, d]^2, 1e-12)) with Uc = u_stop - u_start: the scores depend on the chunking, as in the
+ * reference.  EL_DMF_COS_ROW: rows divided by their norms.  Qt [I, D] is the caller's: it is filled unless qt_ready != 0 (it depends
+ * on Uc alone, on nothing with EL_DMF_COS_ROW); not read with EL_DMF_DOT.                                                          */
+int el_dmf_scores(el_ctx* ctx, void* stream, const el_dmf_state* st, const float* P, const float* Q, int64_t u_start, int64_t u_stop,
+                  float* Qt, int32_t qt_ready, float* out, int64_t ld, void* ws, size_t ws_bytes);
+
 /* ---- BPR-MF, NumPy semantics (BPRMF; K5) ------------------------------------- */
 
 typedef struct el_bprsgd_state {
