@@ -106,6 +106,19 @@ class DmfState(C.Structure):
                 ("slot_u", _i32p), ("slot_i", _i32p)]
 
 
+EL_CNMF_WS_STEP, EL_CNMF_WS_FORWARD, EL_CNMF_WS_SCORES = 0, 1, 2
+CNMF_TABLES = ("P", "Q", "gP", "gQ", "mP", "vP", "mQ", "vQ")
+CNMF_CONV = ("W", "b", "gW", "gb", "mW", "vW", "mb", "vb")
+CNMF_HEAD = ("D", "gD", "mD", "vD")
+
+
+class CnmfState(C.Structure):
+    _fields_ = [("U", C.c_int64), ("I", C.c_int64), ("F", C.c_int32), ("n_layers", C.c_int32), ("channels", C.c_int32 * 7),
+                ("kernels", C.c_int32 * 6), ("strides", C.c_int32 * 6), ("reserved", C.c_int32), ("l_w", C.c_float), ("dropout", C.c_float),
+                ("seed", C.c_uint64), *[(n, _f32p) for n in CNMF_TABLES], *[(n, _f32p * 6) for n in CNMF_CONV],
+                *[(n, _f32p * 4) for n in CNMF_HEAD]]
+
+
 class BprsgdState(C.Structure):
     _fields_ = [
         ("P", _f64p), ("Q", _f64p), ("b", _f64p),
@@ -292,6 +305,17 @@ PROTOTYPES = {
                                  C.c_size_t]),
     "el_dmf_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DmfState), _f32p, _f32p, C.c_int64, C.c_int64, _f32p, C.c_int32, _f32p,
                                 C.c_int64, C.c_void_p, C.c_size_t]),
+    "el_cnmf_ws_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(CnmfState), C.c_int64, C.c_int32]),
+    "el_cnmf_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CnmfState), _i32p, _i32p, C.c_int64, _f32p, C.c_void_p, C.c_size_t]),
+    "el_cnmf_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CnmfState), _i32p, _i32p, _i32p, C.c_int64, C.c_int32, _f64p, C.c_void_p,
+                                C.c_size_t]),
+    "el_cnmf_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CnmfState), C.c_int32, C.c_float]),
+    "el_cnmf_train_step": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CnmfState), _i32p, _i32p, _i32p, C.c_int64, C.c_int32, C.c_float, _f64p,
+                                     C.c_void_p, C.c_size_t]),
+    "el_cnmf_item_image": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CnmfState), _f32p]),
+    "el_cnmf_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CnmfState), _f32p, C.c_int64, C.c_int64, _f32p, C.c_int64, C.c_void_p,
+                                 C.c_size_t]),
+    "el_cnmf_dropout_masks": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CnmfState), C.c_int32, C.c_int64, _f32p]),
     "el_spmm_csr_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GraphCsr), _f32p, _f32p, C.c_int32, _f32p, _f32p]),
     "el_lightgcn_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "el_lightgcn_propagate": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GraphCsr), _f32p, _f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t]),

@@ -3212,6 +3212,117 @@ class DmfDeviceState:
     pop_loss = FismDeviceState.pop_loss
 
 
+class ConvNeuMfDeviceState:
+    """ConvNeuralMatrixFactorizationModel's variables (neural/ConvNeuMF/convolutional_neural_matrix_factorization_model.py) with their
+    gradient buffers and Adam slots (include/elliot_hip.h, el_cnmf_state).  weights: a dict P [U, F], Q [I, F], "conv": [(kernel
+    [k, k, C_in, C_out], bias [C_out]), ...], "dense": [(Wd1 [C, C], bd1 [C]), (Wd2 [C, 1], bd2 [1])].  The variables in the
+    reference's order are `names`.  The item image of layer 1 is kept until touch()."""
+
+    def __init__(self, ctx, weights, channels, kernels, strides, l_w=0.0, dropout=0.0, dropout_seed=42):
+        self.ctx, dev = ctx, ctx.device
+        self.P, self.Q = _own(weights["P"], dev), _own(weights["Q"], dev)
+        (self.U, self.F), self.I = self.P.shape, int(self.Q.shape[0])
+        self.channels, self.kernels, self.strides = [int(x) for x in channels], [int(x) for x in kernels], [int(x) for x in strides]
+        if not len(self.channels) - 1 == len(self.kernels) == len(self.strides) == len(weights["conv"]):
+            raise ValueError("ConvNeuMfDeviceState: channels, kernels and strides don't match")
+        self._c = c = _lib.CnmfState(U=self.U, I=self.I, F=self.F, n_layers=len(self.kernels), l_w=float(l_w), dropout=float(dropout),
+                                     seed=int(dropout_seed))
+        self.names = ["P", "Q"]
+        for l, (W, b) in enumerate(weights["conv"][:6]):
+            setattr(self, f"W{l}", _own(W, dev))
+            setattr(self, f"b{l}", _own(np.asarray(b).reshape(-1), dev))
+            self.names += [f"W{l}", f"b{l}"]
+            c.channels[l + 1], c.kernels[l], c.strides[l] = self.channels[l + 1], self.kernels[l], self.strides[l]
+        c.channels[0] = self.channels[0]
+        for q, x in enumerate(x for Wb in weights["dense"] for x in Wb):
+            setattr(self, f"D{q}", _own(np.asarray(x).reshape(-1) if q != 0 else x, dev))
+            self.names.append(f"D{q}")
+        for n in self.names:
+            for pre in ("g", "m", "v"):
+                setattr(self, pre + n, torch.zeros_like(getattr(self, n)))
+            for pre in ("", "g", "m", "v"):
+                t = getattr(self, pre + n)
+                if n in ("P", "Q"):
+                    setattr(c, pre + n, t.data_ptr())
+                else:
+                    getattr(c, pre + n[0])[int(n[1:])] = t.data_ptr()
+        self.loss = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.step, self._image = 0, None
+
+    def _call(self, name, *args):
+        check(getattr(self.ctx.lib, name)(self.ctx.handle, self.ctx.stream(), C.byref(self._c), *args), name)
+
+    def ws_bytes(self, n, which):
+        need = int(self.ctx.lib.el_cnmf_ws_bytes(self.ctx.handle, C.byref(self._c), int(n), int(which)))
+        if need == 0:
+            raise _lib.ElliotHipError("el_cnmf_ws_bytes: " + self.ctx.lib.el_last_error().decode())
+        return need
+
+    def _ws(self, n, which):
+        need = self.ws_bytes(n, which)
+        return _ptr(workspace(self, "_ws%d" % which, need, self.ctx.device)), need
+
+    def _batch(self, u, i, j):
+        return _ptr(u, torch.int32, "u"), _ptr(i, torch.int32, "i"), _ptr(j, torch.int32, "j"), int(u.numel())
+
+    def touch(self):
+        """The variables changed: the next scores() rebuilds the item image."""
+        self._image = None
+
+    def grads(self, u, i, j):
+        """Loss and tape.gradient of train_step into the gradient buffers (g + name); the dropout masks are those of step + 1."""
+        self._call("el_cnmf_grads", *self._batch(u, i, j), int(self.step + 1), _ptr(self.loss, torch.float64),
+                   *self._ws(u.numel(), _lib.EL_CNMF_WS_STEP))
+
+    def apply(self, lr):
+        self.step += 1
+        self.touch()
+        self._call("el_cnmf_apply", int(self.step), float(adam_lr_t(lr, self.step)))
+
+    def train_step(self, u, i, j, lr):
+        self.step += 1
+        self.touch()
+        self._call("el_cnmf_train_step", *self._batch(u, i, j), int(self.step), float(adam_lr_t(lr, self.step)),
+                   _ptr(self.loss, torch.float64), *self._ws(u.numel(), _lib.EL_CNMF_WS_STEP))
+
+    def dropout_masks(self, step, B):
+        """[2, 2, B, C_L] (call, head layer, sample, unit): the factors the training calls of `step` apply (el_cnmf_dropout_masks)."""
+        out = torch.empty((2, 2, int(B), self.channels[-1]), dtype=torch.float32, device=self.ctx.device)
+        self._call("el_cnmf_dropout_masks", int(step), int(B), _ptr(out, torch.float32))
+        return out
+
+    def forward(self, u, i, out=None):
+        """x of `call` on the pairs, no dropout (el_cnmf_forward)."""
+        if out is None:
+            out = torch.empty(u.numel(), dtype=torch.float32, device=self.ctx.device)
+        self._call("el_cnmf_forward", _ptr(u, torch.int32, "u"), _ptr(i, torch.int32, "i"), int(u.numel()), _ptr(out, torch.float32),
+                   *self._ws(u.numel(), _lib.EL_CNMF_WS_FORWARD))
+        return out
+
+    def item_image(self):
+        """T [I, H_1 k_1 C_1] of the current Q and W1: computed once per change of the variables (el_cnmf_item_image)."""
+        if self._image is None:
+            h1 = (self.F - self.kernels[0]) // self.strides[0] + 1
+            self._image = torch.empty((self.I, h1 * self.kernels[0] * self.channels[1]), dtype=torch.float32, device=self.ctx.device)
+            self._call("el_cnmf_item_image", _ptr(self._image, torch.float32))
+        return self._image
+
+    def scores(self, u_start, u_stop, out=None):
+        """get_recs of the users [u_start, u_stop) against ALL items (el_cnmf_scores)."""
+        n = int(u_stop) - int(u_start)
+        ws = self._ws(n, _lib.EL_CNMF_WS_SCORES)                                              # (refusals come before the image)
+        if out is None:
+            out = torch.empty((n, self.I), dtype=torch.float32, device=self.ctx.device)
+        self._call("el_cnmf_scores", _ptr(self.item_image(), torch.float32), int(u_start), int(u_stop), _ptr(out, torch.float32),
+                   int(out.stride(0)), *ws)
+        return out
+
+    def recommend(self, u_start, u_stop, k, excl=None, cand=None):
+        return dense_topk(self.ctx, self.scores(u_start, u_stop), u_start, u_stop, k, excl=excl, cand=cand)
+
+    pop_loss = FismDeviceState.pop_loss
+
+
 # ------------------------------------------------------------------------------------------
 # graph propagation: LightGCN (graph_based/lightgcn) -- SURVEY 8f N3
 # ------------------------------------------------------------------------------------------

@@ -38,9 +38,10 @@ from .latent_factor_models.FM.factorization_machine import FM
 from .latent_factor_models.FISM.FISM import FISM
 from .neural.NAIS.nais import NAIS
 from .neural.DMF.deep_matrix_factorization import DMF
+from .neural.ConvNeuMF.convolutional_neural_matrix_factorization import ConvNeuMF
 
 __all__ = ["BaseRecommenderModel", "init_charger", "RecMixin", "BPRMF_batch", "BPRMF", "MultiVAE", "MultiDAE", "NeuMF", "GMF",
            "MF", "PMF", "FunkSVD", "LogisticMatrixFactorization", "LMF", "CML", "MF2020", "LightGCN", "NGCF", "ProxyRecommender",
            "ItemKNN", "UserKNN", "iALS", "WRMF", "EASER", "RP3beta", "Slim", "PureSVD",
            "AttributeItemKNN", "AttributeUserKNN", "VSM", "KaHFM", "SlopeOne", "BPRSlim", "ItemAutoRec", "UserAutoRec", "AMF",
-           "VBPR", "FM", "FISM", "NAIS", "DMF"]
+           "VBPR", "FM", "FISM", "NAIS", "DMF", "ConvNeuMF"]

@@ -683,6 +683,61 @@ int el_dmf_forward(el_ctx* ctx, void* stream, const el_dmf_state* st, const floa
 int el_dmf_scores(el_ctx* ctx, void* stream, const el_dmf_state* st, const float* P, const float* Q, int64_t u_start, int64_t u_stop,
                   float* Qt, int32_t qt_ready, float* out, int64_t ld, void* ws, size_t ws_bytes);
 
+/* ---- ConvNeuMF: outer-product neural CF (neural/ConvNeuMF; el_cnmf.hip) --------------------------------------------
+ * x_ui = Dense(1)(Dense(C_L)(sum over pixels of A_L)), A_l = relu(conv_l(A_(l-1)) + b_l), A_0[a, b] = P[u, a] Q[i, b]; VALID padding,
+ * kernel == stride in every layer.  Step: sum softplus(-clip(x_ui - x_uj, -80, 1e8)) + l_w (l2(p_u) + l2(q_i) + l2(q_j)) per triplet,
+ * Keras Adam: the sparse apply's arithmetic on every row of P and Q, TF's dense ApplyAdam on the conv and Dense variables.
+ * Supported: 1 <= n_layers <= 6, channels[0] == 1, 1 <= channels[l] <= 64, F <= 256, 1 <= kernels[l] == strides[l] <= 4, every map
+ * side >= 1; anything else is refused before a launch (el_last_error names "layers", "channels", "stride", "kernel" or "map").
+ * Entry points only: EL_ABI_VERSION stays.                                                                                         */
+#define EL_CNMF_WS_STEP 0      /* el_cnmf_ws_bytes: el_cnmf_grads / el_cnmf_train_step on n triplets */
+#define EL_CNMF_WS_FORWARD 1   /* el_cnmf_forward on n pairs */
+#define EL_CNMF_WS_SCORES 2    /* el_cnmf_scores on a chunk of n users */
+
+typedef struct el_cnmf_state {
+    int64_t U, I;
+    int32_t F, n_layers;                                /* embedding_size; conv layers L */
+    int32_t channels[7];                                /* channels[0] = 1, channels[l] = C_l */
+    int32_t kernels[6];  int32_t strides[6];
+    int32_t reserved;
+    float l_w;  float dropout;                          /* dropout_prob of the two head Dropout layers (training calls only) */
+    uint64_t seed;                                      /* of the dropout masks */
+    float* P;  float* Q;                                /* [U, F], [I, F] */
+    float* gP; float* gQ;                               /* dense gradient tables: rewritten by el_cnmf_grads, zero again after the apply */
+    float* mP; float* vP;  float* mQ;  float* vQ;
+    float* W[6];   float* b[6];                         /* Keras layout: conv kernel [k, k, C_(l-1), C_l], bias [C_l] */
+    float* gW[6];  float* gb[6];
+    float* mW[6];  float* vW[6];  float* mb[6];  float* vb[6];
+    float* D[4];                                        /* the head: Wd1 [C_L, C_L], bd1 [C_L], Wd2 [C_L, 1], bd2 [1] */
+    float* gD[4];  float* mD[4];  float* vD[4];
+} el_cnmf_state;
+
+/* Scratch of the call named by `which` (EL_CNMF_WS_*) for n triplets / pairs / users; 0 = refused (el_last_error says why). */
+size_t el_cnmf_ws_bytes(el_ctx* ctx, const el_cnmf_state* st, int64_t n, int32_t which);
+/* out[e] = x of `call` on the n pairs (u[e], i[e]); no dropout. */
+int el_cnmf_forward(el_ctx* ctx, void* stream, const el_cnmf_state* st, const int32_t* u, const int32_t* i, int64_t n, float* out,
+                    void* ws, size_t ws_bytes);
+/* Replaces the loss and tape.gradient of train_step on B triplets (u, i, j): every gradient buffer of the state is rewritten (gP, gQ
+ * whole), L is ADDED to loss_out (device double[1]).  The 2 B pairs (positive calls first) are split into contiguous ranges over a
+ * fixed number of workgroups; nothing per pixel is kept between the forward and the backward pass (recomputed).  No floating-point
+ * atomics: the same input gives the same bytes.  `step` picks the dropout masks (with dropout > 0).  Indices are not checked.       */
+int el_cnmf_grads(el_ctx* ctx, void* stream, const el_cnmf_state* st, const int32_t* u, const int32_t* i, const int32_t* j, int64_t B,
+                  int32_t step, double* loss_out, void* ws, size_t ws_bytes);
+/* Adam on every variable from the gradient buffers.  lr_t: the bias-corrected step size of `step`. */
+int el_cnmf_apply(el_ctx* ctx, void* stream, const el_cnmf_state* st, int32_t step, float lr_t);
+/* el_cnmf_grads followed by el_cnmf_apply: the same bits. */
+int el_cnmf_train_step(el_ctx* ctx, void* stream, const el_cnmf_state* st, const int32_t* u, const int32_t* i, const int32_t* j,
+                       int64_t B, int32_t step, float lr_t, double* loss_out, void* ws, size_t ws_bytes);
+/* image [I, H_1 k_1 C_1]: T_i[x, a, c] = sum_b W1[a, b, c] Q[i, k_1 x + b], the item side of layer 1.  It depends on Q and W1 only. */
+int el_cnmf_item_image(el_ctx* ctx, void* stream, const el_cnmf_state* st, float* image);
+/* Replaces get_recs for the users [u_start, u_stop) against ALL items: out[u - u_start, i] (ld >= I), for el_dense_topk.  `image` is
+ * what el_cnmf_item_image left for the current Q and W1; no dropout.                                                               */
+int el_cnmf_scores(el_ctx* ctx, void* stream, const el_cnmf_state* st, const float* image, int64_t u_start, int64_t u_stop, float* out,
+                   int64_t ld, void* ws, size_t ws_bytes);
+/* out [2, 2, B, C_L] (call 0 = positive / 1 = negative, head layer, sample, unit): the factors (0 or 1 / (1 - dropout)) the training
+ * calls of step `step` apply, from the device function they use.                                                                   */
+int el_cnmf_dropout_masks(el_ctx* ctx, void* stream, const el_cnmf_state* st, int32_t step, int64_t B, float* out);
+
 /* ---- BPR-MF, NumPy semantics (BPRMF; K5) ------------------------------------- */
 
 typedef struct el_bprsgd_state {
